@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the LaMP label-graph forward path on MI355X (the BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one forward pass of the hot path (LAMP.forward, eval mode) over one synthetic batch of
 the configuration the metric is quoted on: reuters-shaped, batch 32 per GPU, T = 302 fixed,
@@ -19,12 +19,22 @@ reference's single-process nn.DataParallel scatter (main.py:106-108).
 BASELINE.json configs[4] (4096 labels x 512 tokens, d_model 1024, batch 8192 over 8 GPUs) is
     python bench.py --gpus 8 --workload synthetic4096 --batch 1024 --steps 2 --warmup 1
 
-Rank 0 prints ONE JSON line with, besides the contract fields,
-  ranks_seen / per_rank   which ranks reported and each one's own samples/s,
+A plain run sets up, warms up, times exactly K steps and prints ONE JSON line (rank 0) with the contract fields (metric,
+value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step, ...), `config`, and
+  ranks_seen / per_rank   which ranks reported and each one's own samples/s.
+Under "nccl" rank 0 requires one physical device per rank (exit 5).
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0): DIR/logits.npy and DIR/enc_output.npy,
+float32, 64 MB at most in all (a larger array is written as a fixed, seeded sample of its elements; see dump_outputs).  The
+inputs and weights are seeded, so two runs with the same arguments -- of two builds, say -- can be compared file for file.
+
+--full adds everything else the benchmark measures and checks, each outside the timed region (the --no-* options below
+drop single legs of it):
+  step_ms_synced          per-step latency with a device synchronise after every step,
+  host_issue_us_per_forward  how long the host takes to enqueue one forward (also per rank),
   cross_rank_check        SURVEY.md 8e's contract, checked across real devices: every rank holds the SAME weights and
                           its OWN batch; after the timed region rank 0 re-runs the first samples of every other rank's
                           batch on its own device and compares the logits that rank computed bit for bit (exit 4 on a
-                          mismatch).  Under "nccl" rank 0 also requires one physical device per rank (exit 5),
+                          mismatch),
   roofline      the dominant kernel class (fp32-MFMA GEMM): algorithmic FLOPs of its launches divided
                 by their HIP-event durations (events recorded by liblamp_hip.so on the launch stream,
                 in an instrumented replay of the same K steps right after the timed region);
@@ -37,6 +47,8 @@ Rank 0 prints ONE JSON line with, besides the contract fields,
   workloads     (N = 1) the other GPU configurations of BASELINE.json -- bibtex, delicious, synthetic4096 --
                 each for a bounded number of steps: value, ms_per_step, GEMM roofline, attention TFLOP/s; and
                 reuters_ragged, the headline model on lengths U{20..302} (SURVEY.md 8d variant ii),
+  pipelined_batches_in_flight  samples/s with 2 and 4 independent batches in flight on round-robin streams,
+  training_step (N = 1) the reference's train-loop body, measured by tools/bench_train.py in a child process,
   cpu_baseline  the oracle (a port of the reference's op sequence, `as_written`, autograd graph
                 built as the reference's test loop does) timed on this host's cores on a bounded
                 sample (N = 1 only).
@@ -362,6 +374,32 @@ def warm_device(step, seconds=DEVICE_WARMUP_S):
     return n
 
 
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: all files of one run together stay below this
+DUMP_SEED = 0
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: write every tensor of `arrays` as path/<name>.npy, float32 (float64 stays float64).  Each array may
+    take an equal share of `budget`; a larger one is written as a 1-D sample: its flattened elements at sorted positions
+    drawn with seed DUMP_SEED, so that two runs with the same arguments write the same positions.  -> {name: shape written}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = budget // len(arrays) - 4096          # room for the .npy header
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        n = share // t.element_size()
+        if t.numel() > n:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(t.numel(), (n,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def csrc_fingerprint():
     """sha256 over the kernel sources (names and contents), first 16 hex digits: stamps a committed profile with the
     kernels it was measured on (there is no .git on the GPU box)."""
@@ -519,7 +557,8 @@ def roofline_of(prof, n_steps, workload, live=None, chain_gflop=None, pmc=None, 
 
 
 def measure(N, name, w, batch, steps, warmup, device, rank, sync, lengths=None, graph=False, n_max=None):
-    """Build one workload on `device`, warm up, time exactly `steps` steps between barriers.  -> dict."""
+    """Build one workload on `device`, warm up, time exactly `steps` steps between barriers.  -> dict; `out` is what the
+    last timed step returned (under --graph: the captured step's output tensors, which every replay rewrites)."""
     model, sd, adj, seq, pos = build(w, batch, device, seed=rank, lengths=lengths, n_max=n_max)
     src = (seq.to(device), pos.to(device))
 
@@ -542,14 +581,16 @@ def measure(N, name, w, batch, steps, warmup, device, rank, sync, lengths=None, 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        run()
+        last = run()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     sync()
+    if g is None:
+        out = last
     logits = out[0]
     assert torch.isfinite(logits).all(), 'non-finite logits'
     return dict(model=model, sd=sd, adj=adj, seq=seq, pos=pos, step=step, run=run, elapsed=elapsed,
-                device_warmup_steps=warm_n, graph=g)
+                device_warmup_steps=warm_n, graph=g, out=out)
 
 
 def device_identity(index):
@@ -649,7 +690,14 @@ def main():
                     help='A/B switch: the dense tile kernels for the label self-attention even where the decoder flags the label '
                          'graph as sparse and unstructured (LAMP.use_sparse_label_attention; synthetic4096)')
     ap.add_argument('--mask', default=None, choices=['prior', 'none', 'inveye'], help='override the workload label mask')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (logits, enc_output) as DIR/<name>.npy (rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: latency, host issue time, cross-rank check, pipelined batches, '
+                         'roofline / kernel figures and their profiler sub-runs, the other workloads, training step, CPU baseline')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     hostcpu.fit_intra_op_threads(int(os.environ.get('LOCAL_WORLD_SIZE', os.environ.get('WORLD_SIZE', '1'))))   # lamp_amd/hostcpu.py
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -698,17 +746,22 @@ def main():
     m = measure(N, args.workload, w, args.batch, args.steps, args.warmup, device, rank, cp.barrier, lengths=lengths,
                 graph=args.graph, n_max=n_max)
     model, step, run, my_elapsed = m['model'], m['step'], m['run'], m['elapsed']
+    if args.dump_outputs and rank == 0:
+        written = dump_outputs(args.dump_outputs, {'logits': m['out'][0], 'enc_output': m['out'][1]})
+        print('outputs of the last timed step -> %s: %s' % (args.dump_outputs, written), file=sys.stderr)
 
-    # host issue time per forward: how long the Python / ctypes side takes to ENQUEUE one forward (all its launches) while the
-    # device still has work queued -- what eight issue loops on one host compete with (outside the timed region)
-    torch.cuda.synchronize()
-    n_issue = min(args.steps, 50)
-    t_i = time.perf_counter()
-    for _ in range(n_issue):
-        run()
-    host_issue_us = (time.perf_counter() - t_i) / n_issue * 1e6
-    torch.cuda.synchronize()
-    cp.barrier()
+    host_issue_us = 0.0
+    if args.full:
+        # host issue time per forward: how long the Python / ctypes side takes to ENQUEUE one forward (all its launches) while
+        # the device still has work queued -- what eight issue loops on one host compete with (outside the timed region)
+        torch.cuda.synchronize()
+        n_issue = min(args.steps, 50)
+        t_i = time.perf_counter()
+        for _ in range(n_issue):
+            run()
+        host_issue_us = (time.perf_counter() - t_i) / n_issue * 1e6
+        torch.cuda.synchronize()
+        cp.barrier()
 
     # every rank reports (rank, device, elapsed, samples, tokens); rank 0 aggregates: total samples / max elapsed
     n_tok = float(sum(lengths)) if lengths else float(args.batch * w['T'])
@@ -721,67 +774,67 @@ def main():
     identity_strong = all(st for _, st in ident_rows)
     elapsed = max(r[2] for r in rows)
 
-    # ---- SURVEY.md 8e across ranks: same weights, different batches; rank 0 recomputes the first samples of every other
-    # rank's batch on ITS device and compares with what that rank computed, bit for bit ----
-    n_chk = min(args.batch, 64)
-    own = step()[0][:n_chk].detach().clone()
-    torch.cuda.synchronize()
-    theirs = cp.gather(own)
-    cross = None
-    if rank == 0 and world > 1:
-        from lamp_amd import synthetic as S
-        bad, worst = [], 0.0
-        for r in range(1, world):
-            w_r, len_r = batch_of_rank(args, w_base, r)
-            seq_r, pos_r = S.make_batch(args.batch, w_r['V'], w_r['T'], lengths=len_r, seed=r)
-            mine = model((seq_r[:n_chk].to(device), pos_r[:n_chk].to(device)), None, None, None)[0].cpu()
-            if not torch.equal(mine, theirs[r]):
-                bad.append(r)
-                worst = max(worst, float((mine.double() - theirs[r].double()).abs().max()))
-        cross = {'weights': 'identical on every rank (seed 0)', 'batches': 'rank r draws its batch with seed r',
-                 'recomputed_on': 'rank 0', 'ranks_checked': list(range(1, world)), 'samples_per_rank': n_chk,
-                 'bitwise_equal': not bad, 'mismatching_ranks': bad, 'max_abs_diff': worst}
-
-    # per-step latency with a device sync after every step (median and min), outside the timed region
-    lat = []
-    for _ in range(min(args.steps, 50)):
+    cross = lat = pipelined = None
+    if args.full:
+        # ---- SURVEY.md 8e across ranks: same weights, different batches; rank 0 recomputes the first samples of every other
+        # rank's batch on ITS device and compares with what that rank computed, bit for bit ----
+        n_chk = min(args.batch, 64)
+        own = step()[0][:n_chk].detach().clone()
         torch.cuda.synchronize()
-        ts = time.perf_counter()
-        run()
-        torch.cuda.synchronize()
-        lat.append((time.perf_counter() - ts) * 1e3)
-    lat.sort()
+        theirs = cp.gather(own)
+        if rank == 0 and world > 1:
+            from lamp_amd import synthetic as S
+            bad, worst = [], 0.0
+            for r in range(1, world):
+                w_r, len_r = batch_of_rank(args, w_base, r)
+                seq_r, pos_r = S.make_batch(args.batch, w_r['V'], w_r['T'], lengths=len_r, seed=r)
+                mine = model((seq_r[:n_chk].to(device), pos_r[:n_chk].to(device)), None, None, None)[0].cpu()
+                if not torch.equal(mine, theirs[r]):
+                    bad.append(r)
+                    worst = max(worst, float((mine.double() - theirs[r].double()).abs().max()))
+            cross = {'weights': 'identical on every rank (seed 0)', 'batches': 'rank r draws its batch with seed r',
+                     'recomputed_on': 'rank 0', 'ranks_checked': list(range(1, world)), 'samples_per_rank': n_chk,
+                     'bitwise_equal': not bad, 'mismatching_ranks': bad, 'max_abs_diff': worst}
 
-    # ---- throughput mode (reported beside `value`, never as `value`): successive batches issued round-robin
-    # on two HIP streams, so that one forward's launch gaps / ramp / tail are filled by the other's kernels.  Measured
-    # over a FIXED window (>= PIPELINED_WINDOW_S of device time, at least --steps steps), not over --steps iterations:
-    # a 20-step run would otherwise time 16 ms, most of it the two streams' ramp ----
-    pipelined = None
-    if not args.graph and not args.no_pipelined:
-        n_pipe = max(args.steps, int(PIPELINED_WINDOW_S / max(my_elapsed / args.steps, 1e-6)) + 1)
-        pipelined = {'unit': 'samples/s per GPU', 'steps': n_pipe, 'window_s': PIPELINED_WINDOW_S,
-                     'note': 'independent batches in flight on round-robin HIP streams (what evaluate.test_epoch(streams=n) '
-                             'does); latency per batch is NOT reduced'}
-        for depth in (2, 4):
-            streams = [torch.cuda.Stream(device=device) for _ in range(depth)]
-            for _ in range(2):
-                for st in streams:
-                    with torch.cuda.stream(st):
+        # per-step latency with a device sync after every step (median and min), outside the timed region
+        lat = []
+        for _ in range(min(args.steps, 50)):
+            torch.cuda.synchronize()
+            ts = time.perf_counter()
+            run()
+            torch.cuda.synchronize()
+            lat.append((time.perf_counter() - ts) * 1e3)
+        lat.sort()
+
+        # ---- throughput mode (reported beside `value`, never as `value`): successive batches issued round-robin
+        # on two HIP streams, so that one forward's launch gaps / ramp / tail are filled by the other's kernels.  Measured
+        # over a FIXED window (>= PIPELINED_WINDOW_S of device time, at least --steps steps), not over --steps iterations:
+        # a 20-step run would otherwise time 16 ms, most of it the two streams' ramp ----
+        if not args.graph and not args.no_pipelined:
+            n_pipe = max(args.steps, int(PIPELINED_WINDOW_S / max(my_elapsed / args.steps, 1e-6)) + 1)
+            pipelined = {'unit': 'samples/s per GPU', 'steps': n_pipe, 'window_s': PIPELINED_WINDOW_S,
+                         'note': 'independent batches in flight on round-robin HIP streams (what evaluate.test_epoch(streams=n) '
+                                 'does); latency per batch is NOT reduced'}
+            for depth in (2, 4):
+                streams = [torch.cuda.Stream(device=device) for _ in range(depth)]
+                for _ in range(2):
+                    for st in streams:
+                        with torch.cuda.stream(st):
+                            step()
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                for i in range(n_pipe):
+                    with torch.cuda.stream(streams[i % depth]):
                         step()
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for i in range(n_pipe):
-                with torch.cuda.stream(streams[i % depth]):
-                    step()
-            torch.cuda.synchronize()
-            e2 = time.perf_counter() - t1
-            pipelined['depth_%d' % depth] = {'value': args.batch * n_pipe / e2,
-                                              'ms_per_step_amortised': e2 / n_pipe * 1e3}
-        pipelined['value'] = pipelined['depth_2']['value']
-        pipelined['streams'] = 2
+                torch.cuda.synchronize()
+                e2 = time.perf_counter() - t1
+                pipelined['depth_%d' % depth] = {'value': args.batch * n_pipe / e2,
+                                                  'ms_per_step_amortised': e2 / n_pipe * 1e3}
+            pipelined['value'] = pipelined['depth_2']['value']
+            pipelined['streams'] = 2
 
-    prof_steps = min(args.steps, 20)
-    prof, kernels = profile_steps(N, step, prof_steps)
+        prof_steps = min(args.steps, 20)
+        prof, kernels = profile_steps(N, step, prof_steps)
 
     if rank != 0:
         cp.close()
@@ -795,31 +848,7 @@ def main():
     samples = sum(r[3] for r in rows)
     value = samples / elapsed
     ms_per_step = elapsed / args.steps * 1e3
-    fl = f_live(w)
     plain = not (args.ragged or args.mask)
-    live = None
-    if n_gpus == 1 and world == 1 and plain and not args.graph and not args.no_kernel_trace and args.batch <= 64:
-        live = live_kernel_trace(args)
-    # FLOPs of the decoder chain launches of one forward (lamp_amd/csrc/chain.hip; two per decoder layer, each the
-    # d x d output projection and the d -> d_ff -> d FFN over the B*L label rows)
-    # one chain per attention block of the decoder: n_layers_dec x (enc-dec attention + label self-attention unless
-    # no_dec_self_att); each = the (h d_v) -> d output projection and the d -> d_ff -> d FFN over the B * L label rows
-    rows_dec = args.batch * w['L']
-    dec = model.decoder.layer_stack
-    n_chains = sum(2 if hasattr(l, 'slf_attn') else 1 for l in dec)
-    hdv = dec[0].enc_attn.n_head * dec[0].enc_attn.d_v
-    chain_gflop = n_chains * (2.0 * rows_dec * hdv * w['d'] + 4.0 * rows_dec * w['d'] * w['dff']) / 1e9
-    pmc = None
-    if n_gpus == 1 and world == 1 and plain and not args.graph and not args.no_pmc and args.batch <= 64:
-        pmc = live_pmc(args)
-    roof = roofline_of(prof, prof_steps, args.workload if plain else None, live, chain_gflop, pmc, kernels.get('attention'))
-    if args.ragged and prof['gemm']['ms'] > 0:
-        # the launchers count the padded upper bound of the packed encoder's rows: use the real token count
-        gf = gemm_flops_per_step(w, args.batch, n_tok)
-        tf = gf * prof_steps / (prof['gemm']['ms'] * 1e-3) / 1e12
-        roof.update(achieved=tf, frac=tf / PEAK_FP32_MFMA_TFLOPS, algorithmic_gflop_per_step=gf / 1e9,
-                    flops_source='analytic, real token count %d of %d padded positions' % (n_tok, args.batch * w['T']))
-        kernels['gemm']['tflops'] = tf
     # what the model object computed ONCE per weight version, outside every forward (all of it a function of the weights alone)
     from lamp_amd.Models import LAMP as _LAMP
     fx_head, fx_head_sub = executed_flops(w, model)
@@ -834,19 +863,15 @@ def main():
         'metric': 'forward samples/sec, reuters d512 2+2L 4h' if args.workload == 'reuters' else
                   'forward samples/sec, %s d%d 2+2L %dh' % (args.workload, w['d'], w['h']),
         'value': value, 'unit': 'samples/s', 'n_gpus': n_gpus, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': ms_per_step, 'step_ms_synced': {'median': lat[len(lat) // 2], 'min': lat[0], 'n': len(lat)},
+        'ms_per_step': ms_per_step,
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
         'dtype': 'f32', 'data': 'synthetic',
         'ranks_seen': ranks_seen,
         'per_rank': [{'rank': int(r[0]), 'device': int(r[1]), 'device_identity': identities[int(r[0])],
                       'value': r[3] / r[2], 'ms_per_step': r[2] / args.steps * 1e3, 'tokens_per_batch': int(r[4]),
-                      'padded_length': int(r[5]), 'host_issue_us_per_forward': r[6],
-                      'host_issue_frac_of_step': r[6] / (r[2] / args.steps * 1e6),
-                      'cpu_affinity': affinities[int(r[0])]} for r in sorted(rows)],
-        'host_issue_us_per_forward': max(r[6] for r in rows),
+                      'padded_length': int(r[5]), 'cpu_affinity': affinities[int(r[0])]} for r in sorted(rows)],
         'physical_devices': physical, 'physical_devices_from': 'pci/uuid' if identity_strong else 'host/visibility/index (weak)',
         'backend': cp.backend, 'control_plane_ranks': cp.ranks_in_group(),
-        'cross_rank_check': cross,
         'config': {'workload': '%s: batch %d/GPU, T=%d %s, L=%d, d_model=%d, d_ff=%d, 2 enc + 2 dec graph layers, '
                                '%d heads, label_mask=%s, fp32' %
                                (args.workload, args.batch, w['T'],
@@ -864,26 +889,59 @@ def main():
                    'host_threads': {'torch_default': TORCH_DEFAULT_THREADS, 'intra_op_fitted_to_cpu_quota': torch.get_num_threads(),
                                     'usable_cores': hostcpu.usable_cores()},
                    },
-        'roofline': roof,
-        'forward': {
-            'f_live_gflop_per_sample': fl / 1e9,
-            'achieved_tflops_per_gpu': value / n_gpus * fl / 1e12,
-            'frac_of_fp32_mfma_peak': value / n_gpus * fl / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-            'executed_gflop_per_sample': fx_head / 1e9,
-            'executed_frac_of_fp32_mfma_peak': value / n_gpus * fx_head / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-            'not_executed_gflop_per_sample': {k: x / 1e9 for k, x in fx_head_sub.items()},
-            'kernel_time_us_per_step': sum(k['us_per_step'] for k in kernels.values()),
-            'kernel_time_note': 'HIP-event durations of an INSTRUMENTED replay (an event pair around every launch adds '
-                                '~2-3 us per kernel): the sum may exceed ms_per_step; rocprofv3 kernel-only figures are '
-                                'under profiles/',
-        },
-        'kernels': kernels,
-        'kernel_trace': live,
-        'pmc': pmc,
-        'pipelined_batches_in_flight': pipelined,
     }
 
-    if n_gpus == 1 and not args.no_extra_workloads and args.workload == 'reuters' and plain:
+    if args.full:
+        fl = f_live(w)
+        live = None
+        if n_gpus == 1 and world == 1 and plain and not args.graph and not args.no_kernel_trace and args.batch <= 64:
+            live = live_kernel_trace(args)
+        # FLOPs of the decoder chain launches of one forward (lamp_amd/csrc/chain.hip; two per decoder layer, each the
+        # d x d output projection and the d -> d_ff -> d FFN over the B*L label rows)
+        # one chain per attention block of the decoder: n_layers_dec x (enc-dec attention + label self-attention unless
+        # no_dec_self_att); each = the (h d_v) -> d output projection and the d -> d_ff -> d FFN over the B * L label rows
+        rows_dec = args.batch * w['L']
+        dec = model.decoder.layer_stack
+        n_chains = sum(2 if hasattr(l, 'slf_attn') else 1 for l in dec)
+        hdv = dec[0].enc_attn.n_head * dec[0].enc_attn.d_v
+        chain_gflop = n_chains * (2.0 * rows_dec * hdv * w['d'] + 4.0 * rows_dec * w['d'] * w['dff']) / 1e9
+        pmc = None
+        if n_gpus == 1 and world == 1 and plain and not args.graph and not args.no_pmc and args.batch <= 64:
+            pmc = live_pmc(args)
+        roof = roofline_of(prof, prof_steps, args.workload if plain else None, live, chain_gflop, pmc, kernels.get('attention'))
+        if args.ragged and prof['gemm']['ms'] > 0:
+            # the launchers count the padded upper bound of the packed encoder's rows: use the real token count
+            gf = gemm_flops_per_step(w, args.batch, n_tok)
+            tf = gf * prof_steps / (prof['gemm']['ms'] * 1e-3) / 1e12
+            roof.update(achieved=tf, frac=tf / PEAK_FP32_MFMA_TFLOPS, algorithmic_gflop_per_step=gf / 1e9,
+                        flops_source='analytic, real token count %d of %d padded positions' % (n_tok, args.batch * w['T']))
+            kernels['gemm']['tflops'] = tf
+        for p, r in zip(result['per_rank'], sorted(rows)):
+            p.update(host_issue_us_per_forward=r[6], host_issue_frac_of_step=r[6] / (r[2] / args.steps * 1e6))
+        result.update({
+            'step_ms_synced': {'median': lat[len(lat) // 2], 'min': lat[0], 'n': len(lat)},
+            'host_issue_us_per_forward': max(r[6] for r in rows),
+            'cross_rank_check': cross,
+            'roofline': roof,
+            'forward': {
+                'f_live_gflop_per_sample': fl / 1e9,
+                'achieved_tflops_per_gpu': value / n_gpus * fl / 1e12,
+                'frac_of_fp32_mfma_peak': value / n_gpus * fl / 1e12 / PEAK_FP32_MFMA_TFLOPS,
+                'executed_gflop_per_sample': fx_head / 1e9,
+                'executed_frac_of_fp32_mfma_peak': value / n_gpus * fx_head / 1e12 / PEAK_FP32_MFMA_TFLOPS,
+                'not_executed_gflop_per_sample': {k: x / 1e9 for k, x in fx_head_sub.items()},
+                'kernel_time_us_per_step': sum(k['us_per_step'] for k in kernels.values()),
+                'kernel_time_note': 'HIP-event durations of an INSTRUMENTED replay (an event pair around every launch adds '
+                                    '~2-3 us per kernel): the sum may exceed ms_per_step; rocprofv3 kernel-only figures are '
+                                    'under profiles/',
+            },
+            'kernels': kernels,
+            'kernel_trace': live,
+            'pmc': pmc,
+            'pipelined_batches_in_flight': pipelined,
+        })
+
+    if args.full and n_gpus == 1 and not args.no_extra_workloads and args.workload == 'reuters' and plain:
         # the other GPU configurations of BASELINE.json, bounded; the headline model is dropped first
         sd_h, adj_h, seq_h, pos_h = m['sd'], m['adj'], m['seq'], m['pos']
         del model, step, run
@@ -936,7 +994,7 @@ def main():
         result['training_step'] = training_step_line()
         m.update(sd=sd_h, adj=adj_h, seq=seq_h, pos=pos_h)
 
-    if n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and n_gpus == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(w, m['sd'], m['adj'], m['seq'], m['pos'], args.cpu_budget)
         result['cpu_baseline'] = cb
         result['speedup_vs_cpu_as_written'] = value / cb['value']

@@ -47,7 +47,7 @@ def test_bench_spawns_its_own_ranks(dev):
     assert r1.returncode == 0, r1.stderr[-2000:]
     assert one['n_gpus'] == 1 and one['ranks_seen'] == [0] and len(one['per_rank']) == 1
     assert one['metric'] == 'forward samples/sec, reuters d512 2+2L 4h' and one['steps'] == 5 and one['unit'] == 'samples/s'
-    r2, two = _bench(['--gpus', '2'] + common, {'LAMP_BENCH_BACKEND': 'gloo'})
+    r2, two = _bench(['--gpus', '2', '--full'] + common, {'LAMP_BENCH_BACKEND': 'gloo'})
     assert r2.returncode == 0, r2.stderr[-2000:]
     assert two['n_gpus'] == 2 and two['ranks_seen'] == [0, 1] and len(two['per_rank']) == 2
     assert two['config']['launcher'] == 'self-spawned ranks' and two['physical_devices'] == 1
@@ -56,7 +56,7 @@ def test_bench_spawns_its_own_ranks(dev):
     assert two['cross_rank_check']['bitwise_equal'] is True and two['cross_rank_check']['ranks_checked'] == [1]
     assert two['per_rank'][0]['device_identity'] == two['per_rank'][1]['device_identity']
     # ragged batches: the two ranks pad to DIFFERENT lengths; the samples still come out bit-identical on rank 0
-    r2r, rag = _bench(['--gpus', '2', '--ragged'] + common, {'LAMP_BENCH_BACKEND': 'gloo'})
+    r2r, rag = _bench(['--gpus', '2', '--ragged', '--full'] + common, {'LAMP_BENCH_BACKEND': 'gloo'})
     assert r2r.returncode == 0, r2r.stderr[-2000:]
     assert rag['per_rank'][0]['padded_length'] != rag['per_rank'][1]['padded_length']
     assert rag['cross_rank_check']['bitwise_equal'] is True
@@ -84,7 +84,7 @@ def test_bench_kernel_only_fraction_is_measured_in_the_run(dev):
     """roofline.frac_kernel_only comes from a rocprofv3 --kernel-trace --stats sub-run of the same invocation (N = 1), not
     from a committed file: the trace must be there, count every forward, and its GEMM-class time must be below the
     instrumented HIP-event time the plain `frac` uses."""
-    r, out = _bench(['--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-pipelined', '--no-extra-workloads'])
+    r, out = _bench(['--steps', '20', '--warmup', '5', '--full', '--no-cpu-baseline', '--no-pipelined', '--no-extra-workloads'])
     assert r.returncode == 0, r.stderr[-2000:]
     kt, roof = out['kernel_trace'], out['roofline']
     assert kt and 'skipped' not in kt, kt
@@ -120,7 +120,7 @@ def test_bench_and_eval_with_eight_ranks_on_one_device(dev, tmp_path):
     """The rank count the driver's scaling run uses (batch shards over 8 GPUs), as far as one GPU allows:
     eight self-spawned ranks over gloo sharing this box's device -- every rank reports, rank 0 recomputes the first samples
     of ranks 1..7 bit for bit (fixed and ragged batches), and the aggregate is all samples over the slowest rank."""
-    common = ['--steps', '5', '--warmup', '2', '--no-cpu-baseline', '--no-pipelined', '--no-extra-workloads', '--no-kernel-trace']
+    common = ['--steps', '5', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-pipelined', '--no-extra-workloads', '--no-kernel-trace']
     for extra in ([], ['--ragged']):
         r, out = _bench(['--gpus', '8'] + extra + common, {'LAMP_BENCH_BACKEND': 'gloo'})
         assert r.returncode == 0, r.stderr[-2000:]
@@ -159,13 +159,38 @@ def _assert_contract(line, n, steps, warmup, workload='reuters'):
     assert abs(line['value'] - n * batch / (line['ms_per_step'] * 1e-3)) < 1e-6 * line['value']   # whole job / slowest rank
 
 
+FULL_ONLY_KEYS = ('step_ms_synced', 'host_issue_us_per_forward', 'cross_rank_check', 'roofline', 'forward', 'kernels',
+                  'kernel_trace', 'pmc', 'pipelined_batches_in_flight', 'workloads', 'training_step', 'cpu_baseline')
+
+
+def test_plain_bench_line_is_the_headline_only_and_dumps_the_last_step(dev, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` measures the headline and nothing else; with --dump-outputs it writes what the
+    last timed step returned, the same from run to run, and equal to the model's forward on bench.build's seeded batch."""
+    import numpy as np
+    import bench
+    for d in ('a', 'b'):
+        r, line = _bench(['--gpus', '1', '--steps', '7', '--warmup', '2', '--dump-outputs', str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        _assert_contract(line, 1, 7, 2)
+        assert not set(FULL_ONLY_KEYS) & set(line), sorted(set(FULL_ONLY_KEYS) & set(line))
+    a = {k: np.load(str(tmp_path / 'a' / (k + '.npy'))) for k in ('logits', 'enc_output')}
+    assert a['logits'].shape == (32, 90) and a['enc_output'].shape == (32, 302, 512)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    for k, v in a.items():
+        assert np.array_equal(np.load(str(tmp_path / 'b' / (k + '.npy'))), v), k
+    model, sd, adj, seq, pos = bench.build(dict(bench.WORKLOADS['reuters']), 32, dev)
+    logits, enc, _ = model((seq.to(dev), pos.to(dev)), None, None, None)
+    assert np.abs(logits.detach().cpu().numpy() - a['logits']).max() <= 1e-5
+    assert np.abs(enc.detach().cpu().numpy() - a['enc_output']).max() <= 1e-5
+
+
 def test_the_drivers_scaling_commands_rehearsed_on_one_device(dev):
     """the exact launches of the round-end scaling run -- `python bench.py --gpus 1 ...` and, for N = 2, 4, 8,
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
     --steps K --warmup W` -- with the N ranks sharing this box's one device over gloo (RCCL refuses two ranks on one device),
-    plus BASELINE configs[4]'s command at a batch that fits eight ranks on one device.  Every line must parse and satisfy the
-    contract; the N = 1 line carries roofline and cpu_baseline; with no RCCL the reason is in config.backend_note."""
-    r1, one = _bench(['--gpus', '1', '--steps', '5', '--warmup', '2', '--no-pipelined', '--cpu-budget', '4'])
+    plus BASELINE configs[4]'s command at a batch that fits eight ranks on one device, each with --full.  Every line must parse
+    and satisfy the contract; the N = 1 line carries roofline and cpu_baseline; with no RCCL the reason is in config.backend_note."""
+    r1, one = _bench(['--gpus', '1', '--steps', '5', '--warmup', '2', '--full', '--no-pipelined', '--cpu-budget', '4'])
     assert r1.returncode == 0, r1.stderr[-2000:]
     _assert_contract(one, 1, 5, 2)
     roof, cpu = one['roofline'], one['cpu_baseline']
@@ -188,7 +213,7 @@ def test_the_drivers_scaling_commands_rehearsed_on_one_device(dev):
         return json.loads(lines[0])
     values = {1: one['value']}
     for n, port in ((2, 29531), (4, 29532), (8, 29533)):
-        line = launched(n, ['--steps', '5', '--warmup', '2'], port)
+        line = launched(n, ['--steps', '5', '--warmup', '2', '--full'], port)
         _assert_contract(line, n, 5, 2)
         assert line['config']['launcher'] == 'torch.distributed.run' and line['backend'] == 'gloo'
         assert 'backend_note' in line['config']                    # the reason when an RCCL group was wanted and could not start
@@ -197,7 +222,7 @@ def test_the_drivers_scaling_commands_rehearsed_on_one_device(dev):
         values[n] = line['value']
     # one device shared by N ranks: the aggregate must not collapse (the ranks' forwards interleave on the device)
     assert all(values[n] > 0.5 * values[1] for n in (2, 4, 8)), values
-    c5 = launched(8, ['--workload', 'synthetic4096', '--batch', '4', '--steps', '2', '--warmup', '1'], 29534)
+    c5 = launched(8, ['--workload', 'synthetic4096', '--batch', '4', '--steps', '2', '--warmup', '1', '--full'], 29534)
     _assert_contract(c5, 8, 2, 1, workload='synthetic4096')
     assert c5['metric'] == 'forward samples/sec, synthetic4096 d1024 2+2L 8h' and c5['config']['batch_per_gpu'] == 4
     assert c5['cross_rank_check']['bitwise_equal'] is True

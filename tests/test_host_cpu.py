@@ -176,6 +176,27 @@ def test_bench_counts_executed_flops_not_f_live():
     assert 0 < fx5 < bench.f_live(w5)
 
 
+def test_bench_dump_outputs_stays_within_budget_and_samples_the_same_positions(tmp_path):
+    """bench.py --dump-outputs: float32 (float64 kept), an array over its share of the budget written as a seeded sample
+    of its elements, the same positions from call to call, all files together within the budget."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(1)
+    small = torch.randn(4, 9, generator=g, dtype=torch.float64)
+    big = torch.randn(3, 50, 70, generator=g).half()
+    budget = 2 * (4096 + 4000)
+    shapes = bench.dump_outputs(str(tmp_path / 'a'), {'logits': small, 'enc_output': big}, budget=budget)
+    assert shapes == {'logits': [4, 9], 'enc_output': [1000]}
+    a = {k: np.load(str(tmp_path / 'a' / (k + '.npy'))) for k in shapes}
+    assert a['logits'].dtype == np.float64 and np.array_equal(a['logits'], small.numpy())
+    assert a['enc_output'].dtype == np.float32
+    assert sum(os.path.getsize(str(tmp_path / 'a' / (k + '.npy'))) for k in shapes) <= budget
+    idx = torch.randint(big.numel(), (1000,), generator=torch.Generator().manual_seed(bench.DUMP_SEED)).sort().values
+    assert np.array_equal(a['enc_output'], big.float().reshape(-1)[idx].numpy())
+    bench.dump_outputs(str(tmp_path / 'b'), {'logits': small, 'enc_output': big}, budget=budget)
+    assert np.array_equal(np.load(str(tmp_path / 'b' / 'enc_output.npy')), a['enc_output'])
+
+
 def test_pack_mask_bits_layout():
     g = torch.Generator().manual_seed(0)
     blocked = (torch.rand(70, 100, generator=g) < 0.5).to(torch.uint8)

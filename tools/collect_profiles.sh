@@ -9,17 +9,17 @@ OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 python -c "import bench; print(bench.csrc_fingerprint())" > "$OUT/csrc_fingerprint.txt"
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra-workloads > "$OUT/bench_driver_style_20steps.json" 2>/dev/null
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra-workloads > "$OUT/bench_driver_style_20steps.json" 2>/dev/null
 for wl in bibtex delicious; do
-  python bench.py --workload $wl --steps 50 --warmup 5 --no-cpu-baseline > "$OUT/bench_$wl.json" 2>/dev/null
+  python bench.py --full --workload $wl --steps 50 --warmup 5 --no-cpu-baseline > "$OUT/bench_$wl.json" 2>/dev/null
 done
-python bench.py --workload synthetic4096 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench_synthetic4096.json" 2>/dev/null
-python bench.py --ragged --no-cpu-baseline > "$OUT/bench_reuters_ragged.json" 2>/dev/null
-python bench.py --workload synthetic4096 --batch 1024 --steps 2 --warmup 1 --no-cpu-baseline --no-pipelined > "$OUT/bench_synthetic4096_b1024.json" 2>/dev/null
-python bench.py --workload synthetic4096 --mask none --steps 3 --warmup 1 --no-cpu-baseline --no-pipelined > "$OUT/bench_synthetic4096_none.json" 2>/dev/null
-LAMP_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 50 --warmup 5 --no-pipelined > "$OUT/bench_two_ranks_one_gpu_gloo.json" 2>/dev/null
-LAMP_BENCH_BACKEND=gloo python bench.py --gpus 2 --ragged --steps 50 --warmup 5 --no-pipelined > "$OUT/bench_two_ranks_one_gpu_gloo_ragged.json" 2>/dev/null
+python bench.py --full --workload synthetic4096 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench_synthetic4096.json" 2>/dev/null
+python bench.py --full --ragged --no-cpu-baseline > "$OUT/bench_reuters_ragged.json" 2>/dev/null
+python bench.py --full --workload synthetic4096 --batch 1024 --steps 2 --warmup 1 --no-cpu-baseline --no-pipelined > "$OUT/bench_synthetic4096_b1024.json" 2>/dev/null
+python bench.py --full --workload synthetic4096 --mask none --steps 3 --warmup 1 --no-cpu-baseline --no-pipelined > "$OUT/bench_synthetic4096_none.json" 2>/dev/null
+LAMP_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 50 --warmup 5 --no-pipelined > "$OUT/bench_two_ranks_one_gpu_gloo.json" 2>/dev/null
+LAMP_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --ragged --steps 50 --warmup 5 --no-pipelined > "$OUT/bench_two_ranks_one_gpu_gloo_ragged.json" 2>/dev/null
 python tools/check_rccl_control_plane.py > "$OUT/rccl_control_plane_one_rank.txt" 2>&1
 python tools/bench_eval_epoch.py > "$OUT/eval_epoch_end_to_end.json" 2>/dev/null
 python tools/bench_kernels.py gemm_ab 2>&1 | grep -v amdgpu.ids > "$OUT/gemm_tiles.txt"
@@ -27,7 +27,7 @@ python tools/bench_kernels.py gemm 2>&1 | grep -v amdgpu.ids > "$OUT/gemm_tiles_
 python tools/bench_kernels.py attn 2>&1 | grep -v amdgpu.ids > "$OUT/attn_variants.txt"
 python tools/bench_kernels.py sparse_rows 2>&1 | grep -v amdgpu.ids > "$OUT/sparse_label_attention.txt"
 python tools/bench_kernels.py sparse 2>&1 | grep -v amdgpu.ids >> "$OUT/sparse_label_attention.txt"
-python bench.py --workload synthetic4096 --steps 3 --warmup 1 --no-cpu-baseline --no-pipelined --no-sparse-label-attention > "$OUT/bench_synthetic4096_dense_label_attention.json" 2>/dev/null
+python bench.py --full --workload synthetic4096 --steps 3 --warmup 1 --no-cpu-baseline --no-pipelined --no-sparse-label-attention > "$OUT/bench_synthetic4096_dense_label_attention.json" 2>/dev/null
 # same-box A/B of the weights-only embedding fold (round 6), three round-robin rounds per workload
 AB_STEPS=200 bash tools/ab_flags.sh "$TAG" "" "" "--no-embed-fold" > /dev/null
 AB_STEPS=200 bash tools/ab_flags.sh "$TAG" "--ragged" "" "--no-embed-fold" > /dev/null
@@ -43,9 +43,9 @@ tools/probes/lds_dma_oob > "$OUT/lds_dma_oob.txt" 2>&1
 python tools/bench_kernels.py attn_tile 2>&1 | grep -v amdgpu.ids > "$OUT/attn_tile.txt"
 python tools/batch_sweep.py > "$OUT/batch_sweep.txt" 2>/dev/null
 tools/probes/mfma_issue 20 > "$OUT/mfma_issue.txt" 2>&1
-LAMP_BENCH_BACKEND=gloo python bench.py --gpus 8 --steps 20 --warmup 5 --no-pipelined > "$OUT/bench_eight_ranks_one_gpu_gloo.json" 2>/dev/null
-LAMP_BENCH_BACKEND=gloo python bench.py --gpus 8 --ragged --steps 20 --warmup 5 --no-pipelined > "$OUT/bench_eight_ranks_one_gpu_gloo_ragged.json" 2>/dev/null
-BENCH="python $PWD/bench.py --no-cpu-baseline --no-pipelined --no-extra-workloads"
+LAMP_BENCH_BACKEND=gloo python bench.py --full --gpus 8 --steps 20 --warmup 5 --no-pipelined > "$OUT/bench_eight_ranks_one_gpu_gloo.json" 2>/dev/null
+LAMP_BENCH_BACKEND=gloo python bench.py --full --gpus 8 --ragged --steps 20 --warmup 5 --no-pipelined > "$OUT/bench_eight_ranks_one_gpu_gloo_ragged.json" 2>/dev/null
+BENCH="python $PWD/bench.py --full --no-cpu-baseline --no-pipelined --no-extra-workloads"
 ( cd /tmp && rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o p -f csv -- $BENCH --steps 100 --warmup 10 > "$OUT/bench_under_rocprof.json" 2>/dev/null )
 ( cd /tmp && rocprofv3 --kernel-trace --stats -d "$OUT/stats_ragged" -o p -f csv -- $BENCH --ragged --steps 100 --warmup 10 > "$OUT/bench_ragged_under_rocprof.json" 2>/dev/null )
 # PMC passes are separate runs, each with --kernel-trace only (never combined with other trace domains)

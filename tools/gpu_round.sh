@@ -16,7 +16,7 @@ for w in $WHAT; do
       timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q --maxfail=40 -k "sdpa or mha or model_golden or baseline or bitwise or maps" -p no:cacheprovider > "$OUT/pytest_attn.log" 2>&1
       echo "pytest rc=$?" >> "$OUT/pytest_attn.log"; tail -25 "$OUT/pytest_attn.log" ;;
     bench)
-      timeout 600 python bench.py --steps 100 --warmup 10 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+      timeout 600 python bench.py --full --steps 100 --warmup 10 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
       python - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -33,7 +33,7 @@ print('  cpu', d.get('cpu_baseline', {}).get('value'))
 PY
       ;;
     ragged)
-      timeout 300 python bench.py --ragged --steps 200 --warmup 20 --no-cpu-baseline --no-extra-workloads > "$OUT/bench_ragged.json" 2> "$OUT/bench_ragged.err"; echo "ragged rc=$?"
+      timeout 300 python bench.py --full --ragged --steps 200 --warmup 20 --no-cpu-baseline --no-extra-workloads > "$OUT/bench_ragged.json" 2> "$OUT/bench_ragged.err"; echo "ragged rc=$?"
       python -c "import json,sys; d=json.load(open(sys.argv[1])); print('ragged value %.0f samples/s  ms/step %.4f  pipelined %s' % (d['value'], d['ms_per_step'], d['pipelined_batches_in_flight'] and round(d['pipelined_batches_in_flight']['value'])))" "$OUT/bench_ragged.json" ;;
     attn) timeout 300 python tools/bench_kernels.py attn 2>&1 | grep -v amdgpu.ids > "$OUT/attn_variants.txt"; grep -E "mode=0" "$OUT/attn_variants.txt" ;;
     trace) timeout 300 python tools/bench_kernels.py gemm_trace 2>&1 | grep -v amdgpu.ids > "$OUT/gemm_trace.txt"; cat "$OUT/gemm_trace.txt" ;;

@@ -1,7 +1,7 @@
 #!/bin/bash
 set -u
 OUT=$PWD/gpurun_out/${1:-r05n}; mkdir -p $OUT; export TMPDIR=/tmp
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
