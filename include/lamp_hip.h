@@ -466,6 +466,63 @@ int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src
                  int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux,
                  void* workspace, size_t workspace_bytes, lamp_stream_t stream);
 
+/* ---- the one-hot genomics encoder (GraphEncoder(onehot=True), lamp/Encoders.py:46-51,68-73) ----------------------
+ * For src_seq / src_pos int64 [B, T] over a vocabulary of n_vocab (9) symbols, with T2 = T / 2:
+ *   y1 = conv1(E[src]^T)[:, :, :T]            Conv1d(n_vocab, d, 16, padding 8)
+ *   P  = max_pool1d(relu(dropout(y1)), 2, 2)   [B, T2, d]
+ *   X  = relu(conv2(P)[:, :, :T2])^T + position_enc(src_pos[:, :T2])   Conv1d(d, d, 16, padding 8) -> the encoder's rows
+ * and src_seq[:, :T2] is the key-padding source of the encoder and of the enc-dec attention.  conv1's input is one-hot, so it
+ * is a gather from the weights-only tap table t1[v][t][:] = sum_ci E[v][ci] conv1_w[:][ci][t] (the caller builds it once per
+ * weight version).  conv2_pack (nullable): conv2_w repacked [co][t][ci] by lamp_conv_pack(flip 0); without it every forward
+ * repacks into its workspace.  16-byte aligned pointers, d_model % 4 == 0. */
+typedef struct lamp_onehot_frontend {
+    const float* t1;          /* [n_vocab, 16, d_model] */
+    const float* conv1_b;     /* [d_model] */
+    const float* conv2_w;     /* [d_model, d_model, 16] (Conv1d layout; may be NULL when conv2_pack is given) */
+    const float* conv2_b;     /* [d_model] */
+    const float* conv2_pack;  /* [d_model, 16, d_model] or NULL */
+    int32_t n_vocab;          /* <= 16 */
+    int32_t taps;             /* 16 */
+} lamp_onehot_frontend;
+
+/* lamp_forward with the one-hot front end in place of the embedding gather: logits [B, n_labels], enc_output [B, T2, d_model].
+ * m describes the encoder layers and the decoder as for lamp_forward (m->position_enc required, m->enc0_emb_w1 NULL).  The
+ * encoder runs the padded layout (T2 depends on the padded length, so padding is part of the result); a sample's outputs do
+ * not depend on B or on the micro-batch split, bit for bit, at a fixed T.  conv2 is counted in LAMP_K_GEMM. */
+size_t lamp_onehot_forward_workspace_bytes(const lamp_model* m, const lamp_onehot_frontend* fe, int32_t micro_batch, int32_t T,
+                                           int32_t want_attn);
+int lamp_onehot_forward(const lamp_model* m, const lamp_onehot_frontend* fe, const int64_t* src_seq, const int64_t* src_pos,
+                        int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
+                        size_t workspace_bytes, lamp_stream_t stream);
+
+/* Building blocks of the one-hot encoder (training, module-by-module use).  Padded layout "xpad": [B * (T2 + 16) + 16, d]
+ * rows, sample b's row q at b * (T2 + 16) + 8 + q, every other row 0.
+ *   lamp_conv_pack:        flip 0: packed[co][t][ci] = w[co][ci][t];  flip 1: packed[ci][t][co] = w[co][ci][taps - 1 - t].
+ *   lamp_onehot_front_fwd: xpad of P (above); dropout_p > 0: lamp_dropout's counter-based mask on y1, element
+ *                          (b * T + p) * d_model + c (channel-last).
+ *   lamp_conv_window_fwd:  out[b * rows_out + q][n] = act(sum_{t < 16, ci} x[(b * rows_in + q + t) * c_in + ci] w_pack[n][t][ci]
+ *                          + bias[n]) + pos_table[src_pos[b * pos_ld + q]][n]  (bias, pos_table, relu_out nullable; relu_out
+ *                          gets act(...) before the position row).  Every output row reads 16 input rows, so rows_in >=
+ *                          rows_out + 15 (else LAMP_E_DIMS) and x must hold (B - 1) * rows_in + rows_out + 15 rows.
+ *                          conv2 forward: x = xpad, rows_out = T2, rows_in = T2 + 16;
+ *                          its input gradient: x = the padded dZ + one row, w_pack = the flip-1 repack.
+ *   lamp_conv_relu_bwd_pad: dz (xpad layout) = dy * (relu_out > 0), dy / relu_out [B * rows, d].
+ *   lamp_onehot_front_bwd: from dP [B, T2, d] (the gradient of P): dz [B, T, d] = the gradient of y1, and partials
+ *                          (lamp_onehot_front_bwd_partials_bytes) whose column sums (lamp_colsum over n_vocab * 16 * d
+ *                          columns) are the gradient of t1; dz's column sums are conv1's bias gradient.  Deterministic. */
+int lamp_conv_pack(const float* w, int32_t c_out, int32_t c_in, int32_t taps, int32_t flip, float* packed, lamp_stream_t stream);
+int lamp_onehot_front_fwd(const int64_t* src_seq, int32_t B, int32_t T, const lamp_onehot_frontend* fe, int32_t d_model,
+                          float dropout_p, uint32_t seed, float* xpad, lamp_stream_t stream);
+int lamp_conv_window_fwd(const float* xpad, int32_t B, int32_t rows_out, int32_t rows_in, int32_t c_in, const float* w_pack,
+                         int32_t c_out, const float* bias, int32_t relu, const float* pos_table, int32_t n_position,
+                         const int64_t* src_pos, int64_t pos_ld, float* out, float* relu_out, lamp_stream_t stream);
+int lamp_conv_relu_bwd_pad(const float* dy, const float* relu_out, int32_t B, int32_t rows, int32_t d, float* dz,
+                           lamp_stream_t stream);
+size_t lamp_onehot_front_bwd_partials_bytes(int32_t B, int32_t T, int32_t n_vocab, int32_t d_model);
+int lamp_onehot_front_bwd(const int64_t* src_seq, int32_t B, int32_t T, const lamp_onehot_frontend* fe, int32_t d_model,
+                          float dropout_p, uint32_t seed, const float* dP, float* dz, float* partials, size_t partials_bytes,
+                          lamp_stream_t stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline) ------ */
 enum lamp_kernel_class {
     LAMP_K_EMBED = 0, LAMP_K_GEMM = 1, LAMP_K_ATTN = 2, LAMP_K_LAYERNORM = 3, LAMP_K_DIAG = 4,

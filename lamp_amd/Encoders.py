@@ -7,7 +7,8 @@ PyTorch on the device.  MLPEncoder (:16-27) and RNNEncoder (:112-137) are the re
 constructs and reference checkpoints load; they run wherever their tensors live.  Per-sample input graphs (``adj``,
 :81-85) only shape the encoder's attention maps -- its attention OUTPUT is dead compute -- and are served as a generic
 uint8 mask on the module-by-module route when maps are requested (logits identical either way).  The genomics
-one-hot/conv branch stays outside the scope (it raises at construction).
+one-hot branch (onehot=True, :46-51,68-73: conv1 -> ReLU(dropout) -> max-pool -> conv2 -> ReLU + positions) runs on
+csrc/conv.hip; it serves the reference's 9-symbol DNA vocabulary with position rows and no enc_transform.
 """
 import torch
 import torch.nn as nn
@@ -23,7 +24,14 @@ class GraphEncoder(nn.Module):
                  no_enc_pos_embedding=False):
         super().__init__()
         if onehot:
-            raise NotImplementedError('the one-hot / Conv1d genomics encoder is outside the label-graph hot path')
+            if n_src_vocab != ONEHOT_VOCAB:
+                # conv1 has 9 input channels: the reference fails at its first forward for any other vocabulary
+                raise NotImplementedError('the one-hot encoder takes the %d-symbol DNA vocabulary, not %d'
+                                          % (ONEHOT_VOCAB, n_src_vocab))
+            if no_enc_pos_embedding:
+                raise NotImplementedError('onehot without position embedding is an AttributeError in the reference')
+            if enc_transform != '':
+                raise NotImplementedError('onehot with enc_transform=%r is not served' % (enc_transform,))
         if enc_transform not in ('', 'sum', 'mean', 'flatten', 'max'):
             raise NotImplementedError('enc_transform=%r' % (enc_transform,))
         self.n_max_seq = n_max_seq
@@ -31,7 +39,15 @@ class GraphEncoder(nn.Module):
         self.onehot = onehot
         self.enc_transform = enc_transform
         self.dropout = nn.Dropout(dropout)
-        self.src_word_emb = nn.Embedding(n_src_vocab, d_word_vec, padding_idx=Constants.PAD)
+        if onehot:
+            # lamp/Encoders.py:46-51: a frozen-by-convention identity table over the bases, then the two convolutions
+            self.src_word_emb = nn.Embedding(n_src_vocab, n_src_vocab, padding_idx=Constants.PAD)
+            self.src_word_emb.weight.data.fill_(0)
+            self.src_word_emb.weight.data[1:, 1:] = torch.eye(n_src_vocab - 1)
+            self.conv1 = nn.Conv1d(ONEHOT_VOCAB, d_model, 16, stride=1, padding=8)
+            self.conv2 = nn.Conv1d(d_model, d_model, 16, stride=1, padding=8)
+        else:
+            self.src_word_emb = nn.Embedding(n_src_vocab, d_word_vec, padding_idx=Constants.PAD)
         if no_enc_pos_embedding is False:
             n_position = n_max_seq + 1
             self.position_enc = nn.Embedding(n_position, d_word_vec, padding_idx=Constants.PAD)
@@ -41,7 +57,12 @@ class GraphEncoder(nn.Module):
 
     def forward(self, src_seq, adj, src_pos, return_attns=False):
         pos_table = self.position_enc.weight if hasattr(self, 'position_enc') else None
-        if self.training:
+        if self.onehot:
+            if adj:
+                raise NotImplementedError('per-sample input graphs (adj) are not served with the one-hot encoder')
+            x = onehot_input(self, src_seq, src_pos)
+            src_seq = src_seq[:, :x.size(1)].contiguous()   # lamp/Encoders.py:73
+        elif self.training:
             # module-by-module training (graph encoder + enc_transform feeding another decoder): the embedding records
             # autograd here, the layers below dispatch to lamp_amd/training.py by themselves
             from . import training
@@ -69,6 +90,24 @@ class GraphEncoder(nn.Module):
         del keep
         x = pool_encoder_output(x, src_seq, self.enc_transform)
         return (x, attns) if return_attns else (x, None)
+
+
+ONEHOT_VOCAB = 9   # PAD, UNK, BOS, EOS and five bases
+
+
+def onehot_input(enc, src_seq, src_pos):
+    """lamp/Encoders.py:68-72: the one-hot encoder's input rows [B, T // 2, d] (module-by-module route)."""
+    N.require_device(src_seq)
+    seq, pos = src_seq.long().contiguous(), src_pos.long().contiguous()
+    if enc.training:
+        from . import training
+        return training.onehot_train(enc, seq, pos, training._Seeds())
+    with torch.no_grad():
+        t1 = N.onehot_tap_table(enc.src_word_emb.weight, enc.conv1.weight)
+        w2 = N.f32c(enc.conv2.weight)
+        fe = N.onehot_frontend(t1, N.f32c(enc.conv1.bias), w2, N.f32c(enc.conv2.bias))
+        return N.onehot_encoder_input(seq, pos, fe, N.conv_pack(w2), N.f32c(enc.conv2.bias), N.f32c(enc.position_enc.weight),
+                                      enc.d_model)
 
 
 def pool_encoder_output(enc_output, src_seq, enc_transform):

@@ -91,10 +91,12 @@ class LAMP(nn.Module):
         self._param_list = None
 
     def get_trainable_parameters(self):
-        """Everything but the frozen sinusoid table (reference: lamp/Models.py:97-107)."""
+        """Everything but the frozen sinusoid table, and the one-hot encoder's identity table (reference: lamp/Models.py:97-107)."""
         frozen = set()
         if hasattr(self.encoder, 'position_enc'):
             frozen |= {id(p) for p in self.encoder.position_enc.parameters()}
+        if self.onehot:
+            frozen |= {id(p) for p in self.encoder.src_word_emb.parameters()}
         return (p for p in self.parameters() if id(p) not in frozen)
 
     # ------------------------------------------------------------------ native model descriptor
@@ -162,6 +164,10 @@ class LAMP(nn.Module):
         return (enc.src_word_emb.weight, enc.position_enc.weight if hasattr(enc, 'position_enc') else None,
                 ff.w_1.weight, ff.w_1.bias)
 
+    def _onehot_weights(self):
+        enc = self.encoder
+        return (enc.src_word_emb.weight, enc.conv1.weight, enc.conv1.bias, enc.conv2.weight, enc.conv2.bias)
+
     def _chain_weights(self):
         out = []
         for l in self.decoder.layer_stack:
@@ -185,7 +191,8 @@ class LAMP(nn.Module):
         bits = self.decoder.label_mask_bits
         hoist = self.cache_layer0_query and not replica   # the hoisted projection needs a one-off stream sync
         packs = self.use_chain_packs and not replica      # weights-only repacks: same one-off cost, same staleness rule
-        fold = self.fold_embedding and not replica and len(self.encoder.layer_stack) > 0   # weights-only tables, likewise
+        onehot = bool(getattr(self.encoder, 'onehot', False))
+        fold = self.fold_embedding and not replica and len(self.encoder.layer_stack) > 0 and not onehot   # weights-only tables, likewise
         sparse = bool(self.use_sparse_label_attention and self.use_mask_bits and self.decoder.label_rows_sparse)
         key = tuple(p.data_ptr() for p in params) + (N.ptr(mask), N.ptr(bits), N.ptr(tiles), self.use_label_tiles,
                                                       hoist, self.use_mask_bits, packs, fold, sparse)
@@ -196,6 +203,8 @@ class LAMP(nn.Module):
             key += tuple(w._version for w in self._chain_weights())
         if fold:
             key += tuple(w._version for w in self._fold_weights() if w is not None)
+        if onehot:   # the tap table and W2's repack are weights-only: rebuilt per weight version
+            key += tuple((w.data_ptr(), w._version) for w in self._onehot_weights())
         cache = None if replica else self._native_cache
         if cache is not None and cache[0] == key:
             return cache[1]
@@ -263,7 +272,18 @@ class LAMP(nn.Module):
             m.enc0_emb_w1, m.enc0_pos_w1 = e1.data_ptr(), N.ptr(p1)
             fold_keep = (e1, p1)
             torch.cuda.current_stream().synchronize()
-        built = (m, enc_arr, dec_arr, q0, pack_arr, pack_keep, fold_keep)
+        onehot_keep = None
+        if onehot:
+            # lamp_onehot_frontend: conv1 as a gather from t1 = E . W1 (a pure repack for the reference's identity E), W2 repacked
+            # [co][t][ci] for the implicit-GEMM conv2; built once per weight version like the tables above
+            e_w, w1, b1, w2, b2 = (w.detach() for w in self._onehot_weights())
+            t1 = N.onehot_tap_table(e_w, w1)
+            w2c, b1c, b2c = N.f32c(w2), N.f32c(b1), N.f32c(b2)
+            w2p = N.conv_pack(w2c)
+            fe = N.onehot_frontend(t1, b1c, w2c, b2c, w2p)
+            onehot_keep = (fe, t1, w2c, b1c, b2c, w2p)
+            torch.cuda.current_stream().synchronize()
+        built = (m, enc_arr, dec_arr, q0, pack_arr, pack_keep, fold_keep, onehot_keep)
         if not replica:
             self._native_cache = (key, built)
         return built
@@ -305,6 +325,8 @@ class LAMP(nn.Module):
         return seq_logit.reshape(-1, seq_logit.size(-1)), enc_output, None
 
     def forward(self, src, adj, tgt_seq, binary_tgt, return_attns=False, int_preds=False):
+        if self.onehot and adj:
+            raise NotImplementedError('per-sample input graphs (adj) are not served with the one-hot encoder')
         if not self._fused:
             return self._forward_composite(src, adj, tgt_seq, return_attns, int_preds)
         if adj and return_attns and not int_preds and not self.training:
@@ -327,7 +349,12 @@ class LAMP(nn.Module):
         pos = src_pos.long().contiguous()
         B, T = seq.shape
         L, d = self.n_labels, self.d_model
-        model, enc_arr, dec_arr = self._native_model()[:3]
+        built = self._native_model()
+        model, enc_arr, dec_arr = built[:3]
+        fe = built[7][0] if self.onehot else None
+        T_in = T
+        if fe is not None:
+            T = T_in // 2   # lamp/Encoders.py:69-73: the encoder sees T / 2 rows
         Ne, Nd = model.n_layers_enc, model.n_layers_dec
 
         logits = torch.empty((B, L), dtype=torch.float32, device=dev)
@@ -356,15 +383,26 @@ class LAMP(nn.Module):
             aux = N.Aux(a0, a1, a2, None, 0, 0)
 
         lib = N.lib()
-        per_sample = lib.lamp_forward_workspace_bytes(C.byref(model), 1, T, int(want_attn))
-        fixed = 2 * per_sample - lib.lamp_forward_workspace_bytes(C.byref(model), 2, T, int(want_attn))
+        if fe is not None:
+            def ws_bytes(mb):
+                return lib.lamp_onehot_forward_workspace_bytes(C.byref(model), C.byref(fe), mb, T_in, int(want_attn))
+        else:
+            def ws_bytes(mb):
+                return lib.lamp_forward_workspace_bytes(C.byref(model), mb, T, int(want_attn))
+        per_sample = ws_bytes(1)
+        fixed = 2 * per_sample - ws_bytes(2)
         # enough for the whole batch in one pass unless that exceeds the cap (then it micro-batches)
         whole = fixed + (per_sample - fixed) * B + 4096
         budget = max(per_sample + 4096, min(whole, self.workspace_limit_bytes))
         ws = N.workspace(budget, dev)
-        N.check(lib.lamp_forward(C.byref(model), seq.data_ptr(), pos.data_ptr(), B, T, logits.data_ptr(),
-                                 enc_output.data_ptr(), C.byref(aux) if aux is not None else None,
-                                 ws.data_ptr(), ws.numel(), N.stream()), 'lamp_forward')
+        if fe is not None:
+            N.check(lib.lamp_onehot_forward(C.byref(model), C.byref(fe), seq.data_ptr(), pos.data_ptr(), B, T_in,
+                                            logits.data_ptr(), enc_output.data_ptr(), C.byref(aux) if aux is not None else None,
+                                            ws.data_ptr(), ws.numel(), N.stream()), 'lamp_onehot_forward')
+        else:
+            N.check(lib.lamp_forward(C.byref(model), seq.data_ptr(), pos.data_ptr(), B, T, logits.data_ptr(),
+                                     enc_output.data_ptr(), C.byref(aux) if aux is not None else None,
+                                     ws.data_ptr(), ws.numel(), N.stream()), 'lamp_forward')
         del keep
         if int_preds:
             return logits, enc_output, ipreds

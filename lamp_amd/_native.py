@@ -102,6 +102,11 @@ class Aux(C.Structure):
                 ('n_int_preds', C.c_int32), ('reserved', C.c_int32)]
 
 
+class OnehotFrontend(C.Structure):  # include/lamp_hip.h: lamp_onehot_frontend
+    _fields_ = [('t1', _vp), ('conv1_b', _vp), ('conv2_w', _vp), ('conv2_b', _vp), ('conv2_pack', _vp),
+                ('n_vocab', C.c_int32), ('taps', C.c_int32)]
+
+
 # name -> (restype, argtypes); every function include/lamp_hip.h declares
 _i32, _i64, _sz, _f = C.c_int32, C.c_int64, C.c_size_t, C.c_float
 PROTOTYPES = {
@@ -150,6 +155,17 @@ PROTOTYPES = {
     'lamp_sigmoid_bce_fwd': (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     'lamp_forward_workspace_bytes': (_sz, [C.POINTER(Model), _i32, _i32, _i32]),
     'lamp_forward': (C.c_int, [C.POINTER(Model), _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(Aux), _vp, _sz, _vp]),
+    'lamp_onehot_forward_workspace_bytes': (_sz, [C.POINTER(Model), C.POINTER(OnehotFrontend), _i32, _i32, _i32]),
+    'lamp_onehot_forward': (C.c_int, [C.POINTER(Model), C.POINTER(OnehotFrontend), _vp, _vp, _i32, _i32, _vp, _vp,
+                                      C.POINTER(Aux), _vp, _sz, _vp]),
+    'lamp_conv_pack': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'lamp_onehot_front_fwd': (C.c_int, [_vp, _i32, _i32, C.POINTER(OnehotFrontend), _i32, _f, C.c_uint32, _vp, _vp]),
+    'lamp_conv_window_fwd': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp,
+                                       _vp]),
+    'lamp_conv_relu_bwd_pad': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    'lamp_onehot_front_bwd_partials_bytes': (_sz, [_i32, _i32, _i32, _i32]),
+    'lamp_onehot_front_bwd': (C.c_int, [_vp, _i32, _i32, C.POINTER(OnehotFrontend), _i32, _f, C.c_uint32, _vp, _vp, _vp,
+                                        _sz, _vp]),
     'lamp_prof_enable': (C.c_int, [_i32]),
     'lamp_prof_reset': (C.c_int, []),
     'lamp_prof_read': (C.c_int, [_i32, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -882,3 +898,79 @@ def prof_read():
         check(lib().lamp_prof_read(cls, C.byref(n), C.byref(ms), C.byref(fl), C.byref(by)), 'lamp_prof_read')
         out[name] = dict(launches=n.value, ms=ms.value, flops=fl.value, bytes=by.value)
     return out
+
+
+# ---------------------------------------------------------------- one-hot genomics encoder (csrc/conv.hip)
+ONEHOT_TAPS = 16
+
+
+def onehot_tap_table(emb_w, conv1_w):
+    """t1[v, t, :] = sum_ci E[v, ci] conv1_w[:, ci, t]: conv1 over a one-hot input is a gather from this weights-only table
+    (with the reference's identity E a pure repack of conv1_w, no rounding).  Differentiable; E's PAD row is held constant,
+    as nn.Embedding(padding_idx=PAD) gives it no gradient."""
+    e = torch.cat([emb_w[:1].detach(), emb_w[1:]], 0)
+    return torch.einsum('vi,cit->vtc', e, conv1_w).contiguous()
+
+
+def conv_pack(w, flip=False):
+    """Conv1d weight [c_out, c_in, taps] -> [c_out, taps, c_in] (flip: [c_in, taps, c_out], taps reversed)."""
+    require_device(w)
+    wc = f32c(w.detach())
+    co, ci, taps = wc.shape
+    out = torch.empty((ci, taps, co) if flip else (co, taps, ci), dtype=torch.float32, device=wc.device)
+    check(lib().lamp_conv_pack(ptr(wc), co, ci, taps, int(bool(flip)), ptr(out), stream()), 'lamp_conv_pack')
+    return out
+
+
+def onehot_frontend(t1, conv1_b, conv2_w, conv2_b, conv2_pack=None):
+    return OnehotFrontend(ptr(t1), ptr(conv1_b), ptr(conv2_w), ptr(conv2_b), ptr(conv2_pack), t1.size(0), ONEHOT_TAPS)
+
+
+def onehot_front_fwd(src_seq, fe, d_model, p=0.0, seed=0):
+    """The zero-padded channel-last conv2 input [B * (T2 + 16) + 16, d] (include/lamp_hip.h: lamp_onehot_front_fwd)."""
+    B, T = src_seq.shape
+    T2 = T // 2
+    xpad = torch.empty((B * (T2 + 16) + 16, d_model), dtype=torch.float32, device=src_seq.device)
+    check(lib().lamp_onehot_front_fwd(ptr(src_seq), B, T, C.byref(fe), d_model, float(p), int(seed) & 0xffffffff,
+                                      ptr(xpad), stream()), 'lamp_onehot_front_fwd')
+    return xpad
+
+
+def conv_window(xpad, B, rows_out, rows_in, w_pack, bias=None, relu=False, pos_table=None, src_pos=None, relu_out=False):
+    """lamp_conv_window_fwd: [B * rows_out, c_out] (and the pre-position activations when relu_out)."""
+    c_out, taps, c_in = w_pack.shape
+    out = torch.empty((B * rows_out, c_out), dtype=torch.float32, device=xpad.device)
+    ro = torch.empty_like(out) if relu_out else None
+    check(lib().lamp_conv_window_fwd(ptr(xpad), B, rows_out, rows_in, c_in, ptr(w_pack), c_out, ptr(bias), int(bool(relu)),
+                                     ptr(pos_table), pos_table.size(0) if pos_table is not None else 0, ptr(src_pos),
+                                     src_pos.size(1) if src_pos is not None else 0, ptr(out), ptr(ro), stream()),
+          'lamp_conv_window_fwd')
+    return (out, ro) if relu_out else out
+
+
+def conv_relu_bwd_pad(dy, relu_out, B, rows):
+    d = dy.size(-1)
+    dz = torch.empty((B * (rows + 16) + 16, d), dtype=torch.float32, device=dy.device)
+    check(lib().lamp_conv_relu_bwd_pad(ptr(dy), ptr(relu_out), B, rows, d, ptr(dz), stream()), 'lamp_conv_relu_bwd_pad')
+    return dz
+
+
+def onehot_front_bwd(src_seq, fe, d_model, dP, p=0.0, seed=0):
+    """(dz [B, T, d] = gradient of y1, d t1 [n_vocab, 16, d]) from dP [B, T2, d]."""
+    B, T = src_seq.shape
+    dz = torch.empty((B, T, d_model), dtype=torch.float32, device=dP.device)
+    nbytes = lib().lamp_onehot_front_bwd_partials_bytes(B, T, fe.n_vocab, d_model)
+    part = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dP.device)
+    check(lib().lamp_onehot_front_bwd(ptr(src_seq), B, T, C.byref(fe), d_model, float(p), int(seed) & 0xffffffff, ptr(dP),
+                                      ptr(dz), ptr(part), nbytes, stream()), 'lamp_onehot_front_bwd')
+    dt1 = colsum(part.view(-1, fe.n_vocab * ONEHOT_TAPS * d_model)).view(fe.n_vocab, ONEHOT_TAPS, d_model)
+    return dz, dt1
+
+
+def onehot_encoder_input(src_seq, src_pos, fe, w2_pack, conv2_b, pos_table, d_model):
+    """Eval: the encoder's input rows [B, T2, d] (front end + conv2 with its epilogue)."""
+    B, T = src_seq.shape
+    T2 = T // 2
+    xpad = onehot_front_fwd(src_seq, fe, d_model)
+    out = conv_window(xpad, B, T2, T2 + 16, w2_pack, conv2_b, True, pos_table, src_pos)
+    return out.view(B, T2, d_model)

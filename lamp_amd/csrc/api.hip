@@ -892,9 +892,15 @@ size_t lamp_forward_workspace_bytes(const lamp_model* m, int32_t micro_batch, in
 // encoder.  Samples are independent and no kernel variant depends on the batch size, so a sample's results are
 // bit-identical for every micro-batch split.
 constexpr int MAX_AHEAD_LAYERS = 16;
+static inline size_t onehot_rows(int T_in) { return size_t(T_in / 2 + 16); }   // padded conv2 input rows per sample
+// `fe` (lamp_onehot_forward): the one-hot genomics front end replaces the embedding gather; the encoder then sees T / 2 rows
+// of each sample (T_in tokens, row stride T_in in src_seq / src_pos) in the padded layout.
 static int forward_range(const lamp_model* m, const FwdPlan& pl, const int64_t* src_seq, const int64_t* src_pos,
-                         int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux,
-                         void* workspace, size_t workspace_bytes, hipStream_t s, bool kv_ahead) {
+                         int32_t B, int32_t T_in, float* logits, float* enc_output, const lamp_aux* aux,
+                         void* workspace, size_t workspace_bytes, hipStream_t s, bool kv_ahead,
+                         const lamp_onehot_frontend* fe = nullptr, const float* w2_pack = nullptr) {
+    const int T = fe ? T_in / 2 : T_in;   // encoder rows per sample
+    const int64_t ld_seq = T_in;
     const bool want_enc_attn = aux && aux->enc_self_attn;
     const int d = m->d_model, dff = m->d_inner, dk = m->d_k, dv = m->d_v, L = m->n_labels;
     const int n_ahead = kv_ahead ? m->n_layers_dec : 0;
@@ -910,7 +916,7 @@ static int forward_range(const lamp_model* m, const FwdPlan& pl, const int64_t* 
     // packed rows only.  Row-wise kernels and an M-independent k-order make this bit-identical to computing every
     // padded position.  Not packed (the dead encoder self-attention's maps are wanted, or wide heads): padded layout as
     // before; the enc-dec attention still stops at each sample's last real key either way.
-    const bool packed = !want_enc_attn && !wide_heads(dk, dv) && m->n_layers_enc > 0;
+    const bool packed = !want_enc_attn && !wide_heads(dk, dv) && m->n_layers_enc > 0 && !fe;
     const int Rq = want_enc_attn ? pl.R : L;
     float *H = nullptr, *Y = nullptr, *Xp = nullptr;
     int* plan_ints = nullptr;
@@ -919,6 +925,7 @@ static int forward_range(const lamp_model* m, const FwdPlan& pl, const int64_t* 
     float* Kahead[MAX_AHEAD_LAYERS] = {};
     float* Vahead[MAX_AHEAD_LAYERS] = {};
     MhaScratch sc{};
+    float* fe_x = nullptr;   // the front end's zero-padded channel-last conv2 input
     for (int attempt = 0; attempt < 2; ++attempt) {
         Carver c(workspace, workspace_bytes);
         H = c.take(size_t(mb) * pl.R * dff + dff);
@@ -937,6 +944,7 @@ static int forward_range(const lamp_model* m, const FwdPlan& pl, const int64_t* 
             Kahead[i] = c.take(size_t(mb) * T * pl.hdk);
             Vahead[i] = c.take(size_t(mb) * T * pl.hdv);
         }
+        if (fe) fe_x = c.take(size_t(mb) * onehot_rows(T_in) * d + size_t(16) * d);
         if (c.ok) break;
         if (attempt == 1 || mb <= 1) return LAMP_E_WORKSPACE;
         --mb;  // rounding slack exhausted: one sample fewer
@@ -944,8 +952,8 @@ static int forward_range(const lamp_model* m, const FwdPlan& pl, const int64_t* 
 
     for (int64_t b0 = 0; b0 < B; b0 += mb) {
         const int nb = int(B - b0 < mb ? B - b0 : mb);
-        const int64_t* seq = src_seq + b0 * T;
-        const int64_t* pos = src_pos ? src_pos + b0 * T : nullptr;
+        const int64_t* seq = src_seq + b0 * ld_seq;
+        const int64_t* pos = src_pos ? src_pos + b0 * ld_seq : nullptr;
         float* x = enc_output + b0 * int64_t(T) * d;  // the padded encoder output of this micro-batch
         const int64_t Me = int64_t(nb) * T;
         SeqPlan sp = plan_from(plan_ints, nb, T);
@@ -954,10 +962,10 @@ static int forward_range(const lamp_model* m, const FwdPlan& pl, const int64_t* 
         // gather through 8-byte granules (pointwise.hip: embed_plan_kernel; round 3 had it as a launch of its own -- a
         // dependent launch costs 5-8 us on this chain however little it does -- after folding it into EVERY workgroup of
         // the gather had measured slower, 21.9 us against 6.6 + 10.5).  Padded layout: the plan kernel on its own.
-        if (!packed) LAMP_CK(launch_seq_plan(seq, m->position_enc ? pos : nullptr, nb, T, T, packed, sp, s));
+        if (!packed) LAMP_CK(launch_seq_plan(seq, m->position_enc ? pos : nullptr, nb, T, ld_seq, packed, sp, s));
 
         // ---- GraphEncoder.forward (lamp/Encoders.py:64-110) ----
-        lamp_mask pad_mask{LAMP_MASK_KEY_TOKENS_I64, 0, seq, T, 0, nullptr, 0};
+        lamp_mask pad_mask{LAMP_MASK_KEY_TOKENS_I64, 0, seq, ld_seq, 0, nullptr, 0};
         const float* xk = x;  // what the decoder's K / V projections read
         // Encoder layer 0's W1 folded into the embedding tables (lamp_model::enc0_emb_w1): the gather writes that layer's
         // hidden rows into H beside the embedded rows, and its first GEMM is not launched.
@@ -981,7 +989,16 @@ static int forward_range(const lamp_model* m, const FwdPlan& pl, const int64_t* 
             }
             xk = Xp;
         } else {
-            LAMP_CK(launch_embed(seq, pos, Me, m->src_word_emb, m->n_src_vocab, m->position_enc, m->n_position, d, x, s, &fold));
+            if (fe) {
+                // lamp/Encoders.py:68-73: tap gather + ReLU + pair max, then conv2 as an implicit GEMM whose epilogue adds b2,
+                // applies the ReLU and adds the position row, straight into this micro-batch's encoder rows
+                LAMP_CK(launch_front_fwd(seq, nb, T_in, fe->t1, fe->n_vocab, fe->conv1_b, d, 0.f, 0u, 0, fe_x, s));
+                ConvWindowParams cp{fe_x, w2_pack, fe->conv2_b, x, nullptr, m->position_enc, pos, Me, d, ld_seq,
+                                    d, 16 * d, d, T, T + 16, 1, m->n_position};
+                LAMP_CK(launch_conv_window(cp, s));
+            } else {
+                LAMP_CK(launch_embed(seq, pos, Me, m->src_word_emb, m->n_src_vocab, m->position_enc, m->n_position, d, x, s, &fold));
+            }
             for (int i = 0; i < m->n_layers_enc; ++i) {
                 const lamp_enc_layer& l = m->enc_layers[i];
                 if (want_enc_attn && aux->enc_self_attn[i]) {
@@ -1079,6 +1096,102 @@ int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src
                           workspace_bytes >= (pl.fixed_floats + (pl.per_sample_floats + pl.side_kv_floats) * size_t(B) +
                                               size_t(64) * (8 + 2 * m->n_layers_dec)) * sizeof(float);
     return forward_range(m, pl, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, s, kv_ahead);
+}
+
+// ------------------------------------------------------------------ one-hot genomics encoder (conv.hip)
+static int onehot_check(const lamp_model* m, const lamp_onehot_frontend* fe, int32_t T) {
+    if (!m || !fe) return LAMP_E_NULL;
+    if (!fe->t1 || !fe->conv1_b || !fe->conv2_b || (!fe->conv2_w && !fe->conv2_pack)) return LAMP_E_NULL;
+    if (fe->n_vocab <= 0 || fe->n_vocab > 16 || fe->taps != 16 || T < 2 || m->d_model <= 0) return LAMP_E_DIMS;
+    if (!m->position_enc) return LAMP_E_NULL;   // lamp/Encoders.py:72 adds the position rows unconditionally
+    if (m->enc0_emb_w1 || (m->d_model & 3)) return LAMP_E_UNSUPPORTED;
+    return 0;
+}
+
+static size_t onehot_pack_floats(const lamp_model* m, const lamp_onehot_frontend* fe) {
+    return fe->conv2_pack ? 0 : size_t(16) * m->d_model * m->d_model + 64;
+}
+
+size_t lamp_onehot_forward_workspace_bytes(const lamp_model* m, const lamp_onehot_frontend* fe, int32_t micro_batch, int32_t T,
+                                           int32_t want_attn) {
+    FwdPlan pl;
+    if (micro_batch <= 0 || onehot_check(m, fe, T) != 0 || make_plan(m, T / 2, want_attn, &pl) != 0) return 0;
+    const size_t fixed = pl.fixed_floats + size_t(16) * m->d_model + 64 + onehot_pack_floats(m, fe);
+    const size_t per = pl.per_sample_floats + onehot_rows(T) * m->d_model;
+    return (fixed + per * size_t(micro_batch)) * sizeof(float);
+}
+
+int lamp_onehot_forward(const lamp_model* m, const lamp_onehot_frontend* fe, const int64_t* src_seq, const int64_t* src_pos,
+                        int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
+                        size_t workspace_bytes, lamp_stream_t stream) {
+    hipStream_t s = hipStream_t(stream);
+    LAMP_CK(onehot_check(m, fe, T));
+    if (!src_seq || !src_pos || !logits || !enc_output || !workspace) return LAMP_E_NULL;
+    if (B <= 0) return LAMP_E_DIMS;
+    if (!m->tgt_word_emb || !m->w_out) return LAMP_E_NULL;
+    if (m->n_layers_dec <= 0) return LAMP_E_DIMS;
+    FwdPlan pl;
+    LAMP_CK(make_plan(m, T / 2, aux && aux->enc_self_attn, &pl));
+    if ((m->d_inner & 3) || (m->d_k & 3) || (m->d_v & 3)) return LAMP_E_UNSUPPORTED;
+    const int d = m->d_model;
+    // the front end's rows ride as per-sample floats of the plan; W2's repack (when the caller keeps none) comes first
+    pl.per_sample_floats += onehot_rows(T) * d;
+    pl.fixed_floats += size_t(16) * d + 64;
+    const size_t pack_floats = onehot_pack_floats(m, fe);
+    if (workspace_bytes < pack_floats * sizeof(float)) return LAMP_E_WORKSPACE;
+    if ((fe->conv2_pack && !aligned16(fe->conv2_pack)) || (!fe->conv2_pack && !aligned16(fe->conv2_w)) || !aligned16(fe->t1) ||
+        !aligned16(fe->conv1_b) || !aligned16(workspace))
+        return LAMP_E_ALIGN;   // before the repack below: argument errors never follow a launch
+    const float* pack = fe->conv2_pack;
+    char* ws = static_cast<char*>(workspace);
+    if (!pack) {
+        float* p = reinterpret_cast<float*>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
+        LAMP_CK(launch_conv_pack(fe->conv2_w, d, d, 16, 0, p, s));
+        pack = p;
+        ws += pack_floats * sizeof(float);
+        workspace_bytes -= pack_floats * sizeof(float);
+    }
+    return forward_range(m, pl, src_seq, src_pos, B, T, logits, enc_output, aux, ws, workspace_bytes, s, false, fe, pack);
+}
+
+int lamp_conv_pack(const float* w, int32_t c_out, int32_t c_in, int32_t taps, int32_t flip, float* packed,
+                   lamp_stream_t stream) {
+    return launch_conv_pack(w, c_out, c_in, taps, flip, packed, hipStream_t(stream));
+}
+
+int lamp_onehot_front_fwd(const int64_t* src_seq, int32_t B, int32_t T, const lamp_onehot_frontend* fe, int32_t d_model,
+                          float dropout_p, uint32_t seed, float* xpad, lamp_stream_t stream) {
+    if (!fe) return LAMP_E_NULL;
+    return launch_front_fwd(src_seq, B, T, fe->t1, fe->n_vocab, fe->conv1_b, d_model, dropout_p, seed, 0, xpad,
+                            hipStream_t(stream));
+}
+
+int lamp_conv_window_fwd(const float* xpad, int32_t B, int32_t rows_out, int32_t rows_in, int32_t c_in, const float* w_pack,
+                         int32_t c_out, const float* bias, int32_t relu, const float* pos_table, int32_t n_position,
+                         const int64_t* src_pos, int64_t pos_ld, float* out, float* relu_out, lamp_stream_t stream) {
+    if (B <= 0) return LAMP_E_DIMS;
+    ConvWindowParams p{xpad, w_pack, bias, out, relu_out, pos_table, src_pos, int64_t(B) * rows_out, c_out, pos_ld,
+                       c_out, 16 * c_in, c_in, rows_out, rows_in, relu != 0, n_position};
+    return launch_conv_window(p, hipStream_t(stream));
+}
+
+int lamp_conv_relu_bwd_pad(const float* dy, const float* relu_out, int32_t B, int32_t rows, int32_t d, float* dz,
+                           lamp_stream_t stream) {
+    return launch_relu_bwd_pad(dy, relu_out, B, rows, d, dz, hipStream_t(stream));
+}
+
+size_t lamp_onehot_front_bwd_partials_bytes(int32_t B, int32_t T, int32_t n_vocab, int32_t d_model) {
+    if (B <= 0 || T <= 0 || n_vocab <= 0 || d_model <= 0) return 0;
+    return size_t(front_dt1_chunks(B, T)) * n_vocab * 16 * d_model * sizeof(float);
+}
+
+int lamp_onehot_front_bwd(const int64_t* src_seq, int32_t B, int32_t T, const lamp_onehot_frontend* fe, int32_t d_model,
+                          float dropout_p, uint32_t seed, const float* dP, float* dz, float* partials, size_t partials_bytes,
+                          lamp_stream_t stream) {
+    if (!fe) return LAMP_E_NULL;
+    if (partials_bytes < lamp_onehot_front_bwd_partials_bytes(B, T, fe->n_vocab, d_model)) return LAMP_E_WORKSPACE;
+    return launch_front_bwd(src_seq, B, T, fe->t1, fe->n_vocab, fe->conv1_b, d_model, dropout_p, seed, dP, dz, partials,
+                            hipStream_t(stream));
 }
 
 // ------------------------------------------------------------------ profiling ABI

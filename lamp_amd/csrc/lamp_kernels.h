@@ -205,6 +205,29 @@ int launch_prior_graph(const int64_t* ids, const int64_t* offsets, int64_t n_sam
 int launch_sigmoid_bce(const float* logits, const float* targets, int64_t n_rows, int L, float* probs,
                        float* row_loss, hipStream_t s);
 
+// ---- one-hot genomics front end (conv.hip) ----
+// out[m][n] = act(sum_k x[row(m) * c_in + k] * w[n][k] + bias[n]) (+ pos_table[src_pos[b * pos_ld + q]][n]), k < K,
+// m = b * rows_out + q, row(m) = b * rows_in + q: a Conv1d over a channel-last, zero-padded input as an implicit GEMM.
+struct ConvWindowParams {
+    const float* x;        // [.., c_in] rows; a sample's first row at b * rows_in
+    const float* w;        // [N, K] packed taps, K = taps * c_in contiguous
+    const float* bias;     // [N] or nullptr
+    float* out;            // [M, ldo]
+    float* relu_out;       // [M, N] act(...) before the position row, or nullptr
+    const float* pos_table;  // [n_position, N] or nullptr
+    const int64_t* src_pos;  // [nb, pos_ld]
+    int64_t M, ldo, pos_ld;
+    int N, K, c_in, rows_out, rows_in, relu, n_position;
+};
+int launch_conv_window(const ConvWindowParams& p, hipStream_t s);
+int launch_front_fwd(const int64_t* seq, int nb, int T, const float* t1, int n_vocab, const float* b1, int d, float p_drop,
+                     uint32_t seed, int64_t e_base, float* xpad, hipStream_t s);
+int launch_conv_pack(const float* w, int c_out, int c_in, int taps, int flip, float* packed, hipStream_t s);
+int launch_relu_bwd_pad(const float* dy, const float* relu_out, int nb, int T2, int d, float* dz, hipStream_t s);
+int64_t front_dt1_chunks(int nb, int T);
+int launch_front_bwd(const int64_t* seq, int nb, int T, const float* t1, int n_vocab, const float* b1, int d, float p_drop,
+                     uint32_t seed, const float* dP, float* dz, float* partial, hipStream_t s);
+
 // ---- profiling (lamp_prof_* in the ABI) ----
 struct ProfScope {
     int idx;

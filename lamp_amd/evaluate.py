@@ -174,7 +174,12 @@ def test_epoch(model, batches, n_labels, batch_size, device, pad_last_batch=True
     `merge_stage=True`: the `prefetch` batches of a stage go through the model as ONE forward, padded to the stage's longest
     batch (no all-PAD filler rows).  A sample's outputs do not depend on the batch it travels in nor on the padded length, bit
     for bit (DESIGN.md 3b), so predictions, targets and the per-batch mean losses are the ones of the batch-by-batch loop;
-    the issuing thread makes one call per stage instead of one per batch and the kernels see `prefetch` times the rows."""
+    the issuing thread makes one call per stage instead of one per batch and the kernels see `prefetch` times the rows.
+    One-hot genomics models (LAMP(onehot=True)) are the exception: their encoder length is half the padded
+    length, so their results depend on it by the reference's own definition.  Each of their batches is padded to its own
+    longest sequence, as the reference's DataLoader does, and merge_stage is refused for them."""
+    if merge_stage and getattr(model, 'onehot', False):
+        raise ValueError("merge_stage pads batches to the stage's longest one, which changes a one-hot model's results")
     import time
     t_start = time.perf_counter()
     hostcpu.fit_intra_op_threads(world_size)   # a 256-thread OpenMP pool under a 16-core cgroup quota stalls the whole process (hostcpu.py)

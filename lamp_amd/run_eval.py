@@ -33,10 +33,13 @@ from .evaluate import test_epoch
 from .Models import LAMP
 
 
+ONEHOT_DATASETS = ('deepsea', 'gm12878', 'gm12878_unique2', 'gm12878_unique', 'tcell')
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('-data', required=True, help='train_valid_test.pt in the reference format')
-    ap.add_argument('-dataset', default='', help='dataset name (only used for the no-position-embedding rule)')
+    ap.add_argument('-dataset', default='', help='dataset name (used for the no-position-embedding and one-hot rules)')
     ap.add_argument('-checkpoint', default=None, help="reference checkpoint: {'model': state_dict, ...}")
     ap.add_argument('-split', default='test', choices=['train', 'valid', 'test'])
     ap.add_argument('-batch_size', type=int, default=32)
@@ -67,6 +70,10 @@ def parse(argv=None):
         opt.n_head2 = opt.n_head
     if opt.dataset in ('bibtext', 'delicious', 'bookmarks', 'sider'):
         opt.no_enc_pos_embedding = True
+    # config_args.py:90-91: the genomics datasets read DNA through the one-hot / Conv1d encoder
+    opt.onehot = opt.dataset in ONEHOT_DATASETS
+    if opt.onehot and opt.merge_stages:
+        ap.error('-merge_stages changes the padded length, hence the results, of a one-hot model')
     if opt.d_model % opt.n_head:
         ap.error('d_model must be divisible by n_head')
     return opt
@@ -161,7 +168,7 @@ def main(argv=None):
                  n_layers_dec=opt.n_layers_dec, n_head=h, n_head2=opt.n_head2, d_word_vec=d, d_model=d,
                  d_inner_hid=opt.d_inner_hid, d_k=d // h, d_v=d // h, encoder='graph', decoder='graph',
                  no_enc_pos_embedding=opt.no_enc_pos_embedding, no_dec_self_att=opt.no_dec_self_att,
-                 label_adj_matrix=adj, label_mask=opt.label_mask, dec_dropout2=False)
+                 label_adj_matrix=adj, label_mask=opt.label_mask, dec_dropout2=False, onehot=opt.onehot)
     if opt.checkpoint:
         model.load_state_dict(load_checkpoint_state(opt.checkpoint))
     model = model.to(device).eval()
@@ -176,7 +183,7 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     out = {'split': opt.split, 'n_samples': batches.n_insts, 'n_labels': n_labels, 'n_batches': len(batches),
            'bce_total': bce_total, 'seconds': dt, 'samples_per_s': batches.n_insts / dt,
-           'checkpoint': opt.checkpoint, 'n_gpus': world, 'backend': plane.backend, 'backend_note': plane.note}
+           'checkpoint': opt.checkpoint, 'onehot': opt.onehot, 'n_gpus': world, 'backend': plane.backend, 'backend_note': plane.note}
     out.update(multilabel_metrics(preds, targets, opt.br_threshold))
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -60,6 +60,21 @@ def make_state_dict(n_src_vocab, n_labels, n_max_seq, d_model, d_inner, n_head, 
     return sd
 
 
+def make_onehot_state_dict(n_labels, n_max_seq, d_model, d_inner, n_head, n_layers_enc, n_layers_dec, seed=0):
+    """The one-hot genomics model (GraphEncoder(onehot=True), lamp/Encoders.py:46-51): make_state_dict's layers over the
+    9-symbol DNA vocabulary, the reference's identity embedding and Conv1d weights drawn like torch's default init."""
+    sd = make_state_dict(9, n_labels, n_max_seq, d_model, d_inner, n_head, n_layers_enc, n_layers_dec, True, seed)
+    g = torch.Generator().manual_seed(seed + 1000)
+    emb = torch.zeros(9, 9)
+    emb[1:, 1:] = torch.eye(8)
+    sd['encoder.src_word_emb.weight'] = emb
+    for name, c_in in (('conv1', 9), ('conv2', d_model)):
+        bound = 1.0 / math.sqrt(c_in * 16)
+        sd['encoder.%s.weight' % name] = (torch.rand((d_model, c_in, 16), generator=g) * 2 - 1) * bound
+        sd['encoder.%s.bias' % name] = (torch.rand((d_model,), generator=g) * 2 - 1) * bound
+    return sd
+
+
 def make_adjacency(n_labels, p, seed=0):
     """Symmetric Bernoulli(p) OR identity."""
     g = torch.Generator().manual_seed(seed)

@@ -236,6 +236,54 @@ class _EmbedFn(torch.autograd.Function):
         return None, None, d_emb, None  # the position table is frozen (lamp/Models.py:97-107)
 
 
+class _OnehotFn(torch.autograd.Function):
+    """lamp/Encoders.py:68-73, the one-hot genomics front end: conv1 as a gather from the tap table t1 (N.onehot_tap_table,
+    whose autograd carries the gradient on to conv1's weight and the embedding), ReLU(dropout), pair max, conv2 + ReLU + the
+    frozen position rows.  Backward: conv2's input gradient with the same window kernel on the flipped repack, its weight
+    gradient by lamp_gemm over the overlapping window view of the saved input, the front end's by one scatter in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, src_seq, src_pos, t1, b1, w2, b2, pos_w, p, seed):
+        B, T = src_seq.shape
+        T2, d = T // 2, w2.size(0)
+        t1, b1, b2 = t1.contiguous(), b1.contiguous(), b2.contiguous()
+        w2c = N.f32c(w2)
+        pack = N.conv_pack(w2c)
+        fe = N.onehot_frontend(t1, b1, w2c, b2, pack)
+        xpad = N.onehot_front_fwd(src_seq, fe, d, p, seed)
+        out, ro = N.conv_window(xpad, B, T2, T2 + 16, pack, b2, True, pos_w, src_pos, relu_out=True)
+        ctx.save_for_backward(src_seq, t1, b1, w2c, b2, xpad, ro)
+        ctx.p, ctx.seed = p, seed
+        return out.view(B, T2, d)
+
+    @staticmethod
+    def backward(ctx, dx):
+        src_seq, t1, b1, w2, b2, xpad, ro = ctx.saved_tensors
+        B, T = src_seq.shape
+        T2, d = T // 2, w2.size(0)
+        Tp = T2 + 16
+        dz2 = N.conv_relu_bwd_pad(dx.contiguous().view(B * T2, d), ro, B, T2)   # [B Tp + 16, d], ReLU-masked
+        R = B * Tp
+        db2 = N.colsum(dz2[:R])
+        # dW2[co, t, ci] = sum over outputs of dZ[b Tp + 8 + q, co] * xpad[b Tp + q + t, ci]: the window view reads 16 rows
+        # from every row, paired with dZ 8 rows further on (rows past a sample's outputs hold 0)
+        win = xpad.as_strided((16 * d, R - 8), (1, d))
+        dw2 = N.matmul_nt(dz2[8:R].t(), win).view(d, 16, d).permute(0, 2, 1).contiguous()
+        # the gradient of P: rows r + 1 .. r + 16 of the padded dZ against W2 flipped ([ci][15 - t][co])
+        dP = N.conv_window(dz2[1:], B, T2, Tp, N.conv_pack(w2, flip=True))
+        fe = N.onehot_frontend(t1, b1, w2, b2, None)
+        dz1, dt1 = N.onehot_front_bwd(src_seq, fe, d, dP, ctx.p, ctx.seed)
+        db1 = N.colsum(dz1.view(-1, d))
+        return None, None, dt1, db1, dw2, db2, None, None, None
+
+
+def onehot_train(enc, seq, pos, seeds):
+    """The one-hot encoder's input rows [B, T // 2, d] on the autograd graph."""
+    t1 = N.onehot_tap_table(enc.src_word_emb.weight, enc.conv1.weight)
+    return _OnehotFn.apply(seq, pos, t1, enc.conv1.bias, enc.conv2.weight, enc.conv2.bias, enc.position_enc.weight,
+                           float(enc.dropout.p), seeds.next())
+
+
 class _LabelRowsFn(torch.autograd.Function):
     """lamp/Decoders.py:132-134: every sample's decoder input is the whole label table."""
 
@@ -540,9 +588,14 @@ def forward_train(model, src_seq, src_pos, return_attns=False, int_preds=False):
     pos = src_pos.long().contiguous()
     seeds = _Seeds()
     B, T = seq.shape
+    if getattr(enc, 'onehot', False):
+        x = onehot_train(enc, seq, pos, seeds)   # lamp/Encoders.py:68-73; src_seq[:, :T2] from here on
+        T = x.size(1)
+        seq = seq[:, :T].contiguous()
     pad_mask, keep = N.key_token_mask(seq, T)
     pos_w = enc.position_enc.weight if hasattr(enc, 'position_enc') else None
-    x = _EmbedFn.apply(seq, pos, enc.src_word_emb.weight, pos_w)
+    if not getattr(enc, 'onehot', False):
+        x = _EmbedFn.apply(seq, pos, enc.src_word_emb.weight, pos_w)
     enc_attns = []
     for layer in enc.layer_stack:
         if return_attns:
