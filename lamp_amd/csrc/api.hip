@@ -2,6 +2,7 @@
 //
 // Host-side only: argument validation, workspace carving and the launch sequence.  No device
 // memory is allocated here, no pointer is retained, nothing synchronises (except lamp_prof_read).
+#include <algorithm>
 #include <mutex>
 #include <vector>
 
@@ -60,21 +61,23 @@ ProfScope::~ProfScope() {
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// A workspace is a list of regions of per_sample * mb + fixed floats, each rounded up to 256 bytes.  One layout function
+// per workspace declares its regions in order: run over a null base it only sizes them, over the caller's workspace it
+// carves them.  `bound` is affine in the micro-batch and never below what carving that many samples takes: its fixed part
+// holds one 256-byte alignment allowance per region.
 struct Carver {
-    char* base;
-    size_t off, cap;
-    bool ok;
-    Carver(void* p, size_t bytes) : base(static_cast<char*>(p)), off(0), cap(bytes), ok(true) {}
-    float* take(size_t n_floats) {
-        const size_t b = align_up(n_floats * sizeof(float), 256);
-        if (off + b > cap) {
-            ok = false;
-            return nullptr;
-        }
-        float* r = reinterpret_cast<float*>(base + off);
-        off += b;
-        return r;
+    char* base;                 // nullptr: sizing only
+    size_t mb;                  // samples the regions are carved for
+    size_t off = 0;             // bytes taken so far
+    size_t per = 0, fixed = 0;  // bytes per sample; fixed bytes
+    template <class P>
+    void take(P** p, size_t per_sample_floats, size_t fixed_floats = 0) {
+        if (p) *p = base ? reinterpret_cast<P*>(base + off) : nullptr;
+        off += align_up((per_sample_floats * mb + fixed_floats) * sizeof(float), 256);
+        per += per_sample_floats * sizeof(float);
+        fixed += fixed_floats * sizeof(float) + 256;
     }
+    size_t bound(size_t n) const { return per * n + fixed; }
 };
 
 // The residual of a GEMM as a gather from the embedding tables (GemmParams::rg_tok): the encoder's first layer, whose input rows
@@ -114,86 +117,152 @@ static int check_mask(const lamp_mask* m) {
     return 0;
 }
 
-// Scratch of one MultiHeadAttention call on B samples.
+// The mask fields of AttnParams from a lamp_mask (nullable); set a.P first: the tile list only serves calls without maps.
+static void attn_mask(AttnParams& a, const lamp_mask* mask) {
+    a.mask_kind = mask ? mask->kind : LAMP_MASK_NONE;
+    a.mask = mask ? mask->ptr : nullptr;
+    a.m_sb = mask ? mask->stride_b : 0;
+    a.m_sq = mask ? mask->stride_q : 0;
+    a.tiles = (mask && !a.P) ? mask->tile_list : nullptr;
+    a.tiles_stride = mask ? mask->tile_list_stride : 0;
+    a.sparse_rows = mask && (mask->flags & LAMP_MASK_SPARSE_ROWS) != 0;
+    a.allowed_pairs = mask ? mask->allowed_pairs : 0;
+}
+
+// The Q / K / V projections of one attention block; a null output is not projected.  Projections that share their input
+// go out as segments of ONE launch (same bits as one launch each): K with V when both read the same rows at the same
+// width, Q with both when it reads those rows too.  m_dev / A_dense (GemmParams): the key / value rows are packed.
+static int project_qkv(const lamp_mha_weights& w, int d, int dk, int dv, const float* xq, int64_t Mq, float* Q,
+                       const float* xk, const float* xv, int64_t Mk, float* K, float* V, hipStream_t s, const int* m_dev,
+                       const float* A_dense) {
+    const int hdk = w.n_head * dk, hdv = w.n_head * dv;
+    const bool one_kv = K && V && xk == xv && hdk == hdv;
+    const bool one_qkv = one_kv && Q && xq == xk && Mq == Mk && !m_dev;
+    const float* W[3] = {w.w_qs, w.w_ks, w.w_vs};
+    float* C[3] = {Q, K, V};
+    if (Q) LAMP_CK(linear(xq, Mq, d, d, W, one_qkv ? 3 : 1, hdk, d, nullptr, nullptr, 0, 0, C, hdk, s));
+    if (one_qkv) return 0;
+    if (one_kv) return linear(xk, Mk, d, d, W + 1, 2, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, s, m_dev, A_dense);
+    if (K) LAMP_CK(linear(xk, Mk, d, d, W + 1, 1, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, s, m_dev, A_dense));
+    if (V) LAMP_CK(linear(xv, Mk, d, d, W + 2, 1, hdv, d, nullptr, nullptr, 0, 0, C + 2, hdv, s, m_dev, A_dense));
+    return 0;
+}
+
+// PositionwiseFeedForward.forward (lamp/SubLayers.py:133-142).
+struct FfnParams {
+    const float* x;   // [M, d]; out may alias it
+    int64_t M;
+    int d, dff;
+    const lamp_ffn_weights* w;
+    float *out, *hidden;
+    const float* w_out = nullptr;   // fused read-out of the last decoder block: the final LayerNorm writes logits, not out
+    int n_labels = 0;
+    float* logits = nullptr;
+    // Packed encoder rows (ragged batches): the live row count in device memory (M is the upper bound the launches are sized
+    // for); with `scatter` this is the LAST encoder layer, whose LayerNorm also writes the padded [nb, T, d] encoder output
+    // `y_flat` (see layernorm_kernel<.., RG = 2>).
+    const int* rows_dev = nullptr;
+    const SeqPlan* scatter = nullptr;
+    int nb = 0, T = 0;
+    float* y_flat = nullptr;
+    // relu(x W1^T + b1) is already in `hidden` (the encoder's first layer with W1 folded into the embedding tables,
+    // pointwise.hip: gather_row): the first GEMM is not launched, and with `rg` the residual is gathered (x does not exist)
+    bool hidden_ready = false;
+    const ResGather* rg = nullptr;
+};
+
+static int ffn_core(const FfnParams& f, hipStream_t s) {
+    const lamp_ffn_weights& w = *f.w;
+    const int d = f.d, dff = f.dff;
+    if (!w.w1 || !w.b1 || !w.w2 || !w.b2 || !w.ln_g || !w.ln_b) return LAMP_E_NULL;
+    if (f.rg && !f.hidden_ready) return LAMP_E_UNSUPPORTED;
+    if (!f.hidden_ready) {
+        const float* W[1] = {w.w1};
+        const float* b[1] = {w.b1};
+        float* C[1] = {f.hidden};
+        LAMP_CK(linear(f.x, f.M, d, d, W, 1, dff, d, b, nullptr, 0, 1, C, dff, s, f.rows_dev));
+    }
+    {
+        const float* W[1] = {w.w2};
+        const float* b[1] = {w.b2};
+        float* C[1] = {f.out};
+        LAMP_CK(linear(f.hidden, f.M, dff, dff, W, 1, d, dff, b, f.x, d, 0, C, d, s, f.rows_dev, nullptr, f.rg));
+    }
+    LayerNormParams ln{f.out, f.M, d, w.ln_g, w.ln_b, f.out};
+    if (f.scatter) {
+        ln.M = int64_t(f.nb) * f.T; ln.scatter = f.scatter; ln.T = f.T; ln.y_flat = f.y_flat;
+    } else if (f.rows_dev) {
+        ln.m_dev = f.rows_dev;
+    } else if (f.w_out) {   // the final decoder LayerNorm also produces the logits and its output row is not stored
+        ln.y = nullptr; ln.w_out = f.w_out; ln.n_labels = f.n_labels; ln.logits = f.logits;
+    }
+    return launch_layernorm(ln, s);
+}
+
+// Scratch of one MultiHeadAttention call.
 struct MhaScratch {
     float *Q, *K, *V, *A;
     float* S = nullptr;    // (h*B, lq, lk) score scratch, only for d_k or d_v > 128 (attention_general.hip)
     float* lse = nullptr;  // [h][B][lq] row log-sum-exp: lets requested attention maps come from the single-pass kernel
-    int* plan_ints = nullptr;  // plan_int_count(B, lk) ints: the SeqPlan of a key-token mask when the caller did not bring one
+    int* plan_ints = nullptr;  // the SeqPlan of a key-token mask when the caller did not bring one
 };
-static inline size_t plan_int_count(int64_t B, int T) { return size_t(3) * size_t(B) + 3 + size_t(B) * size_t((T + 31) / 32); }
 static inline SeqPlan plan_from(int* ints, int64_t B, int T) {
     return SeqPlan{ints, ints + B, ints + 2 * B, ints + 3 * B + 1, reinterpret_cast<unsigned*>(ints + 3 * B + 3), (T + 31) / 32, nullptr};
 }
 static inline bool wide_heads(int dk, int dv) { return dk > 128 || dv > 128; }
+// the SeqPlan of c.mb samples of T keys: 3 mb + 3 ints and mb words of pad bits
+static inline void take_plan(Carver& c, int** ints, int T) { c.take(ints, 3 + size_t((T + 31) / 32), 3); }
 
-// The position-wise feed-forward block that follows an attention block in a decoder layer (lamp/Layers.py:35-36, :40-45):
-// handed to mha_core so that the attention's output projection, its LayerNorm and this block run as ONE launch
-// (chain.hip) when the shape allows.  `done` tells the caller whether that happened.
-struct FfnTail {
-    const lamp_ffn_weights* ffn;
-    int dff;
-    const float* w_out;   // fused read-out of the last decoder block (nullable), as in ffn_core
-    int n_labels;
-    float* logits;
-    bool done;
-    const lamp_chain_pack* pk;   // nullable: weights-only packed copies of (fc, w1, w2) for the chain launch
+// The scratch of an attention call with lq queries and lk keys per sample (c.mb samples).  `plan`: with the plan_ints region.
+static void mha_layout(Carver& c, MhaScratch& sc, int lq, int lk, int h, int dk, int dv, bool plan) {
+    c.take(&sc.Q, size_t(lq) * h * dk);
+    c.take(&sc.K, size_t(lk) * h * dk);
+    c.take(&sc.V, size_t(lk) * h * dv);
+    c.take(&sc.A, size_t(lq) * h * dv);
+    if (wide_heads(dk, dv)) c.take(&sc.S, size_t(h) * lq * lk);
+    c.take(&sc.lse, size_t(h) * lq);
+    if (plan) take_plan(c, &sc.plan_ints, lk);
+}
+
+// One MultiHeadAttention.forward (lamp/SubLayers.py:77-121) on B samples: mha_attend, then (with `out`) mha_tail.
+struct MhaCall {
+    const float* xq;   // [B, lq, d] queries, also the residual; `out` may alias it unless xq_shared
+    const float* xkv;  // [B, lk, d] keys and values
+    int B, lq, lk, d, dk, dv;
+    const lamp_mha_weights* w;
+    const lamp_mask* mask;
+    float* out;        // nullptr: the attention map only (the reference's dead encoder self-attention)
+    float* attn;       // nullable maps (h * P_batch, lq, lk): this call's samples are P_b0 + b
+    int P_batch = 0, P_b0 = 0;
+    bool xq_shared = false;            // xq is ONE [lq, d] block used by every sample (decoder layer 0: the label embeddings,
+                                       // SURVEY.md G11): its projection is computed once, the residual read modulo lq
+    const float* q_ready = nullptr;    // the query projection, already computed
+    bool kv_ready = false;             // the scratch's K / V already hold this call's projections (see forward)
+    const SeqPlan* keys = nullptr;     // per-sample key extents of a key-token mask (ragged batches)
+    bool keys_packed = false;          // xkv holds the packed token rows (keys->rows[0] of them, counted on the device)
+    const float* xkv_dense = nullptr;  // with keys_packed: the padded rows, read instead when nothing was skipped
 };
 
-// MultiHeadAttention.forward (lamp/SubLayers.py:77-121).  `xq_shared`: xq is ONE [lq, d] block used
-// by every sample (decoder layer 0: the label embeddings) -- its projection is then
-// computed once, and the residual is read modulo lq.  `out` may alias xq unless xq_shared.
-// `out == nullptr` computes the attention map only (the reference's dead encoder self-attention).
-static int mha_core(const float* xq, bool xq_shared, const float* xkv, int B, int lq, int lk, int d, int dk,
-                    int dv, const lamp_mha_weights& w, const lamp_mask* mask, float* out, float* attn,
-                    const MhaScratch& sc, hipStream_t s, bool kv_ready = false,
-                    const float* q_ready = nullptr, int P_batch = 0, int P_b0 = 0, const SeqPlan* keys = nullptr,
-                    bool keys_packed = false, const float* xkv_dense = nullptr, FfnTail* tail = nullptr) {
-    // keys: per-sample key extents of a key-token mask (ragged batches); keys_packed: xkv holds the packed token rows
-    // (keys->rows[0] of them, counted on the device) instead of [B, lk, d]
-    const int h = w.n_head;
-    if (h < 1 || dk < 1 || dv < 1) return LAMP_E_DIMS;
-    if (!w.w_qs || !w.w_ks || !w.w_vs || (out && (!w.ln_g || !w.ln_b))) return LAMP_E_NULL;
-    if (h == 1 && out && dv != d) return LAMP_E_DIMS;  // no fc: O is added to the residual directly
-    if (h > 1 && out && !w.fc) return LAMP_E_NULL;
-    const int hdk = h * dk, hdv = h * dv;
-    const int64_t Mq = xq_shared ? lq : int64_t(B) * lq;
-    const int64_t Mk = int64_t(B) * lk;
-    const bool self = (xq == xkv) && !xq_shared && lq == lk;
-    const bool need_v = out != nullptr;
 
-    if (self && hdk == hdv && need_v) {
-        float* C[3] = {sc.Q, sc.K, sc.V};
-        const float* W[3] = {w.w_qs, w.w_ks, w.w_vs};
-        LAMP_CK(linear(xq, Mq, d, d, W, 3, hdk, d, nullptr, nullptr, 0, 0, C, hdk, s));
-    } else {
-        if (!q_ready) {
-            const float* W[1] = {w.w_qs};
-            float* C[1] = {sc.Q};
-            LAMP_CK(linear(xq, Mq, d, d, W, 1, hdk, d, nullptr, nullptr, 0, 0, C, hdk, s));
-        }
-        const int* mk_dev = keys_packed ? keys->rows : nullptr;
-        const float* xd = keys_packed ? xkv_dense : nullptr;  // the padded rows, read instead when nothing was skipped
-        if (kv_ready) {
-            // sc.K / sc.V were projected earlier (every decoder layer's K/V in one launch, see forward_range)
-        } else if (need_v && hdk == hdv) {
-            const float* W[2] = {w.w_ks, w.w_vs};
-            float* C[2] = {sc.K, sc.V};
-            LAMP_CK(linear(xkv, Mk, d, d, W, 2, hdk, d, nullptr, nullptr, 0, 0, C, hdk, s, mk_dev, xd));
-        } else {
-            const float* Wk[1] = {w.w_ks};
-            float* Ck[1] = {sc.K};
-            LAMP_CK(linear(xkv, Mk, d, d, Wk, 1, hdk, d, nullptr, nullptr, 0, 0, Ck, hdk, s, mk_dev, xd));
-            if (need_v) {
-                const float* Wv[1] = {w.w_vs};
-                float* Cv[1] = {sc.V};
-                LAMP_CK(linear(xkv, Mk, d, d, Wv, 1, hdv, d, nullptr, nullptr, 0, 0, Cv, hdv, s, mk_dev, xd));
-            }
-        }
-    }
+// The attention step: projections, the key plan, the attention launch.  Checks the whole call before its first launch.
+static int mha_attend(const MhaCall& c, const MhaScratch& sc, hipStream_t s) {
+    const lamp_mha_weights& w = *c.w;
+    const int h = w.n_head, d = c.d, dk = c.dk, dv = c.dv, B = c.B, lq = c.lq, lk = c.lk;
+    if (h < 1 || dk < 1 || dv < 1) return LAMP_E_DIMS;
+    if (!w.w_qs || !w.w_ks || !w.w_vs || (c.out && (!w.ln_g || !w.ln_b))) return LAMP_E_NULL;
+    if (h == 1 && c.out && dv != d) return LAMP_E_DIMS;  // no fc: O is added to the residual directly
+    if (h > 1 && c.out && !w.fc) return LAMP_E_NULL;
+    const int hdk = h * dk, hdv = h * dv;
+    const bool need_v = c.out != nullptr;
+    const bool kv = !c.kv_ready;
+    LAMP_CK(project_qkv(w, d, dk, dv, c.xq, c.xq_shared ? lq : int64_t(B) * lq, c.q_ready ? nullptr : sc.Q, c.xkv, c.xkv,
+                        int64_t(B) * lk, kv ? sc.K : nullptr, kv && need_v ? sc.V : nullptr, s,
+                        c.keys_packed ? c.keys->rows : nullptr, c.keys_packed ? c.xkv_dense : nullptr));
 
     // A key-token mask without a plan (lamp_mha_fwd on its own): count each sample's keys here, padded layout, so that
     // the module-by-module route takes the same per-sample key split as lamp_forward -- same bits.
+    const lamp_mask* mask = c.mask;
+    const SeqPlan* keys = c.keys;
     SeqPlan local_plan{};
     if (!keys && mask && mask->kind == LAMP_MASK_KEY_TOKENS_I64 && sc.plan_ints && !wide_heads(dk, dv)) {
         local_plan = plan_from(sc.plan_ints, B, lk);
@@ -202,25 +271,18 @@ static int mha_core(const float* xq, bool xq_shared, const float* xkv, int B, in
     }
 
     AttnParams a{};
-    a.Q = q_ready ? q_ready : sc.Q; a.K = sc.K; a.V = need_v ? sc.V : nullptr; a.O = need_v ? sc.A : nullptr; a.P = attn;
+    a.Q = c.q_ready ? c.q_ready : sc.Q; a.K = sc.K; a.V = need_v ? sc.V : nullptr; a.O = need_v ? sc.A : nullptr; a.P = c.attn;
     a.scratch = sc.S;
     // maps + output: single-pass kernel (same O bits as without maps), scores normalised in place afterwards
-    if (attn && need_v && sc.lse) a.lse = sc.lse;
+    if (c.attn && need_v && sc.lse) a.lse = sc.lse;
     a.B = B; a.H = h; a.lq = lq; a.lk = lk; a.dk = dk; a.dv = dv;
-    a.P_batch = P_batch > 0 ? P_batch : B; a.P_b0 = P_b0;
-    a.lay.q_b = xq_shared ? 0 : int64_t(lq) * hdk; a.lay.q_h = dk; a.lay.q_r = hdk;
+    a.P_batch = c.P_batch > 0 ? c.P_batch : B; a.P_b0 = c.P_b0;
+    a.lay.q_b = c.xq_shared ? 0 : int64_t(lq) * hdk; a.lay.q_h = dk; a.lay.q_r = hdk;
     a.lay.k_b = int64_t(lk) * hdk; a.lay.k_h = dk; a.lay.k_r = hdk;
     a.lay.v_b = int64_t(lk) * hdv; a.lay.v_h = dv; a.lay.v_r = hdv;
     a.lay.o_b = int64_t(lq) * hdv; a.lay.o_h = dv; a.lay.o_r = hdv;
     a.scale_log2e = float(1.4426950408889634 / sqrt(double(dk)));
-    a.mask_kind = mask ? mask->kind : LAMP_MASK_NONE;
-    a.mask = mask ? mask->ptr : nullptr;
-    a.m_sb = mask ? mask->stride_b : 0;
-    a.m_sq = mask ? mask->stride_q : 0;
-    a.tiles = (mask && !attn) ? mask->tile_list : nullptr;
-    a.tiles_stride = mask ? mask->tile_list_stride : 0;
-    a.sparse_rows = mask && (mask->flags & LAMP_MASK_SPARSE_ROWS) != 0;
-    a.allowed_pairs = mask ? mask->allowed_pairs : 0;
+    attn_mask(a, mask);
     if (keys && mask && mask->kind == LAMP_MASK_KEY_TOKENS_I64) {
         a.kv_len = keys->klen;
         a.kv_off = keys->off;
@@ -231,19 +293,29 @@ static int mha_core(const float* xq, bool xq_shared, const float* xkv, int B, in
             a.m_sq = 0;
         }
     }
-    LAMP_CK(launch_attn(a, s));
-    if (!out) return 0;
+    return launch_attn(a, s);
+}
 
+// The tail step behind mha_attend (c.out set): fc (+ residual) -> LayerNorm into c.out.  With `f`, the position-wise
+// feed-forward block that follows the attention in a decoder layer (lamp/Layers.py:35-36, :40-45, reading and writing
+// c.out) may run in the same launch (chain.hip, with `pk`: weights-only packed copies of (fc, w1, w2)); then *ffn_ran tells
+// the caller whether it did.
+static int mha_tail(const MhaCall& c, const MhaScratch& sc, const FfnParams* f, const lamp_chain_pack* pk, bool* ffn_ran,
+                    hipStream_t s) {
+    const lamp_mha_weights& w = *c.w;
+    const int h = w.n_head, d = c.d, B = c.B, lq = c.lq, hdv = h * c.dv;
+    const float* xq = c.xq;
+    float* out = c.out;
     const int64_t M = int64_t(B) * lq;
-    const int64_t r_mod = xq_shared ? lq : 0;
-    if (tail) tail->done = false;
-    if (h > 1 && tail && tail->ffn && chain_applies(M, d, hdv, tail->dff, true, tail->pk, xq_shared, tail->w_out != nullptr)) {
+    const int64_t r_mod = c.xq_shared ? lq : 0;
+    if (f) *ffn_ran = false;
+    if (h > 1 && f && chain_applies(M, d, hdv, f->dff, true, pk, c.xq_shared, f->w_out != nullptr)) {
         // fc (+ residual) -> LayerNorm -> W1 -> W2 (+ residual) -> LayerNorm in one launch over 16-row panels (same bits)
-        tail->done = true;
-        return launch_chain(sc.A, hdv, hdv, xq, r_mod, M, d, w.fc, w.ln_g, w.ln_b, tail->ffn, tail->dff,
-                            tail->w_out ? nullptr : out, tail->w_out, tail->n_labels, tail->logits, s, tail->pk);
+        *ffn_ran = true;
+        return launch_chain(sc.A, hdv, hdv, xq, r_mod, M, d, w.fc, w.ln_g, w.ln_b, f->w, f->dff, f->w_out ? nullptr : out,
+                            f->w_out, f->n_labels, f->logits, s, pk);
     }
-    if (h > 1 && tail && tail->ffn && tail->pk && M > 6144 && (!tail->w_out || tail->n_labels == lq)) {
+    if (h > 1 && f && pk && M > 6144 && (!f->w_out || f->n_labels == lq)) {
         // Just past one chain launch's reach (6145-12288 rows: batch 69-136 at 90 labels) the tail is still faster as TWO chain
         // launches over halves of the batch -- whole samples, so that row % lq of the shared residual / read-out rows stays the
         // group-local row -- when each half fills the CUs with 24-row panels: batch 128 = 2 x 5760 rows, +6 % whole-forward
@@ -251,112 +323,28 @@ static int mha_core(const float* xq, bool xq_shared, const float* xkv, int B, in
         // five launches have enough tiles per GEMM to win (profiles/r05_batch_sweep.txt): both keep the separate launches.
         const int per = (B + 1) / 2, last = B - per;
         if (int64_t(per) * lq <= 6144 && int64_t(last) * lq > 4608 &&
-            chain_applies(int64_t(per) * lq, d, hdv, tail->dff, true, tail->pk, xq_shared, tail->w_out != nullptr) &&
-            chain_applies(int64_t(last) * lq, d, hdv, tail->dff, true, tail->pk, xq_shared, tail->w_out != nullptr)) {
+            chain_applies(int64_t(per) * lq, d, hdv, f->dff, true, pk, c.xq_shared, f->w_out != nullptr) &&
+            chain_applies(int64_t(last) * lq, d, hdv, f->dff, true, pk, c.xq_shared, f->w_out != nullptr)) {
             for (int g = 0; g < 2; ++g) {
                 const int64_t r0 = int64_t(g) * per * lq, rows = int64_t(g == 0 ? per : last) * lq;
-                LAMP_CK(launch_chain(sc.A + r0 * hdv, hdv, hdv, xq_shared ? xq : xq + r0 * d, r_mod, rows, d, w.fc, w.ln_g, w.ln_b,
-                                     tail->ffn, tail->dff, tail->w_out ? nullptr : out + r0 * d, tail->w_out, tail->n_labels,
-                                     tail->logits ? tail->logits + r0 : nullptr, s, tail->pk));
+                LAMP_CK(launch_chain(sc.A + r0 * hdv, hdv, hdv, c.xq_shared ? xq : xq + r0 * d, r_mod, rows, d, w.fc, w.ln_g,
+                                     w.ln_b, f->w, f->dff, f->w_out ? nullptr : out + r0 * d, f->w_out, f->n_labels,
+                                     f->logits ? f->logits + r0 : nullptr, s, pk));
             }
-            tail->done = true;
+            *ffn_ran = true;
             return 0;
         }
     }
+    // the residual: added by the fc GEMM, or by the LayerNorm kernel when there is no fc (O is added directly) or when it
+    // is the shared [lq, d] block (row modulo lq)
+    LayerNormParams ln{h == 1 ? sc.A : out, M, d, w.ln_g, w.ln_b, out};
+    if (h == 1 || c.xq_shared) { ln.residual = xq; ln.r_mod = r_mod; }
     if (h > 1) {
         const float* W[1] = {w.fc};
         float* C[1] = {out};
-        if (xq_shared) {
-            // residual = the shared [lq, d] block: added (row modulo lq) by the LayerNorm kernel
-            LAMP_CK(linear(sc.A, M, hdv, hdv, W, 1, d, hdv, nullptr, nullptr, 0, 0, C, d, s));
-            return launch_layernorm(out, M, d, w.ln_g, w.ln_b, 1e-5f, xq, r_mod, out, s);
-        }
-        LAMP_CK(linear(sc.A, M, hdv, hdv, W, 1, d, hdv, nullptr, xq, d, 0, C, d, s));
-        return launch_layernorm(out, M, d, w.ln_g, w.ln_b, 1e-5f, nullptr, 0, out, s);
+        LAMP_CK(linear(sc.A, M, hdv, hdv, W, 1, d, hdv, nullptr, ln.residual ? nullptr : xq, ln.residual ? 0 : d, 0, C, d, s));
     }
-    return launch_layernorm(sc.A, M, d, w.ln_g, w.ln_b, 1e-5f, xq, r_mod, out, s);
-}
-
-// K and V projections of one attention block on their own (same launches mha_core would issue).
-static int project_kv(const float* xkv, int64_t Mk, int d, int dk, int dv, const lamp_mha_weights& w, float* K,
-                      float* V, hipStream_t s, const int* m_dev = nullptr, const float* A_dense = nullptr) {
-    const int hdk = w.n_head * dk, hdv = w.n_head * dv;
-    if (hdk == hdv) {
-        const float* W[2] = {w.w_ks, w.w_vs};
-        float* C[2] = {K, V};
-        return linear(xkv, Mk, d, d, W, 2, hdk, d, nullptr, nullptr, 0, 0, C, hdk, s, m_dev, A_dense);
-    }
-    const float* Wk[1] = {w.w_ks};
-    float* Ck[1] = {K};
-    LAMP_CK(linear(xkv, Mk, d, d, Wk, 1, hdk, d, nullptr, nullptr, 0, 0, Ck, hdk, s, m_dev, A_dense));
-    const float* Wv[1] = {w.w_vs};
-    float* Cv[1] = {V};
-    return linear(xkv, Mk, d, d, Wv, 1, hdv, d, nullptr, nullptr, 0, 0, Cv, hdv, s, m_dev, A_dense);
-}
-
-// K and V projections of the first n decoder layers' enc-attention from the same encoder output: ONE launch when the
-// 2n weight matrices fit the GEMM's segment list (n <= 2) -- 4 x more tiles per launch than layer by layer.
-static int project_kv_layers(const float* x, int64_t Me, int d, int dk, int dv, const lamp_dec_layer* layers, int n,
-                             float* const* K, float* const* V, hipStream_t s, const int* m_dev = nullptr,
-                             const float* A_dense = nullptr) {
-    const int h = layers[0].enc_attn.n_head;
-    bool uniform = 2 * n <= GEMM_MAX_SEG && h * dk == h * dv;
-    for (int i = 1; i < n && uniform; ++i) uniform = layers[i].enc_attn.n_head == h;
-    if (uniform) {
-        const float* W[GEMM_MAX_SEG];
-        float* C[GEMM_MAX_SEG];
-        for (int i = 0; i < n; ++i) {
-            if (!layers[i].enc_attn.w_ks || !layers[i].enc_attn.w_vs) return LAMP_E_NULL;
-            W[2 * i] = layers[i].enc_attn.w_ks;
-            W[2 * i + 1] = layers[i].enc_attn.w_vs;
-            C[2 * i] = K[i];
-            C[2 * i + 1] = V[i];
-        }
-        return linear(x, Me, d, d, W, 2 * n, h * dk, d, nullptr, nullptr, 0, 0, C, h * dk, s, m_dev, A_dense);
-    }
-    for (int i = 0; i < n; ++i) LAMP_CK(project_kv(x, Me, d, dk, dv, layers[i].enc_attn, K[i], V[i], s, m_dev, A_dense));
-    return 0;
-}
-
-// PositionwiseFeedForward.forward (lamp/SubLayers.py:133-142); out may alias x.
-// Packed encoder rows (ragged batches): `rows_dev` = the live row count in device memory (M is the upper bound the
-// launches are sized for); with `scatter` this is the LAST encoder layer, whose LayerNorm also writes the padded
-// [nb, T, d] encoder output `y_flat` (see layernorm_kernel<.., RG = 2>).
-// `hidden_ready`: relu(x W1^T + b1) is already in `hidden` (the encoder's first layer with W1 folded into the embedding
-// tables, pointwise.hip: gather_row) -- the first GEMM is not launched.
-static int ffn_core(const float* x, int64_t M, int d, int dff, const lamp_ffn_weights& w, float* out,
-                    float* hidden, hipStream_t s, const float* w_out = nullptr, int n_labels = 0,
-                    float* logits = nullptr, const int* rows_dev = nullptr, const SeqPlan* scatter = nullptr,
-                    int nb = 0, int T = 0, float* y_flat = nullptr, bool hidden_ready = false, const ResGather* rg = nullptr) {
-    if (!w.w1 || !w.b1 || !w.w2 || !w.b2 || !w.ln_g || !w.ln_b) return LAMP_E_NULL;
-    if (rg && !hidden_ready) return LAMP_E_UNSUPPORTED;   // x itself does not exist then: only the residual may ask for it
-    if (!hidden_ready) {
-        const float* W[1] = {w.w1};
-        const float* b[1] = {w.b1};
-        float* C[1] = {hidden};
-        LAMP_CK(linear(x, M, d, d, W, 1, dff, d, b, nullptr, 0, 1, C, dff, s, rows_dev));
-    }
-    {
-        const float* W[1] = {w.w2};
-        const float* b[1] = {w.b2};
-        float* C[1] = {out};
-        LAMP_CK(linear(hidden, M, dff, dff, W, 1, d, dff, b, x, d, 0, C, d, s, rows_dev, nullptr, rg));
-    }
-    if (scatter)
-        return launch_layernorm(out, int64_t(nb) * T, d, w.ln_g, w.ln_b, 1e-5f, nullptr, 0, out, s, nullptr, 0, nullptr,
-                                nullptr, nullptr, scatter, T, y_flat);
-    if (rows_dev)
-        return launch_layernorm(out, M, d, w.ln_g, w.ln_b, 1e-5f, nullptr, 0, out, s, nullptr, 0, nullptr, nullptr, rows_dev);
-    // with w_out: the final decoder LayerNorm also produces the logits and its output row is not stored
-    return launch_layernorm(out, M, d, w.ln_g, w.ln_b, 1e-5f, nullptr, 0, w_out ? nullptr : out, s, w_out, n_labels,
-                            logits);
-}
-
-static size_t mha_ws_floats(int64_t B, int64_t lq, int64_t lk, int hdk, int hdv, int64_t score_floats = 0) {
-    // Q, K, V, A (+ the score scratch of wide heads) -- each rounded to 256 bytes by the carver
-    auto r = [](size_t n) { return align_up(n * sizeof(float), 256) / sizeof(float); };
-    return r(size_t(B) * lq * hdk) + r(size_t(B) * lk * hdk) + r(size_t(B) * lk * hdv) + r(size_t(B) * lq * hdv) +
-           (score_floats ? r(size_t(score_floats)) : 0);
+    return launch_layernorm(ln, s);
 }
 
 }  // namespace lamp
@@ -375,14 +363,7 @@ int sdpa_impl(const float* q, const float* k, const float* v, float* out, float*
     a.P_batch = B; a.P_b0 = 0;
     a.lay = *layout;
     a.scale_log2e = float(double(inv_temperature) * 1.4426950408889634);
-    a.mask_kind = mask ? mask->kind : LAMP_MASK_NONE;
-    a.mask = mask ? mask->ptr : nullptr;
-    a.m_sb = mask ? mask->stride_b : 0;
-    a.m_sq = mask ? mask->stride_q : 0;
-    a.tiles = (mask && !attn) ? mask->tile_list : nullptr;
-    a.tiles_stride = mask ? mask->tile_list_stride : 0;
-    a.sparse_rows = mask && (mask->flags & LAMP_MASK_SPARSE_ROWS) != 0;
-    a.allowed_pairs = mask ? mask->allowed_pairs : 0;
+    attn_mask(a, mask);
     return launch_attn(a, hipStream_t(stream));
 }
 }  // namespace
@@ -418,7 +399,8 @@ int lamp_linear_fwd(const float* A, int64_t M, int32_t K, int64_t lda, const flo
 
 int lamp_layernorm_fwd(const float* x, int64_t M, int32_t d, const float* gamma, const float* beta, float eps,
                        float* y, lamp_stream_t stream) {
-    return launch_layernorm(x, M, d, gamma, beta, eps, nullptr, 0, y, hipStream_t(stream));
+    LayerNormParams p{x, M, d, gamma, beta, y, eps};
+    return launch_layernorm(p, hipStream_t(stream));
 }
 
 int lamp_sdpa_fwd(const float* q, const float* k, const float* v, float* out, float* attn, int32_t B, int32_t H,
@@ -439,10 +421,10 @@ size_t lamp_mha_workspace_bytes(int32_t B, int32_t lq, int32_t lk, int32_t d_mod
                                 int32_t d_v) {
     (void)d_model;
     if (B <= 0 || lq <= 0 || lk <= 0 || n_head <= 0 || d_k <= 0 || d_v <= 0) return 0;
-    return (mha_ws_floats(B, lq, lk, n_head * d_k, n_head * d_v,
-                          wide_heads(d_k, d_v) ? int64_t(n_head) * B * lq * lk : 0) +
-            align_up(size_t(n_head) * B * lq * sizeof(float), 256) / sizeof(float) +
-            align_up(plan_int_count(B, lk) * sizeof(int), 256) / sizeof(float)) * sizeof(float);
+    Carver c{nullptr, size_t(B)};
+    MhaScratch sc;
+    mha_layout(c, sc, lq, lk, n_head, d_k, d_v, true);
+    return c.off;
 }
 
 int lamp_mha_fwd(const float* xq, const float* xkv, int32_t B, int32_t lq, int32_t lk, int32_t d_model,
@@ -452,18 +434,13 @@ int lamp_mha_fwd(const float* xq, const float* xkv, int32_t B, int32_t lq, int32
     if (B <= 0 || lq <= 0 || lk <= 0 || d_model <= 0 || d_k <= 0 || d_v <= 0 || w->n_head <= 0) return LAMP_E_DIMS;
     if (d_model & 3) return LAMP_E_UNSUPPORTED;
     LAMP_CK(check_mask(mask));
-    const int hdk = w->n_head * d_k, hdv = w->n_head * d_v;
-    Carver c(workspace, workspace_bytes);
+    Carver c{static_cast<char*>(workspace), size_t(B)};
     MhaScratch sc;
-    sc.Q = c.take(size_t(B) * lq * hdk);
-    sc.K = c.take(size_t(B) * lk * hdk);
-    sc.V = c.take(size_t(B) * lk * hdv);
-    sc.A = c.take(size_t(B) * lq * hdv);
-    if (wide_heads(d_k, d_v)) sc.S = c.take(size_t(w->n_head) * B * lq * lk);
-    sc.lse = c.take(size_t(w->n_head) * B * lq);
-    sc.plan_ints = reinterpret_cast<int*>(c.take(plan_int_count(B, lk)));
-    if (!c.ok) return LAMP_E_WORKSPACE;
-    return mha_core(xq, false, xkv, B, lq, lk, d_model, d_k, d_v, *w, mask, out, attn, sc, hipStream_t(stream));
+    mha_layout(c, sc, lq, lk, w->n_head, d_k, d_v, true);
+    if (c.off > workspace_bytes) return LAMP_E_WORKSPACE;
+    const MhaCall a{xq, xkv, B, lq, lk, d_model, d_k, d_v, w, mask, out, attn};
+    LAMP_CK(mha_attend(a, sc, hipStream_t(stream)));
+    return mha_tail(a, sc, nullptr, nullptr, nullptr, hipStream_t(stream));
 }
 
 size_t lamp_ffn_workspace_bytes(int64_t M, int32_t d_model, int32_t d_inner) {
@@ -478,7 +455,7 @@ int lamp_ffn_fwd(const float* x, int64_t M, int32_t d_model, int32_t d_inner, co
     if (M <= 0 || d_model <= 0 || d_inner <= 0) return LAMP_E_DIMS;
     if ((d_model & 3) || (d_inner & 3)) return LAMP_E_UNSUPPORTED;
     if (workspace_bytes < size_t(M) * d_inner * sizeof(float)) return LAMP_E_WORKSPACE;
-    return ffn_core(x, M, d_model, d_inner, *w, out, static_cast<float*>(workspace), hipStream_t(stream));
+    return ffn_core(FfnParams{x, M, d_model, d_inner, w, out, static_cast<float*>(workspace)}, hipStream_t(stream));
 }
 
 int lamp_embed_fwd(const int64_t* src_seq, const int64_t* src_pos, int64_t n_tokens, const float* emb,
@@ -520,8 +497,9 @@ int lamp_layernorm_residual_fwd(const float* x, const float* residual, int64_t r
     if (!y) return LAMP_E_NULL;
     if (!(dropout_p >= 0.f) || !(dropout_p < 1.f)) return LAMP_E_UNSUPPORTED;
     const DropoutSpec ds = make_dropout(dropout_p, seed);
-    return launch_layernorm(x, M, d, gamma, beta, eps, residual, residual_rows, y, hipStream_t(stream), nullptr, 0,
-                            nullptr, dropout_p > 0.f ? &ds : nullptr);
+    LayerNormParams p{x, M, d, gamma, beta, y, eps};
+    p.residual = residual; p.r_mod = residual_rows; p.drop = dropout_p > 0.f ? &ds : nullptr;
+    return launch_layernorm(p, hipStream_t(stream));
 }
 
 size_t lamp_layernorm_bwd_workspace_bytes(int64_t M, int32_t d) { return layernorm_bwd_workspace_bytes(M, d); }
@@ -609,8 +587,9 @@ int lamp_ffn_train_fwd(const float* x, int64_t M, int32_t d_model, int32_t d_inn
         LAMP_CK(linear(h, M, d_inner, d_inner, W, 1, d_model, d_inner, b, nullptr, 0, 0, C, d_model, s));
     }
     const DropoutSpec ds = make_dropout(dropout_p, seed);
-    return launch_layernorm(o, M, d_model, w->ln_g, w->ln_b, 1e-5f, x, 0, y, s, nullptr, 0, nullptr,
-                            dropout_p > 0.f ? &ds : nullptr);
+    LayerNormParams p{o, M, d_model, w->ln_g, w->ln_b, y};
+    p.residual = x; p.drop = dropout_p > 0.f ? &ds : nullptr;
+    return launch_layernorm(p, s);
 }
 
 size_t lamp_ffn_bwd_workspace_bytes(int64_t M, int32_t d_model, int32_t d_inner) {
@@ -689,25 +668,7 @@ int lamp_mha_train_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, 
     hipStream_t s = hipStream_t(stream);
     const int hdk = H * dk, hdv = H * dv;
     const int64_t Mq = int64_t(B) * lq, Mk = int64_t(B) * lk;
-    // the projections that share their input go out as segments of one launch (same bits as one launch each)
-    const bool one_kv = xk == xv && hdk == hdv, one_qkv = one_kv && xq == xk && lq == lk;
-    {
-        const float* W[3] = {w->w_qs, w->w_ks, w->w_vs};
-        float* C[3] = {q, k, v};
-        LAMP_CK(linear(xq, Mq, d, d, W, one_qkv ? 3 : 1, hdk, d, nullptr, nullptr, 0, 0, C, hdk, s));
-    }
-    if (!one_qkv && one_kv) {
-        const float* W[2] = {w->w_ks, w->w_vs};
-        float* C[2] = {k, v};
-        LAMP_CK(linear(xk, Mk, d, d, W, 2, hdk, d, nullptr, nullptr, 0, 0, C, hdk, s));
-    } else if (!one_qkv) {
-        const float* Wk[1] = {w->w_ks};
-        float* Ck[1] = {k};
-        LAMP_CK(linear(xk, Mk, d, d, Wk, 1, hdk, d, nullptr, nullptr, 0, 0, Ck, hdk, s));
-        const float* Wv[1] = {w->w_vs};
-        float* Cv[1] = {v};
-        LAMP_CK(linear(xv, Mk, d, d, Wv, 1, hdv, d, nullptr, nullptr, 0, 0, Cv, hdv, s));
-    }
+    LAMP_CK(project_qkv(*w, d, dk, dv, xq, Mq, q, xk, xv, Mk, k, v, s, nullptr, nullptr));
     const lamp_attn_layout lay{int64_t(lq) * hdk, dk, hdk, int64_t(lk) * hdk, dk, hdk, int64_t(lk) * hdv, dv, hdv,
                                int64_t(lq) * hdv, dv, hdv};
     LAMP_CK(sdpa_impl(q, k, v, a, P, lse, B, H, lq, lk, dk, dv, c->inv_temperature, mask, &lay, stream));
@@ -724,8 +685,9 @@ int lamp_mha_train_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, 
         LAMP_CK(linear(a, Mq, hdv, hdv, W, 1, d, hdv, nullptr, nullptr, 0, 0, C, d, s));
         pre = o;
     }
-    return launch_layernorm(pre, Mq, d, w->ln_g, w->ln_b, 1e-5f, xq, 0, y, s, nullptr, 0, nullptr,
-                            c->p_out > 0.f ? &ds : nullptr);
+    LayerNormParams ln{pre, Mq, d, w->ln_g, w->ln_b, y};
+    ln.residual = xq; ln.drop = c->p_out > 0.f ? &ds : nullptr;
+    return launch_layernorm(ln, s);
 }
 
 size_t lamp_mha_bwd_workspace_bytes(const lamp_mha_train_desc* c) {
@@ -821,284 +783,256 @@ int lamp_sigmoid_bce_fwd(const float* logits, const float* targets, int64_t n_ro
 }
 
 // ------------------------------------------------------------------ whole forward
-static int model_heads(const lamp_model* m, int* h_max) {
-    int h = 1;
-    for (int i = 0; i < m->n_layers_enc; ++i) h = h > m->enc_layers[i].slf_attn.n_head ? h : m->enc_layers[i].slf_attn.n_head;
-    for (int i = 0; i < m->n_layers_dec; ++i) {
-        const lamp_dec_layer& l = m->dec_layers[i];
-        h = h > l.enc_attn.n_head ? h : l.enc_attn.n_head;
-        if (l.slf_attn.present) h = h > l.slf_attn.n_head ? h : l.slf_attn.n_head;
-    }
-    *h_max = h;
-    return 0;
-}
-
-struct FwdPlan {
-    size_t fixed_floats;       // independent of the micro-batch
-    size_t per_sample_floats;  // times micro-batch
-    int R;                     // rows per sample of the widest activation
-    int hdk, hdv;
-    size_t side_kv_floats;     // per sample; K/V of every decoder layer's enc-attention, projected in one launch
-    size_t score_floats;       // per sample; (h, Rq, R) score scratch of wide heads, else 0
-    size_t lse_floats;         // per sample; (h, Rq)
+// Shapes of one whole forward: what its workspace layout and its stages read.
+struct FwdDims {
+    int T, L, R, Rq;         // encoder rows per sample, labels, max(T, L), Q / A rows (R with the encoder's maps, else L)
+    int d, dff, h, dk, dv;   // h: the most heads of any attention block
+    int n_ahead;             // decoder layers whose enc-attention K / V are projected right after the encoder, or 0
+    int fe_rows;             // one-hot front end: padded conv2 input rows per sample, else 0
+    bool w2_repack;          // one-hot front end without a caller-packed conv2 weight
 };
 
-static int make_plan(const lamp_model* m, int T, int want_attn, FwdPlan* pl) {
+// The model checks the workspace sizes share with the forward.  T_in: tokens per sample; the one-hot front end `fe`
+// halves them.  The K/V-ahead buffers are counted for every decoder layer of a token model: the forward drops them
+// (n_ahead = 0) when it does not project ahead.
+static int fwd_dims(const lamp_model* m, const lamp_onehot_frontend* fe, int T_in, bool want_attn, FwdDims* g) {
     if (!m) return LAMP_E_NULL;
+    const int T = fe ? T_in / 2 : T_in;
     if (m->d_model <= 0 || m->d_inner <= 0 || m->d_k <= 0 || m->d_v <= 0 || m->n_labels <= 0 || T <= 0 ||
         m->n_layers_enc < 0 || m->n_layers_dec < 0)
         return LAMP_E_DIMS;
     if ((m->n_layers_enc && !m->enc_layers) || (m->n_layers_dec && !m->dec_layers)) return LAMP_E_NULL;
     int h = 1;
-    model_heads(m, &h);
-    const int L = m->n_labels;
-    const int R = T > L ? T : L;
-    pl->R = R;
-    pl->hdk = h * m->d_k;
-    pl->hdv = h * m->d_v;
-    const int Rq = want_attn ? R : L;  // the Q / A buffers only see encoder rows when maps are wanted
-    // + 64 floats of slack per region for the carver's 256-byte rounding
-    pl->fixed_floats = 64 * 11;
-    pl->per_sample_floats = size_t(R) * m->d_inner + size_t(Rq) * pl->hdk + size_t(R) * pl->hdk +
-                            size_t(R) * pl->hdv + size_t(Rq) * pl->hdv + size_t(L) * m->d_model;
-    // wide heads (d_k or d_v > 128): the scores of the largest attention of the forward go through this scratch
-    pl->score_floats = wide_heads(m->d_k, m->d_v) ? size_t(h) * Rq * R : 0;
-    pl->per_sample_floats += pl->score_floats;
-    pl->lse_floats = size_t(h) * Rq;  // row log-sum-exp of an attention whose maps are requested
-    pl->per_sample_floats += pl->lse_floats;
-    // ragged batches: the packed token rows of the encoder ([n_tok + 1, d]: + the shared PAD row), one more row of the
-    // FFN hidden buffer for it, and the SeqPlan's 3 mb + 3 ints
-    pl->per_sample_floats += size_t(T) * m->d_model + 3 + size_t((T + 31) / 32);
-    pl->fixed_floats += size_t(m->d_model) + size_t(m->d_inner) + 64 * 3 + 4;
-    // the plan's hand-off granules inside the merged plan + gather launch: 2 mb + 2 eight-byte words
-    pl->per_sample_floats += 4;
-    pl->fixed_floats += 4 + 64;
-    // the row -> (token, position) maps of the gathered residual (folded first encoder layer): 2 (mb T + 1) ints
-    pl->per_sample_floats += 2 * size_t(T);
-    pl->fixed_floats += 2 + 64;
-    // K/V of all decoder layers' enc-attention, projected together right after the encoder when the batch fits
-    pl->side_kv_floats = size_t(m->n_layers_dec) * T * (pl->hdk + pl->hdv);
+    for (int i = 0; i < m->n_layers_enc; ++i) h = std::max(h, m->enc_layers[i].slf_attn.n_head);
+    for (int i = 0; i < m->n_layers_dec; ++i) {
+        const lamp_dec_layer& l = m->dec_layers[i];
+        h = std::max(h, l.enc_attn.n_head);
+        if (l.slf_attn.present) h = std::max(h, l.slf_attn.n_head);
+    }
+    const int L = m->n_labels, R = std::max(T, L);
+    *g = FwdDims{T, L, R, want_attn ? R : L, m->d_model, m->d_inner, h, m->d_k, m->d_v, fe ? 0 : m->n_layers_dec,
+                 fe ? T + 16 : 0, fe && !fe->conv2_pack};
     return 0;
 }
 
-size_t lamp_forward_workspace_bytes(const lamp_model* m, int32_t micro_batch, int32_t T, int32_t want_attn) {
-    FwdPlan pl;
-    if (micro_batch <= 0 || make_plan(m, T, want_attn, &pl) != 0) return 0;
-    return (pl.fixed_floats + (pl.per_sample_floats + pl.side_kv_floats) * size_t(micro_batch)) * sizeof(float);
+// The carved workspace of the forward.
+struct FwdScratch {
+    float* H;           // FFN hidden rows (+ one for the shared PAD row of the packed layout)
+    MhaScratch mha;     // Q, K, V, A (+ S of wide heads), lse of the largest attention
+    float* Y;           // decoder rows
+    float* Xp;          // packed encoder rows [n_tok + 1, d]: + the shared PAD row
+    int* plan_ints;     // the micro-batch's SeqPlan
+    unsigned long long* granules;   // the plan's hand-off words inside the merged plan + gather launch: 2 mb + 2
+    int *row_tok, *row_pos;         // [mb T + 1] each: token / position of every packed row, for the gathered residual
+    float *K_ahead[GEMM_MAX_SEG / 2], *V_ahead[GEMM_MAX_SEG / 2];   // K/V ahead
+    float* fe_x;        // the one-hot front end's zero-padded channel-last conv2 input
+    float* w2;          // conv2's packed weight
+};
+
+// THE forward workspace: every region, in carve order.
+static void fwd_layout(const FwdDims& g, Carver& c, FwdScratch& w) {
+    const size_t T = g.T, d = g.d;
+    c.take(&w.H, size_t(g.R) * g.dff, g.dff);
+    mha_layout(c, w.mha, g.Rq, g.R, g.h, g.dk, g.dv, false);
+    c.take(&w.Y, size_t(g.L) * d);
+    c.take(&w.Xp, T * d, d);
+    take_plan(c, &w.plan_ints, g.T);
+    c.take(&w.granules, 4, 4);
+    c.take(&w.row_tok, 2 * T, 2);
+    for (int i = 0; i < g.n_ahead; ++i) {   // the byte bound may count more layers than the forward projects ahead
+        const bool kept = i < GEMM_MAX_SEG / 2;
+        c.take(kept ? &w.K_ahead[i] : nullptr, T * g.h * g.dk);
+        c.take(kept ? &w.V_ahead[i] : nullptr, T * g.h * g.dv);
+    }
+    if (g.fe_rows) c.take(&w.fe_x, size_t(g.fe_rows) * d, 16 * d);
+    if (g.w2_repack) c.take(&w.w2, 0, 16 * d * d);
+    w.row_pos = w.row_tok ? w.row_tok + (c.mb * T + 1) : nullptr;
 }
 
-// The whole batch in micro-batches that fit `workspace`.  `kv_ahead`: the enc-attention K/V projections of EVERY
-// decoder layer (they depend only on the encoder output) are issued as one multi-segment launch right after the
-// encoder.  Samples are independent and no kernel variant depends on the batch size, so a sample's results are
-// bit-identical for every micro-batch split.
-constexpr int MAX_AHEAD_LAYERS = 16;
-static inline size_t onehot_rows(int T_in) { return size_t(T_in / 2 + 16); }   // padded conv2 input rows per sample
-// `fe` (lamp_onehot_forward): the one-hot genomics front end replaces the embedding gather; the encoder then sees T / 2 rows
-// of each sample (T_in tokens, row stride T_in in src_seq / src_pos) in the padded layout.
-static int forward_range(const lamp_model* m, const FwdPlan& pl, const int64_t* src_seq, const int64_t* src_pos,
-                         int32_t B, int32_t T_in, float* logits, float* enc_output, const lamp_aux* aux,
-                         void* workspace, size_t workspace_bytes, hipStream_t s, bool kv_ahead,
-                         const lamp_onehot_frontend* fe = nullptr, const float* w2_pack = nullptr) {
-    const int T = fe ? T_in / 2 : T_in;   // encoder rows per sample
-    const int64_t ld_seq = T_in;
-    const bool want_enc_attn = aux && aux->enc_self_attn;
-    const int d = m->d_model, dff = m->d_inner, dk = m->d_k, dv = m->d_v, L = m->n_labels;
-    const int n_ahead = kv_ahead ? m->n_layers_dec : 0;
-    const size_t per_sample = pl.per_sample_floats + (n_ahead ? pl.side_kv_floats : 0);
-    const size_t ws_floats = workspace_bytes / sizeof(float);
-    if (ws_floats < pl.fixed_floats + per_sample) return LAMP_E_WORKSPACE;
-    int64_t mb = int64_t((ws_floats - pl.fixed_floats) / per_sample);
-    if (mb > B) mb = B;
+static Carver fwd_size(const FwdDims& g) {
+    Carver c{nullptr, 1};
+    FwdScratch unused;
+    fwd_layout(g, c, unused);
+    return c;
+}
 
-    // Ragged batches.  Every micro-batch first counts its samples' extents on the device (SeqPlan).  `packed`: the encoder
-    // runs on the packed non-PAD token rows (+ ONE shared PAD row: all PAD positions of lamp/Encoders.py:64-79 hold the
-    // same row-wise result), its last LayerNorm scatters into the padded enc_output, and K / V are projected from the
-    // packed rows only.  Row-wise kernels and an M-independent k-order make this bit-identical to computing every
-    // padded position.  Not packed (the dead encoder self-attention's maps are wanted, or wide heads): padded layout as
-    // before; the enc-dec attention still stops at each sample's last real key either way.
-    const bool packed = !want_enc_attn && !wide_heads(dk, dv) && m->n_layers_enc > 0 && !fe;
-    const int Rq = want_enc_attn ? pl.R : L;
-    float *H = nullptr, *Y = nullptr, *Xp = nullptr;
-    int* plan_ints = nullptr;
-    int* row_maps = nullptr;   // [2][mb T + 1]: token / position index of every (packed) encoder row, for the gathered residual
-    unsigned long long* granules = nullptr;
-    float* Kahead[MAX_AHEAD_LAYERS] = {};
-    float* Vahead[MAX_AHEAD_LAYERS] = {};
-    MhaScratch sc{};
-    float* fe_x = nullptr;   // the front end's zero-padded channel-last conv2 input
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        Carver c(workspace, workspace_bytes);
-        H = c.take(size_t(mb) * pl.R * dff + dff);
-        sc.Q = c.take(size_t(mb) * Rq * pl.hdk);
-        sc.K = c.take(size_t(mb) * pl.R * pl.hdk);
-        sc.V = c.take(size_t(mb) * pl.R * pl.hdv);
-        sc.A = c.take(size_t(mb) * Rq * pl.hdv);
-        sc.S = pl.score_floats ? c.take(size_t(mb) * pl.score_floats) : nullptr;
-        sc.lse = c.take(size_t(mb) * pl.lse_floats);
-        Y = c.take(size_t(mb) * L * d);
-        Xp = c.take(size_t(mb) * T * d + d);
-        plan_ints = reinterpret_cast<int*>(c.take(plan_int_count(mb, T)));
-        granules = reinterpret_cast<unsigned long long*>(c.take(size_t(4) * mb + 4));
-        row_maps = reinterpret_cast<int*>(c.take(2 * (size_t(mb) * T + 1)));
-        for (int i = 0; i < n_ahead; ++i) {
-            Kahead[i] = c.take(size_t(mb) * T * pl.hdk);
-            Vahead[i] = c.take(size_t(mb) * T * pl.hdv);
-        }
-        if (fe) fe_x = c.take(size_t(mb) * onehot_rows(T_in) * d + size_t(16) * d);
-        if (c.ok) break;
-        if (attempt == 1 || mb <= 1) return LAMP_E_WORKSPACE;
-        --mb;  // rounding slack exhausted: one sample fewer
+// One micro-batch of the forward: what its stages share.
+struct Pass {
+    const lamp_model* m;
+    const lamp_onehot_frontend* fe;
+    const FwdDims& g;
+    const FwdScratch& w;
+    const lamp_aux* aux;
+    float* logits;          // of the whole batch
+    hipStream_t s;
+    int B, nb;              // samples of the batch, of this micro-batch
+    int64_t b0;             // this micro-batch's first sample
+    const int64_t *seq, *pos;   // [nb, ld_seq] tokens and (nullable) positions
+    int64_t ld_seq;
+    float* x;               // [nb, T, d] padded encoder output rows
+    bool packed;
+    SeqPlan sp;
+    lamp_mask pad_mask;
+    lamp_mask label_mask;
+    const float* xk = nullptr;   // what the decoder's K / V projections read: x or the packed rows
+    int n_int = 0;               // intermediate predictions written so far
+};
+
+// GraphEncoder.forward (lamp/Encoders.py:64-110) on the packed non-PAD token rows (+ ONE shared PAD row: all PAD positions
+// of lamp/Encoders.py:64-79 hold the same row-wise result); the last LayerNorm scatters into the padded encoder output.
+// Row-wise kernels and an M-independent k-order make this bit-identical to computing every padded position.
+static int encode_packed(Pass& p) {
+    const lamp_model* m = p.m;
+    const FwdScratch& w = p.w;
+    const int d = p.g.d, dff = p.g.dff, T = p.g.T;
+    // The plan rides in the first workgroups of the embedding gather's launch and hands its results to the gather through
+    // 8-byte granules (pointwise.hip: embed_plan_kernel; round 3 had it as a launch of its own -- a dependent launch costs
+    // 5-8 us on this chain however little it does -- after folding it into EVERY workgroup of the gather had measured
+    // slower, 21.9 us against 6.6 + 10.5).
+    // Encoder layer 0's W1 folded into the embedding tables (lamp_model::enc0_emb_w1): the gather writes that layer's
+    // hidden rows into H beside the embedded rows, and its first GEMM is not launched.
+    // ... and the embedded rows themselves are not written either: their one reader, the residual of that layer's second
+    // GEMM, gathers them from the tables through the row maps the gather kernel leaves instead (8 bytes per row).
+    const bool folded = m->enc0_emb_w1 != nullptr;
+    const bool gather_res =
+        folded && gemm_gathered_residual_ok(d, dff, d, m->enc_layers[0].pos_ffn.b2, w.Xp, m->src_word_emb, m->position_enc);
+    const EmbedFold fold{m->enc0_emb_w1, m->enc0_pos_w1, dff, folded ? w.H : nullptr, gather_res ? w.row_tok : nullptr,
+                         gather_res ? w.row_pos : nullptr};
+    const ResGather rg{w.row_tok, w.row_pos, m->src_word_emb, m->position_enc};
+    LAMP_CK(launch_embed_plan(p.seq, p.pos, m->position_enc != nullptr, p.nb, T, m->src_word_emb, m->n_src_vocab,
+                              m->position_enc, m->n_position, d, p.sp, w.granules, w.Xp, p.s, &fold));
+    for (int i = 0; i < m->n_layers_enc; ++i) {   // lamp/Layers.py:18
+        FfnParams f{w.Xp, int64_t(p.nb) * T + 1, d, dff, &m->enc_layers[i].pos_ffn, w.Xp, w.H};
+        f.rows_dev = p.sp.rows + 1; f.hidden_ready = folded && i == 0; f.rg = gather_res && i == 0 ? &rg : nullptr;
+        if (i + 1 == m->n_layers_enc) { f.scatter = &p.sp; f.nb = p.nb; f.T = T; f.y_flat = p.x; }
+        LAMP_CK(ffn_core(f, p.s));
     }
-
-    for (int64_t b0 = 0; b0 < B; b0 += mb) {
-        const int nb = int(B - b0 < mb ? B - b0 : mb);
-        const int64_t* seq = src_seq + b0 * ld_seq;
-        const int64_t* pos = src_pos ? src_pos + b0 * ld_seq : nullptr;
-        float* x = enc_output + b0 * int64_t(T) * d;  // the padded encoder output of this micro-batch
-        const int64_t Me = int64_t(nb) * T;
-        SeqPlan sp = plan_from(plan_ints, nb, T);
-        sp.granules = packed ? granules : nullptr;
-        // Packed layout: the plan rides in the first workgroups of the embedding gather's launch and hands its results to the
-        // gather through 8-byte granules (pointwise.hip: embed_plan_kernel; round 3 had it as a launch of its own -- a
-        // dependent launch costs 5-8 us on this chain however little it does -- after folding it into EVERY workgroup of
-        // the gather had measured slower, 21.9 us against 6.6 + 10.5).  Padded layout: the plan kernel on its own.
-        if (!packed) LAMP_CK(launch_seq_plan(seq, m->position_enc ? pos : nullptr, nb, T, ld_seq, packed, sp, s));
-
-        // ---- GraphEncoder.forward (lamp/Encoders.py:64-110) ----
-        lamp_mask pad_mask{LAMP_MASK_KEY_TOKENS_I64, 0, seq, ld_seq, 0, nullptr, 0};
-        const float* xk = x;  // what the decoder's K / V projections read
-        // Encoder layer 0's W1 folded into the embedding tables (lamp_model::enc0_emb_w1): the gather writes that layer's
-        // hidden rows into H beside the embedded rows, and its first GEMM is not launched.
-        // ... and the embedded rows themselves are not written either: their one reader, the residual of that layer's second
-        // GEMM, gathers them from the tables through the row maps the gather kernel leaves instead (8 bytes per row).
-        const bool folded = m->enc0_emb_w1 && m->n_layers_enc > 0;
-        int* row_tok = row_maps, *row_pos = row_maps + (size_t(mb) * T + 1);
-        // (padded layout = the dead self-attention's maps are wanted: layer 0's map reads the embedded rows, so they are written)
-        const bool gather_res = folded && packed &&
-                                gemm_gathered_residual_ok(d, dff, d, m->enc_layers[0].pos_ffn.b2, Xp, m->src_word_emb, m->position_enc);
-        const EmbedFold fold{m->enc0_emb_w1, m->enc0_pos_w1, dff, folded ? H : nullptr, gather_res ? row_tok : nullptr,
-                             gather_res ? row_pos : nullptr};
-        const ResGather rg{row_tok, row_pos, m->src_word_emb, m->position_enc};
-        if (packed) {
-            LAMP_CK(launch_embed_plan(seq, pos, m->position_enc != nullptr, nb, T, m->src_word_emb, m->n_src_vocab,
-                                      m->position_enc, m->n_position, d, sp, granules, Xp, s, &fold));
-            for (int i = 0; i < m->n_layers_enc; ++i) {
-                const bool last = i + 1 == m->n_layers_enc;
-                LAMP_CK(ffn_core(Xp, Me + 1, d, dff, m->enc_layers[i].pos_ffn, Xp, H, s, nullptr, 0, nullptr, sp.rows + 1,
-                                 last ? &sp : nullptr, nb, T, x, folded && i == 0, gather_res && i == 0 ? &rg : nullptr));  // lamp/Layers.py:18
-            }
-            xk = Xp;
-        } else {
-            if (fe) {
-                // lamp/Encoders.py:68-73: tap gather + ReLU + pair max, then conv2 as an implicit GEMM whose epilogue adds b2,
-                // applies the ReLU and adds the position row, straight into this micro-batch's encoder rows
-                LAMP_CK(launch_front_fwd(seq, nb, T_in, fe->t1, fe->n_vocab, fe->conv1_b, d, 0.f, 0u, 0, fe_x, s));
-                ConvWindowParams cp{fe_x, w2_pack, fe->conv2_b, x, nullptr, m->position_enc, pos, Me, d, ld_seq,
-                                    d, 16 * d, d, T, T + 16, 1, m->n_position};
-                LAMP_CK(launch_conv_window(cp, s));
-            } else {
-                LAMP_CK(launch_embed(seq, pos, Me, m->src_word_emb, m->n_src_vocab, m->position_enc, m->n_position, d, x, s, &fold));
-            }
-            for (int i = 0; i < m->n_layers_enc; ++i) {
-                const lamp_enc_layer& l = m->enc_layers[i];
-                if (want_enc_attn && aux->enc_self_attn[i]) {
-                    // lamp/Layers.py:16 -- only the attention map of this block is ever observable.  Maps are
-                    // (h*B, T, T) over the WHOLE batch: this micro-batch fills rows h*B + b0 + b.
-                    LAMP_CK(mha_core(x, false, x, nb, T, T, d, dk, dv, l.slf_attn, &pad_mask, nullptr,
-                                     aux->enc_self_attn[i], sc, s, false, nullptr, B, int(b0), &sp));
-                }
-                LAMP_CK(ffn_core(x, Me, d, dff, l.pos_ffn, x, H, s, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr,
-                                 folded && i == 0));  // lamp/Layers.py:18
-            }
-        }
-        const int* kv_rows = packed ? sp.rows : nullptr;
-        if (n_ahead > 0)
-            LAMP_CK(project_kv_layers(xk, Me, d, dk, dv, m->dec_layers, n_ahead, Kahead, Vahead, s, kv_rows, packed ? x : nullptr));
-
-        // ---- GraphDecoder.forward (lamp/Decoders.py:127-163) ----
-        // the label graph: bit-packed rows when the caller provides them (one dword per 32-key tile), else bytes
-        lamp_mask label_mask{LAMP_MASK_NONE, 0, nullptr, 0, 0, nullptr, 0};
-        if (m->label_mask_bits)
-            label_mask = lamp_mask{LAMP_MASK_BITS_U32, m->label_mask_flags, m->label_mask_bits, 0, (L + 31) / 32, m->label_tiles,
-                                   (L + 31) / 32 + 1, m->label_mask_allowed};
-        else if (m->label_mask)
-            label_mask = lamp_mask{LAMP_MASK_U8, 0, m->label_mask, 0, L, m->label_tiles, (L + 31) / 32 + 1};
-        const int64_t Md = int64_t(nb) * L;
-        int n_int = 0;
-        auto int_pred = [&](void) -> int {
-            if (aux && aux->int_preds && n_int < aux->n_int_preds && aux->int_preds[n_int])
-                LAMP_CK(launch_diag(Y, m->w_out, nb, L, d, aux->int_preds[n_int] + b0 * L, s));
-            ++n_int;
-            return 0;
-        };
-        for (int i = 0; i < m->n_layers_dec; ++i) {
-            const lamp_dec_layer& l = m->dec_layers[i];
-            const bool has_slf = l.slf_attn.present != 0;
-            float* Penc = (aux && aux->dec_enc_attn) ? aux->dec_enc_attn[i] : nullptr;
-            float* Pslf = (aux && aux->dec_self_attn) ? aux->dec_self_attn[i] : nullptr;
-            MhaScratch sci = sc;
-            const bool ahead = n_ahead > 0;
-            if (ahead) {
-                sci.K = Kahead[i];
-                sci.V = Vahead[i];
-            }
-            // input->label messages (lamp/Layers.py:35); layer 0's query is the label table itself (its LayerNorm
-            // kernel adds the shared residual)
-            // the feed-forward block behind each attention block rides in the attention's tail launch when the shape
-            // allows (chain.hip: same bits either way); pos_ffn2 follows the self-attention, or pos_ffn1 when there is none
-            const bool last = i + 1 == m->n_layers_dec;
-            const lamp_chain_pack* pk = m->chain_packs ? m->chain_packs + 2 * i : nullptr;
-            FfnTail t1{&l.pos_ffn1, dff, nullptr, 0, nullptr, false, pk};
-            FfnTail t2{&l.pos_ffn2, dff, last ? m->w_out : nullptr, L, last ? logits + b0 * L : nullptr, false, pk ? pk + 1 : nullptr};
-            if (i == 0)
-                LAMP_CK(mha_core(m->tgt_word_emb, true, xk, nb, L, T, d, dk, dv, l.enc_attn, &pad_mask, Y, Penc, sci, s,
-                                 ahead, m->dec0_query, B, int(b0), &sp, packed, x, &t1));
-            else
-                LAMP_CK(mha_core(Y, false, xk, nb, L, T, d, dk, dv, l.enc_attn, &pad_mask, Y, Penc, sci, s, ahead, nullptr,
-                                 B, int(b0), &sp, packed, x, &t1));
-            if (!t1.done) LAMP_CK(ffn_core(Y, Md, d, dff, l.pos_ffn1, Y, H, s));  // lamp/Layers.py:36
-            if (has_slf) {
-                LAMP_CK(int_pred());  // dec_output_int, lamp/Decoders.py:149-151
-                // label->label messages over the label graph (lamp/Layers.py:40)
-                LAMP_CK(mha_core(Y, false, Y, nb, L, L, d, dk, dv, l.slf_attn, &label_mask, Y, Pslf, sc, s, false, nullptr,
-                                 B, int(b0), nullptr, false, nullptr, &t2));
-            }
-            if (!t2.done) {
-                if (!last) {
-                    LAMP_CK(ffn_core(Y, Md, d, dff, l.pos_ffn2, Y, H, s));  // lamp/Layers.py:45
-                } else {
-                    // last layer: the read-out (lamp/Models.py:124-126) is fused into this LayerNorm
-                    LAMP_CK(ffn_core(Y, Md, d, dff, l.pos_ffn2, Y, H, s, m->w_out, L, logits + b0 * L));
-                }
-            }
-            if (!last) LAMP_CK(int_pred());                                 // all but the last (lamp/Models.py:130)
-        }
-    }
+    p.xk = w.Xp;
     return 0;
 }
 
-int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T,
-                 float* logits, float* enc_output, const lamp_aux* aux, void* workspace, size_t workspace_bytes,
-                 lamp_stream_t stream) {
-    hipStream_t s = hipStream_t(stream);
-    if (!m || !src_seq || !logits || !enc_output || !workspace) return LAMP_E_NULL;
-    if (B <= 0 || T <= 0) return LAMP_E_DIMS;
-    if (!m->src_word_emb || !m->tgt_word_emb || !m->w_out) return LAMP_E_NULL;
-    if (m->position_enc && !src_pos) return LAMP_E_NULL;
-    if (m->enc0_emb_w1 && m->position_enc && !m->enc0_pos_w1) return LAMP_E_NULL;
-    if (m->n_layers_dec <= 0) return LAMP_E_DIMS;
-    FwdPlan pl;
-    LAMP_CK(make_plan(m, T, aux && aux->enc_self_attn, &pl));
-    if ((m->d_model & 3) || (m->d_inner & 3) || (m->d_k & 3) || (m->d_v & 3)) return LAMP_E_UNSUPPORTED;
-    // One launch for every decoder layer's enc-attention K/V projection (they all read the finished encoder output)
-    // when the whole batch still fits the workspace with the extra K/V buffers and the weights fit one segment list.
-    const bool kv_ahead = 2 * m->n_layers_dec <= GEMM_MAX_SEG && m->n_layers_dec > 1 && m->n_layers_dec <= MAX_AHEAD_LAYERS &&
-                          workspace_bytes >= (pl.fixed_floats + (pl.per_sample_floats + pl.side_kv_floats) * size_t(B) +
-                                              size_t(64) * (8 + 2 * m->n_layers_dec)) * sizeof(float);
-    return forward_range(m, pl, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, s, kv_ahead);
+// lamp/Encoders.py:68-73, the one-hot front end in place of the embedding gather: tap gather + ReLU + pair max, then conv2
+// as an implicit GEMM whose epilogue adds b2, applies the ReLU and adds the position row, straight into the encoder rows.
+static int encode_onehot_front(const Pass& p) {
+    const lamp_onehot_frontend* fe = p.fe;
+    const int d = p.g.d, T = p.g.T;
+    LAMP_CK(launch_front_fwd(p.seq, p.nb, int(p.ld_seq), fe->t1, fe->n_vocab, fe->conv1_b, d, 0.f, 0u, 0, p.w.fe_x, p.s));
+    ConvWindowParams cp{p.w.fe_x, p.w.w2, fe->conv2_b, p.x, nullptr, p.m->position_enc, p.pos, int64_t(p.nb) * T, d, p.ld_seq,
+                        d, 16 * d, d, T, T + 16, 1, p.m->n_position};
+    return launch_conv_window(cp, p.s);
 }
 
-// ------------------------------------------------------------------ one-hot genomics encoder (conv.hip)
+// The encoder on the padded [nb, T, d] rows: when the dead encoder self-attention's maps are wanted (layer 0's map reads the
+// embedded rows, so they are written), with wide heads, or behind the one-hot front end.  The enc-dec attention still stops
+// at each sample's last real key.
+static int encode_padded(Pass& p) {
+    const lamp_model* m = p.m;
+    const FwdScratch& w = p.w;
+    const int d = p.g.d, dff = p.g.dff, T = p.g.T;
+    const int64_t Me = int64_t(p.nb) * T;
+    LAMP_CK(launch_seq_plan(p.seq, m->position_enc ? p.pos : nullptr, p.nb, T, p.ld_seq, false, p.sp, p.s));
+    const bool folded = m->enc0_emb_w1 && m->n_layers_enc > 0;
+    if (p.fe) {
+        LAMP_CK(encode_onehot_front(p));
+    } else {
+        const EmbedFold fold{m->enc0_emb_w1, m->enc0_pos_w1, dff, folded ? w.H : nullptr, nullptr, nullptr};
+        LAMP_CK(launch_embed(p.seq, p.pos, Me, m->src_word_emb, m->n_src_vocab, m->position_enc, m->n_position, d, p.x, p.s,
+                             &fold));
+    }
+    for (int i = 0; i < m->n_layers_enc; ++i) {
+        const lamp_enc_layer& l = m->enc_layers[i];
+        if (p.aux && p.aux->enc_self_attn && p.aux->enc_self_attn[i]) {
+            // lamp/Layers.py:16 -- only the attention map of this block is ever observable.  Maps are
+            // (h*B, T, T) over the WHOLE batch: this micro-batch fills rows h*B + b0 + b.
+            MhaCall a{p.x, p.x, p.nb, T, T, d, p.g.dk, p.g.dv, &l.slf_attn, &p.pad_mask, nullptr, p.aux->enc_self_attn[i],
+                      p.B, int(p.b0)};
+            a.keys = &p.sp;
+            LAMP_CK(mha_attend(a, w.mha, p.s));
+        }
+        FfnParams f{p.x, Me, d, dff, &l.pos_ffn, p.x, w.H};   // lamp/Layers.py:18
+        f.hidden_ready = folded && i == 0;
+        LAMP_CK(ffn_core(f, p.s));
+    }
+    p.xk = p.x;
+    return 0;
+}
+
+// K and V projections of the first n decoder layers' enc-attention from the same encoder output: ONE launch when the
+// 2n weight matrices fit the GEMM's segment list (n <= 2) -- 4 x more tiles per launch than layer by layer.
+static int project_kv_layers(const float* x, int64_t Me, int d, int dk, int dv, const lamp_dec_layer* layers, int n,
+                             float* const* K, float* const* V, hipStream_t s, const int* m_dev, const float* A_dense) {
+    const int h = layers[0].enc_attn.n_head;
+    bool uniform = 2 * n <= GEMM_MAX_SEG && h * dk == h * dv;
+    for (int i = 1; i < n && uniform; ++i) uniform = layers[i].enc_attn.n_head == h;
+    if (uniform) {
+        const float* W[GEMM_MAX_SEG];
+        float* C[GEMM_MAX_SEG];
+        for (int i = 0; i < n; ++i) {
+            if (!layers[i].enc_attn.w_ks || !layers[i].enc_attn.w_vs) return LAMP_E_NULL;
+            W[2 * i] = layers[i].enc_attn.w_ks;
+            W[2 * i + 1] = layers[i].enc_attn.w_vs;
+            C[2 * i] = K[i];
+            C[2 * i + 1] = V[i];
+        }
+        return linear(x, Me, d, d, W, 2 * n, h * dk, d, nullptr, nullptr, 0, 0, C, h * dk, s, m_dev, A_dense);
+    }
+    for (int i = 0; i < n; ++i)
+        LAMP_CK(project_qkv(layers[i].enc_attn, d, dk, dv, nullptr, 0, nullptr, x, x, Me, K[i], V[i], s, m_dev, A_dense));
+    return 0;
+}
+
+// An intermediate prediction (lamp/Decoders.py:149-151, lamp/Models.py:130) from the decoder rows, when one is requested.
+static int int_pred(Pass& p) {
+    const lamp_aux* a = p.aux;
+    const int n = p.n_int++;
+    if (!a || !a->int_preds || n >= a->n_int_preds || !a->int_preds[n]) return 0;
+    return launch_diag(p.w.Y, p.m->w_out, p.nb, p.g.L, p.g.d, a->int_preds[n] + p.b0 * p.g.L, p.s);
+}
+
+// One layer of GraphDecoder.forward (lamp/Decoders.py:127-163).  The feed-forward block behind each attention block rides in
+// the attention's tail launch when the shape allows (chain.hip: same bits either way); pos_ffn2 follows the self-attention,
+// or pos_ffn1 when there is none.
+static int decoder_layer(Pass& p, int i) {
+    const lamp_model* m = p.m;
+    const FwdDims& g = p.g;
+    const FwdScratch& w = p.w;
+    const lamp_dec_layer& l = m->dec_layers[i];
+    const int d = g.d, dff = g.dff, L = g.L;
+    const bool last = i + 1 == m->n_layers_dec;
+    const int64_t Md = int64_t(p.nb) * L;
+    float* Y = w.Y;
+    const lamp_chain_pack* pk = m->chain_packs ? m->chain_packs + 2 * i : nullptr;
+    bool ffn_ran = false;
+    FfnParams f1{Y, Md, d, dff, &l.pos_ffn1, Y, w.H}, f2{Y, Md, d, dff, &l.pos_ffn2, Y, w.H};
+    f2.n_labels = L;
+    if (last) { f2.w_out = m->w_out; f2.logits = p.logits + p.b0 * L; }   // the read-out (lamp/Models.py:124-126)
+
+    // input->label messages (lamp/Layers.py:35); layer 0's query is the label table itself (its LayerNorm kernel adds the
+    // shared residual)
+    MhaScratch sc = w.mha;
+    if (g.n_ahead) { sc.K = w.K_ahead[i]; sc.V = w.V_ahead[i]; }
+    MhaCall enc{i == 0 ? m->tgt_word_emb : Y, p.xk, p.nb, L, g.T, d, g.dk, g.dv, &l.enc_attn, &p.pad_mask, Y,
+                p.aux && p.aux->dec_enc_attn ? p.aux->dec_enc_attn[i] : nullptr, p.B, int(p.b0)};
+    enc.xq_shared = i == 0; enc.q_ready = i == 0 ? m->dec0_query : nullptr; enc.kv_ready = g.n_ahead > 0;
+    enc.keys = &p.sp; enc.keys_packed = p.packed; enc.xkv_dense = p.x;
+    LAMP_CK(mha_attend(enc, sc, p.s));
+    LAMP_CK(mha_tail(enc, sc, &f1, pk, &ffn_ran, p.s));
+    if (!ffn_ran) LAMP_CK(ffn_core(f1, p.s));   // lamp/Layers.py:36
+
+    ffn_ran = false;
+    if (l.slf_attn.present) {
+        LAMP_CK(int_pred(p));  // dec_output_int, lamp/Decoders.py:149-151
+        // label->label messages over the label graph (lamp/Layers.py:40)
+        MhaCall slf{Y, Y, p.nb, L, L, d, g.dk, g.dv, &l.slf_attn, &p.label_mask, Y,
+                    p.aux && p.aux->dec_self_attn ? p.aux->dec_self_attn[i] : nullptr, p.B, int(p.b0)};
+        LAMP_CK(mha_attend(slf, w.mha, p.s));
+        LAMP_CK(mha_tail(slf, w.mha, &f2, pk ? pk + 1 : nullptr, &ffn_ran, p.s));
+    }
+    if (!ffn_ran) LAMP_CK(ffn_core(f2, p.s));   // lamp/Layers.py:45
+    if (!last) LAMP_CK(int_pred(p));   // all but the last (lamp/Models.py:130)
+    return 0;
+}
+
 static int onehot_check(const lamp_model* m, const lamp_onehot_frontend* fe, int32_t T) {
     if (!m || !fe) return LAMP_E_NULL;
     if (!fe->t1 || !fe->conv1_b || !fe->conv2_b || (!fe->conv2_w && !fe->conv2_pack)) return LAMP_E_NULL;
@@ -1108,50 +1042,106 @@ static int onehot_check(const lamp_model* m, const lamp_onehot_frontend* fe, int
     return 0;
 }
 
-static size_t onehot_pack_floats(const lamp_model* m, const lamp_onehot_frontend* fe) {
-    return fe->conv2_pack ? 0 : size_t(16) * m->d_model * m->d_model + 64;
+// The argument checks of lamp_forward and lamp_onehot_forward (fe), all before any launch.
+static int check_forward(const lamp_model* m, const lamp_onehot_frontend* fe, const int64_t* src_seq, const int64_t* src_pos,
+                         int32_t B, int32_t T_in, const float* logits, const float* enc_output, const lamp_aux* aux,
+                         const void* workspace, FwdDims* g) {
+    if (fe) LAMP_CK(onehot_check(m, fe, T_in));
+    if (!m || !src_seq || (fe && !src_pos) || !logits || !enc_output || !workspace) return LAMP_E_NULL;
+    if (B <= 0 || T_in <= 0) return LAMP_E_DIMS;
+    if ((!fe && !m->src_word_emb) || !m->tgt_word_emb || !m->w_out) return LAMP_E_NULL;
+    if (m->position_enc && !src_pos) return LAMP_E_NULL;
+    if (m->enc0_emb_w1 && m->position_enc && !m->enc0_pos_w1) return LAMP_E_NULL;
+    if (m->n_layers_dec <= 0) return LAMP_E_DIMS;
+    LAMP_CK(fwd_dims(m, fe, T_in, aux && aux->enc_self_attn, g));
+    if ((m->d_model & 3) || (m->d_inner & 3) || (m->d_k & 3) || (m->d_v & 3)) return LAMP_E_UNSUPPORTED;
+    if (fe && ((fe->conv2_pack && !aligned16(fe->conv2_pack)) || (!fe->conv2_pack && !aligned16(fe->conv2_w)) ||
+               !aligned16(fe->t1) || !aligned16(fe->conv1_b) || !aligned16(workspace)))
+        return LAMP_E_ALIGN;
+    return 0;
 }
 
+// The whole batch in micro-batches that fit `workspace`.  With g.n_ahead, the enc-attention K/V projections of EVERY
+// decoder layer (they depend only on the encoder output) are issued as one multi-segment launch right after the encoder.
+// Samples are independent and no kernel variant depends on the batch size, so a sample's results are bit-identical for
+// every micro-batch split.
+static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const FwdDims& g, const int64_t* src_seq,
+                   const int64_t* src_pos, int32_t B, int32_t T_in, float* logits, float* enc_output, const lamp_aux* aux,
+                   void* workspace, size_t workspace_bytes, hipStream_t s) {
+    const Carver size = fwd_size(g);
+    if (workspace_bytes < size.bound(1)) return LAMP_E_WORKSPACE;
+    const int64_t mb = std::min<int64_t>(B, (workspace_bytes - size.fixed) / size.per);
+    Carver c{static_cast<char*>(workspace), size_t(mb)};
+    FwdScratch w{};
+    fwd_layout(g, c, w);
+    if (fe) {   // W2's repack comes first when the caller keeps none
+        if (g.w2_repack) LAMP_CK(launch_conv_pack(fe->conv2_w, g.d, g.d, 16, 0, w.w2, s));
+        else w.w2 = const_cast<float*>(fe->conv2_pack);
+    }
+
+    // Ragged batches.  Every micro-batch first counts its samples' extents on the device (SeqPlan).  Packed: the encoder
+    // runs on the packed non-PAD token rows and K / V are projected from them only.  Not packed (the dead encoder
+    // self-attention's maps are wanted, wide heads, or the one-hot front end): the padded layout.
+    const bool packed = !(aux && aux->enc_self_attn) && !wide_heads(g.dk, g.dv) && m->n_layers_enc > 0 && !fe;
+    // the label graph: bit-packed rows when the caller provides them (one dword per 32-key tile), else bytes
+    const int L = g.L;
+    lamp_mask label_mask{LAMP_MASK_NONE, 0, nullptr, 0, 0, nullptr, 0};
+    if (m->label_mask_bits)
+        label_mask = lamp_mask{LAMP_MASK_BITS_U32, m->label_mask_flags, m->label_mask_bits, 0, (L + 31) / 32, m->label_tiles,
+                               (L + 31) / 32 + 1, m->label_mask_allowed};
+    else if (m->label_mask)
+        label_mask = lamp_mask{LAMP_MASK_U8, 0, m->label_mask, 0, L, m->label_tiles, (L + 31) / 32 + 1};
+    for (int64_t b0 = 0; b0 < B; b0 += mb) {
+        const int nb = int(std::min<int64_t>(B - b0, mb));
+        const int64_t* seq = src_seq + b0 * T_in;
+        Pass p{m, fe, g, w, aux, logits, s, B, nb, b0, seq, src_pos ? src_pos + b0 * T_in : nullptr, T_in,
+               enc_output + b0 * int64_t(g.T) * g.d, packed, plan_from(w.plan_ints, nb, g.T),
+               lamp_mask{LAMP_MASK_KEY_TOKENS_I64, 0, seq, T_in, 0, nullptr, 0}, label_mask};
+        p.sp.granules = packed ? w.granules : nullptr;
+        LAMP_CK(packed ? encode_packed(p) : encode_padded(p));
+        if (g.n_ahead)
+            LAMP_CK(project_kv_layers(p.xk, int64_t(nb) * g.T, g.d, g.dk, g.dv, m->dec_layers, g.n_ahead, w.K_ahead,
+                                      w.V_ahead, s, packed ? p.sp.rows : nullptr, packed ? p.x : nullptr));
+        for (int i = 0; i < m->n_layers_dec; ++i) LAMP_CK(decoder_layer(p, i));
+    }
+    return 0;
+}
+
+size_t lamp_forward_workspace_bytes(const lamp_model* m, int32_t micro_batch, int32_t T, int32_t want_attn) {
+    FwdDims g;
+    if (micro_batch <= 0 || fwd_dims(m, nullptr, T, want_attn != 0, &g) != 0) return 0;
+    return fwd_size(g).bound(micro_batch);
+}
+
+int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T,
+                 float* logits, float* enc_output, const lamp_aux* aux, void* workspace, size_t workspace_bytes,
+                 lamp_stream_t stream) {
+    FwdDims g;
+    LAMP_CK(check_forward(m, nullptr, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, &g));
+    // One launch for every decoder layer's enc-attention K/V projection (they all read the finished encoder output)
+    // when the whole batch still fits the workspace with the extra K/V buffers and the weights fit one segment list.
+    const bool kv_ahead =
+        2 * m->n_layers_dec <= GEMM_MAX_SEG && m->n_layers_dec > 1 && workspace_bytes >= fwd_size(g).bound(size_t(B));
+    if (!kv_ahead) g.n_ahead = 0;
+    return forward(m, nullptr, g, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes,
+                   hipStream_t(stream));
+}
+
+// ------------------------------------------------------------------ one-hot genomics encoder (conv.hip)
 size_t lamp_onehot_forward_workspace_bytes(const lamp_model* m, const lamp_onehot_frontend* fe, int32_t micro_batch, int32_t T,
                                            int32_t want_attn) {
-    FwdPlan pl;
-    if (micro_batch <= 0 || onehot_check(m, fe, T) != 0 || make_plan(m, T / 2, want_attn, &pl) != 0) return 0;
-    const size_t fixed = pl.fixed_floats + size_t(16) * m->d_model + 64 + onehot_pack_floats(m, fe);
-    const size_t per = pl.per_sample_floats + onehot_rows(T) * m->d_model;
-    return (fixed + per * size_t(micro_batch)) * sizeof(float);
+    FwdDims g;
+    if (micro_batch <= 0 || onehot_check(m, fe, T) != 0 || fwd_dims(m, fe, T, want_attn != 0, &g) != 0) return 0;
+    return fwd_size(g).bound(micro_batch);
 }
 
+// The encoder sees T / 2 rows of each sample (T tokens, row stride T in src_seq / src_pos) in the padded layout.
 int lamp_onehot_forward(const lamp_model* m, const lamp_onehot_frontend* fe, const int64_t* src_seq, const int64_t* src_pos,
                         int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
                         size_t workspace_bytes, lamp_stream_t stream) {
-    hipStream_t s = hipStream_t(stream);
-    LAMP_CK(onehot_check(m, fe, T));
-    if (!src_seq || !src_pos || !logits || !enc_output || !workspace) return LAMP_E_NULL;
-    if (B <= 0) return LAMP_E_DIMS;
-    if (!m->tgt_word_emb || !m->w_out) return LAMP_E_NULL;
-    if (m->n_layers_dec <= 0) return LAMP_E_DIMS;
-    FwdPlan pl;
-    LAMP_CK(make_plan(m, T / 2, aux && aux->enc_self_attn, &pl));
-    if ((m->d_inner & 3) || (m->d_k & 3) || (m->d_v & 3)) return LAMP_E_UNSUPPORTED;
-    const int d = m->d_model;
-    // the front end's rows ride as per-sample floats of the plan; W2's repack (when the caller keeps none) comes first
-    pl.per_sample_floats += onehot_rows(T) * d;
-    pl.fixed_floats += size_t(16) * d + 64;
-    const size_t pack_floats = onehot_pack_floats(m, fe);
-    if (workspace_bytes < pack_floats * sizeof(float)) return LAMP_E_WORKSPACE;
-    if ((fe->conv2_pack && !aligned16(fe->conv2_pack)) || (!fe->conv2_pack && !aligned16(fe->conv2_w)) || !aligned16(fe->t1) ||
-        !aligned16(fe->conv1_b) || !aligned16(workspace))
-        return LAMP_E_ALIGN;   // before the repack below: argument errors never follow a launch
-    const float* pack = fe->conv2_pack;
-    char* ws = static_cast<char*>(workspace);
-    if (!pack) {
-        float* p = reinterpret_cast<float*>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
-        LAMP_CK(launch_conv_pack(fe->conv2_w, d, d, 16, 0, p, s));
-        pack = p;
-        ws += pack_floats * sizeof(float);
-        workspace_bytes -= pack_floats * sizeof(float);
-    }
-    return forward_range(m, pl, src_seq, src_pos, B, T, logits, enc_output, aux, ws, workspace_bytes, s, false, fe, pack);
+    FwdDims g;
+    LAMP_CK(check_forward(m, fe, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, &g));
+    return forward(m, fe, g, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, hipStream_t(stream));
 }
 
 int lamp_conv_pack(const float* w, int32_t c_out, int32_t c_in, int32_t taps, int32_t flip, float* packed,

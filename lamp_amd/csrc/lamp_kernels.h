@@ -163,14 +163,26 @@ int launch_embed_plan(const int64_t* seq, const int64_t* pos, bool plan_uses_pos
                       const float* pos_table, int n_position, int d, const SeqPlan& sp, unsigned long long* granules, float* out,
                       hipStream_t s, const EmbedFold* fold = nullptr);
 
-// y = LayerNorm(dropout(x) + residual[row % r_mod or row])   (residual nullable; r_mod 0 = per-row residual; drop nullable)
-// m_dev: live row count in device memory (M sizes the launch).  scatter (+ T, y_flat): the last LayerNorm of the packed
-// encoder -- M = nb * T flat positions, y = the packed rows (in place), y_flat = the padded [nb, T, d] encoder output.
-int launch_layernorm(const float* x, int64_t M, int d, const float* g, const float* b, float eps,
-                     const float* residual, int64_t r_mod, float* y, hipStream_t s, const float* w_out = nullptr,
-                     int n_labels = 0, float* logits = nullptr,  // w_out: fused read-out, y may then be NULL
-                     const DropoutSpec* drop = nullptr, const int* m_dev = nullptr, const SeqPlan* scatter = nullptr,
-                     int T = 0, float* y_flat = nullptr);
+// y = LayerNorm(dropout(x) + residual[row % r_mod or row])
+struct LayerNormParams {
+    const float* x;
+    int64_t M;
+    int d;
+    const float *g, *b;
+    float* y;                  // may be NULL with w_out
+    float eps = 1e-5f;
+    const float* residual;     // nullable; r_mod 0: one residual row per row
+    int64_t r_mod;
+    const float* w_out;        // nullable: fused read-out into logits [M] (n_labels = the label count)
+    int n_labels;
+    float* logits;
+    const DropoutSpec* drop;   // nullable
+    const int* m_dev;          // nullable: live row count in device memory (M sizes the launch)
+    const SeqPlan* scatter;    // nullable, with T and y_flat: the last LayerNorm of the packed encoder -- M = nb * T flat
+    int T;                     // positions, y = the packed rows (in place), y_flat = the padded [nb, T, d] encoder output
+    float* y_flat;
+};
+int launch_layernorm(const LayerNormParams& p, hipStream_t s);
 // chain.hip: the row-local tail of a decoder block -- attention output projection (+ residual) -> LayerNorm [-> FFN ->
 // LayerNorm] -- as ONE launch over 16-row panels, bit-identical to the separate launches.  chain_applies: shape limits
 // (LDS residency, tiling) and the row-count heuristic (at most one panel per CU).

@@ -568,39 +568,34 @@ int launch_embed(const int64_t* seq, const int64_t* pos, int64_t n_tok, const fl
     return int(hipGetLastError());
 }
 
-int launch_layernorm(const float* x, int64_t M, int d, const float* g, const float* b, float eps,
-                     const float* residual, int64_t r_mod, float* y, hipStream_t s, const float* w_out, int n_labels,
-                     float* logits, const DropoutSpec* drop, const int* m_dev, const SeqPlan* scatter, int T,
-                     float* y_flat) {
-    if (M <= 0 || d <= 0) return LAMP_E_DIMS;
-    if ((d & 3) || d > 4096) return LAMP_E_UNSUPPORTED;
-    if (!x || !g || !b || (!y && !w_out) || (w_out && (!logits || n_labels <= 0))) return LAMP_E_NULL;
-    if (scatter && (!y_flat || !y || T <= 0 || residual || w_out || (drop && drop->threshold > 0))) return LAMP_E_UNSUPPORTED;
-    if (m_dev && (scatter || residual || w_out || (drop && drop->threshold > 0))) return LAMP_E_UNSUPPORTED;
-    if (!aligned16(x) || (y && !aligned16(y)) || !aligned16(g) || !aligned16(b) || (residual && !aligned16(residual)) ||
-        (w_out && !aligned16(w_out)) || (y_flat && !aligned16(y_flat)))
+int launch_layernorm(const LayerNormParams& p, hipStream_t s) {
+    if (p.M <= 0 || p.d <= 0) return LAMP_E_DIMS;
+    if ((p.d & 3) || p.d > 4096) return LAMP_E_UNSUPPORTED;
+    if (!p.x || !p.g || !p.b || (!p.y && !p.w_out) || (p.w_out && (!p.logits || p.n_labels <= 0))) return LAMP_E_NULL;
+    const bool dr = p.drop && p.drop->threshold > 0;
+    if (p.scatter && (!p.y_flat || !p.y || p.T <= 0 || p.residual || p.w_out || dr)) return LAMP_E_UNSUPPORTED;
+    if (p.m_dev && (p.scatter || p.residual || p.w_out || dr)) return LAMP_E_UNSUPPORTED;
+    if (!aligned16(p.x) || (p.y && !aligned16(p.y)) || !aligned16(p.g) || !aligned16(p.b) || (p.residual && !aligned16(p.residual)) ||
+        (p.w_out && !aligned16(p.w_out)) || (p.y_flat && !aligned16(p.y_flat)))
         return LAMP_E_ALIGN;
     unsigned grid;
-    if (int e = grid4(M, &grid)) return e;
-    ProfScope prof(LAMP_K_LAYERNORM, 0.0, (scatter ? 12.0 : 8.0) * double(M) * d, s);
-    const int nv = (d / 4 + 63) / 64;
-    const bool dr = drop && drop->threshold > 0;
-    const DropoutSpec ds = dr ? *drop : DropoutSpec{0u, 1.f, 0u};
-    const SeqPlan sp = scatter ? *scatter : SeqPlan{};
+    if (int e = grid4(p.M, &grid)) return e;
+    ProfScope prof(LAMP_K_LAYERNORM, 0.0, (p.scatter ? 12.0 : 8.0) * double(p.M) * p.d, s);
+    const int nv = (p.d / 4 + 63) / 64;
+    const DropoutSpec ds = dr ? *p.drop : DropoutSpec{0u, 1.f, 0u};
+    const SeqPlan sp = p.scatter ? *p.scatter : SeqPlan{};
+#define LAMP_LN_ARGS \
+    p.x, p.M, p.d, p.g, p.b, p.eps, p.residual, p.r_mod, p.y, p.w_out, p.n_labels, p.logits, ds, p.m_dev, sp, p.T, p.y_flat
 #define LAMP_LN_LAUNCH(NV_)                                                                                          \
     do {                                                                                                              \
         if (dr)                                                                                                       \
-            hipLaunchKernelGGL((layernorm_kernel<NV_, true, 0>), dim3(grid), dim3(256), 0, s, x, M, d, g, b, eps,      \
-                               residual, r_mod, y, w_out, n_labels, logits, ds, m_dev, sp, T, y_flat);                \
-        else if (scatter)                                                                                             \
-            hipLaunchKernelGGL((layernorm_kernel<NV_, false, 2>), dim3(grid), dim3(256), 0, s, x, M, d, g, b, eps,     \
-                               residual, r_mod, y, w_out, n_labels, logits, ds, m_dev, sp, T, y_flat);                \
-        else if (m_dev)                                                                                               \
-            hipLaunchKernelGGL((layernorm_kernel<NV_, false, 1>), dim3(grid), dim3(256), 0, s, x, M, d, g, b, eps,     \
-                               residual, r_mod, y, w_out, n_labels, logits, ds, m_dev, sp, T, y_flat);                \
+            hipLaunchKernelGGL((layernorm_kernel<NV_, true, 0>), dim3(grid), dim3(256), 0, s, LAMP_LN_ARGS);           \
+        else if (p.scatter)                                                                                           \
+            hipLaunchKernelGGL((layernorm_kernel<NV_, false, 2>), dim3(grid), dim3(256), 0, s, LAMP_LN_ARGS);          \
+        else if (p.m_dev)                                                                                             \
+            hipLaunchKernelGGL((layernorm_kernel<NV_, false, 1>), dim3(grid), dim3(256), 0, s, LAMP_LN_ARGS);          \
         else                                                                                                          \
-            hipLaunchKernelGGL((layernorm_kernel<NV_, false, 0>), dim3(grid), dim3(256), 0, s, x, M, d, g, b, eps,     \
-                               residual, r_mod, y, w_out, n_labels, logits, ds, m_dev, sp, T, y_flat);                \
+            hipLaunchKernelGGL((layernorm_kernel<NV_, false, 0>), dim3(grid), dim3(256), 0, s, LAMP_LN_ARGS);          \
     } while (0)
     if (nv <= 1)
         LAMP_LN_LAUNCH(1);
@@ -613,6 +608,7 @@ int launch_layernorm(const float* x, int64_t M, int d, const float* g, const flo
     else
         LAMP_LN_LAUNCH(16);
 #undef LAMP_LN_LAUNCH
+#undef LAMP_LN_ARGS
     return int(hipGetLastError());
 }
 

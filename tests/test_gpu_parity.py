@@ -645,7 +645,7 @@ def test_chain_routes_of_the_product_library_give_every_sample_the_same_bits(dev
 
 def test_chain_over_two_halves_of_a_large_batch(dev):
     """Just past one chain launch's reach (6145-12288 decoder rows) the row-local tail runs as two chain launches over halves of
-    the batch, whole samples each (api.hip: mha_core), when both halves take 24-row panels.  Batch 136 (68 + 68 samples = 6120
+    the batch, whole samples each (api.hip: mha_tail), when both halves take 24-row panels.  Batch 136 (68 + 68 samples = 6120
     rows each), 128 (2 x 5760) and 105 (53 + 52: 4770 / 4680 rows) take that route; 100 (50 + 50: 4500 rows) and 140 keep the five
     separate launches.  All against the same samples in batches of four (360 rows: separate launches): logits, encoder rows and
     intermediate read-outs bit for bit."""

@@ -255,6 +255,47 @@ def test_argument_errors_come_back_as_status_codes_without_a_gpu():
     assert lib.lamp_forward_workspace_bytes(None, 1, 4, 0) == 0
 
 
+def dummy_model(L, d, dff, h, n_enc, n_dec, dec_self=True, onehot=False):
+    """A lamp_model struct whose pointers are dummies: enough for the *_workspace_bytes queries, which launch nothing."""
+    enc = (N.EncLayer * max(1, n_enc))(*[N.EncLayer(N.MhaWeights(16, 16, 16, 16, 16, 16, h, 1)) for _ in range(n_enc)])
+    dec = (N.DecLayer * n_dec)(*[N.DecLayer(N.MhaWeights(16, 16, 16, 16, 16, 16, h, 1), N.FfnWeights(),
+                                            N.MhaWeights(16, 16, 16, 16, 16, 16, h, 1) if dec_self else N.MhaWeights())
+                                 for _ in range(n_dec)])
+    m = N.Model(9 if onehot else 1000, 1001, L, d, dff, d // h, d // h, n_enc, n_dec, 0, 16, 16, 16, 16, 0, 0, 0, enc, dec)
+    return m, (enc, dec)
+
+
+@pytest.mark.parametrize('n_dec', [1, 2, 3])
+@pytest.mark.parametrize('shape', ['narrow', 'wide_heads', 'no_dec_self'])
+@pytest.mark.parametrize('want_attn', [0, 1])
+@pytest.mark.parametrize('frontend', ['tokens', 'onehot', 'onehot_packed_w2'])
+def test_forward_workspace_bytes_are_affine_in_the_micro_batch(n_dec, shape, want_attn, frontend):
+    """Models.py sizes the whole-batch workspace as fixed + slope * B with fixed = 2 ws(1) - ws(2): every forward
+    workspace size must be exactly affine in micro_batch, for every route the layout has (wide heads, maps, K/V ahead,
+    the one-hot front end with and without a caller-packed conv2 weight)."""
+    lib = N.lib()
+    d, h = (512, 2) if shape == 'wide_heads' else (256, 4)
+    m, keep = dummy_model(L=90, d=d, dff=2 * d, h=h, n_enc=2, n_dec=n_dec, dec_self=shape != 'no_dec_self',
+                          onehot=frontend != 'tokens')
+    T = 300
+    if frontend == 'tokens':
+        def ws(mb):
+            return lib.lamp_forward_workspace_bytes(ctypes.byref(m), mb, T, want_attn)
+    else:
+        fe = N.OnehotFrontend(16, 16, 16, 16, 16 if frontend == 'onehot_packed_w2' else None, 9, 16)
+        def ws(mb):
+            return lib.lamp_onehot_forward_workspace_bytes(ctypes.byref(m), ctypes.byref(fe), mb, T, want_attn)
+    sizes = {mb: ws(mb) for mb in (1, 2, 3, 4, 32, 1024)}
+    slope, fixed = sizes[2] - sizes[1], 2 * sizes[1] - sizes[2]
+    assert slope > 0 and fixed > 0
+    for mb, n in sizes.items():
+        assert n == fixed + slope * mb, (mb, sizes)
+    if frontend == 'onehot':   # W2's repack is a fixed region: a caller-packed W2 leaves the slope as it is
+        fe.conv2_pack = 16
+        assert ws(2) - ws(1) == slope and 2 * ws(1) - ws(2) < fixed
+    assert ws(0) == 0
+
+
 def test_dropin_package_aliases_reference_import_paths():
     import subprocess, sys
     code = ("import lamp.Constants as C, lamp.Models, lamp.Translator, lamp.Beam, lamp.Layers, lamp.SubLayers;"
