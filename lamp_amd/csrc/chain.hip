@@ -22,8 +22,7 @@
 //   H  [16][max(h d_v, d_ff)]  the attention output rows, then the FFN hidden rows (A operand of fc and W2)
 //        both row-major, unpadded, the 16-byte quad q of row r stored in slot q ^ r: the A fragments (16 rows x one quad
 //        per lane group) are then conflict-free b128 reads, and the LDS-DMA that fills them applies the XOR on its source side
-//   ring: per WAVE one slot (NSLOT; two in one of the tuning geometries) of a [WCOLS W rows][32 k] stage -- production geometry:
-//        32 rows, 4 KiB -- written by the wave itself from the registers its W stream arrives in (the image and swizzle of
+//   ring: per WAVE one slot of a [WCOLS W rows][32 k] stage -- 32 rows, 4 KiB -- written by the wave itself from the registers its W stream arrives in (the image and swizzle of
 //        gemm.hip's DMA = 2).  A wave multiplies the panel with ITS OWN output columns' weights, so the k loop has no barrier at
 //        all: the sixteen waves drift apart and cover each other's waits.  (One slot is enough: a wave's LDS queue is in order, the
 //        next stage's writes follow this stage's fragment reads without a wait.)
@@ -93,8 +92,31 @@ struct ChainParams {
     unsigned long long* trace;   // tuning build: per-workgroup stamps
 };
 
-// Geometry: WAVES waves, each owning WCOLS output columns per pass (NB = WCOLS / 16 blocks of 16 x 16), DEPTH register sets of
-// the W stream, NSLOT LDS slots per wave.  A step = one [WCOLS][32 k] stage = 8 NB MFMAs.
+// The chain's LDS as the HOST sizes it, in floats from the start of the workgroup's allocation: the one place the byte counts
+// and the fit decisions of chain_applies, rows4_groups and launch_chain come from.  A panel of `rows` rows:
+//   X [rows][d] at 0 | H [rows][hw] | then either chain_kernel's ring (geometry 0: a [WCOLS][32 k] stage per wave), or the
+//   LDS-resident operands of chain_packed_kernel / chain_rows4_kernel: g1, be1, g2, be2, b2 (d floats each), b1 (dff; 0 without
+//   the FFN) | the modulo-residual rows [rows][d] (res_mod) | the read-out rows [rows][d] (w_out).
+// res_alias / wout_late (chain_rows4_kernel, when the operand rows do not fit beside the panel -- d_ff = 1024: bibtex): the
+// residual rows live in the unused upper half of the H rows while the fc step runs (row stride hw, first column k_h), the
+// read-out rows are loaded over H after the W2 step has consumed it -- neither then adds to the size.
+// The KERNELS carve their own offsets (an attempt to take them from here changed their machine code): the `c_g1 ... c_wout`
+// lines at the top of chain_packed_kernel and chain_rows4_kernel and `ring_b` of chain_kernel place the same regions in the
+// same order and must be kept in step with this function.
+constexpr size_t CHAIN_LDS_LIMIT = size_t(160) * 1024;   // bytes a workgroup may take: what the kernels' attribute is raised to
+struct ChainLds {
+    int panel, end;   // end of X and H = start of the ring / of the operands; end of the operands
+    size_t bytes() const { return size_t(end) * 4; }                                        // the panel and its operands
+    size_t panel_bytes(int ring_floats) const { return size_t(panel + ring_floats) * 4; }   // the panel and chain_kernel's ring
+};
+static ChainLds chain_lds(int rows, int d, int hw, int dff, bool res_mod, bool w_out, int res_alias = 0, int wout_late = 0) {
+    const int panel = rows * (d + hw), vectors = 5 * d + dff, op_rows = rows * d;
+    return ChainLds{panel, panel + vectors + (res_mod && !res_alias ? op_rows : 0) + (w_out && !wout_late ? op_rows : 0)};
+}
+
+// Geometry of chain_kernel: WAVES waves, each owning WCOLS output columns per pass (NB = WCOLS / 16 blocks of 16 x 16), DEPTH
+// register sets of the W stream; NSLOT = 1: one LDS slot per wave (native weights), NSLOT = 3: the packed stream, no LDS pass
+// (the names the profiles know the two forms by).  A step = one [WCOLS][32 k] stage = 8 NB MFMAs.
 template <int WAVES, int WCOLS, int DEPTH, int NSLOT>
 struct ChainGeom {
     static constexpr int NB = WCOLS / 16;
@@ -104,10 +126,63 @@ struct ChainGeom {
     static constexpr int NLD = STAGE_FLOATS / 256;           // 1 KiB loads (= stage writes) per stage
     static constexpr int NRD = 2 * (1 + NB);                 // fragment reads per stage
     static constexpr int NOPS = NLD + NRD + NLD + 1;         // intake operations per step, one per MFMA gap
-    static constexpr bool PACKED = NSLOT >= 3;               // W arrives fragment-major (lamp_pack_weight): no LDS pass, whole lines
-    static constexpr int RING_FLOATS = PACKED ? 0 : WAVES * NSLOT * STAGE_FLOATS;   // (NSLOT == 4: chain_packed_kernel below)
+    static constexpr bool PACKED = NSLOT == 3;               // W arrives fragment-major (lamp_pack_weight): no LDS pass, whole lines
+    static constexpr int RING_FLOATS = PACKED ? 0 : WAVES * STAGE_FLOATS;
     static constexpr int RPW = ROWS / WAVES;                 // LayerNorm rows per wave
-    static_assert(NOPS <= NMF && ROWS % WAVES == 0 && (DEPTH == 2 || DEPTH == 4) && NSLOT >= 0 && NSLOT <= 4, "geometry");
+    static_assert(NOPS <= NMF && ROWS % WAVES == 0 && ((NSLOT == 1 && DEPTH == 2) || (NSLOT == 3 && DEPTH == 4)), "geometry");
+};
+
+// Tuning build: the time line of a workgroup, 24 words written by its first thread as the stamps are taken
+// (tools/bench_kernels.py chain reads them back): [0..5] wall clock at the start, behind fc, LayerNorm 1, W1, W2 and at the end;
+// [6] shader cycles from start to end (the clock the chain ran at); [7] the hardware id register; [8 + 4 s + k] shader clock
+// inside GEMM step s, relative to the start: at entry, after the prologue, after the k loop, at exit.  The product build
+// compiles every member to nothing.  (The stamps go out as global stores of the first thread, one inside every pass of a GEMM
+// step: in-order vmcnt only makes the counted waits more conservative, but wave 0 carries a few stores more than the others,
+// so timelines are comparable only between builds that stamp the same way.  Slots of steps that do not run stay as the caller
+// initialised them.)
+struct ChainTrace {
+#ifdef LAMP_TUNING
+    unsigned long long* o = nullptr;   // this workgroup's words; null: not tracing, or not the first thread
+    unsigned long long c_begin = 0;
+    int gemm_i = 0;
+    __device__ __forceinline__ void begin(unsigned long long* trace) {
+        c_begin = __builtin_readcyclecounter();
+        if (trace && threadIdx.x == 0) o = trace + size_t(blockIdx.x) * 24;
+        step(0);
+    }
+    __device__ __forceinline__ void step(int i) { if (o) o[i] = wall_clock64(); }
+    __device__ __forceinline__ void stamp(int k) { if (o) o[8 + gemm_i * 4 + k] = __builtin_readcyclecounter() - c_begin; }
+    __device__ __forceinline__ void gemm_done() { stamp(3); ++gemm_i; }
+    __device__ __forceinline__ void end() {
+        if (!o) return;
+        step(5);
+        o[6] = __builtin_readcyclecounter() - c_begin;
+        o[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
+    }
+#else
+    __device__ __forceinline__ void begin(unsigned long long*) {}
+    __device__ __forceinline__ void step(int) {}
+    __device__ __forceinline__ void stamp(int) {}
+    __device__ __forceinline__ void gemm_done() {}
+    __device__ __forceinline__ void end() {}
+#endif
+};
+
+// A fragment of k-step kt, chunk c (16x16x4 kernels): row l15, quad 8 kt + 4 c + hi, stored in slot quad ^ l15 (the XOR touches
+// the low four bits): byte offset inside the 16-quad group of the row, o = kt & 1
+__device__ __forceinline__ unsigned chain_a_off(int o, int c, int l15, int hi) { return unsigned(((o * 8 + c * 4 + hi) ^ l15) << 4); }
+
+// Position of a wave's stream through a packed matrix: stage pt = (pass, kt) of STAGE_BYTES; a wave's stages of one pass are
+// contiguous, the next pass lies pass_jump further.  The bookkeeping is a handful of scalar selects in three parts, one per
+// MFMA gap; stages past the end of the stream are requested through an empty descriptor (zeros, no memory access), which
+// keeps the wait counts the same on every step.
+template <unsigned STAGE_BYTES>
+struct ChainStream {
+    unsigned w_bytes, pass_jump, s_off;
+    int nk, total, pt = 0, p_kt = 0, p_wrap = 0;
+    __device__ __forceinline__ void adv_a() { ++pt; ++p_kt; p_wrap = p_kt == nk ? 1 : 0; }
+    __device__ __forceinline__ void adv_b() { s_off += p_wrap ? pass_jump : STAGE_BYTES; p_kt = p_wrap ? 0 : p_kt; }
+    __device__ __forceinline__ void adv_c(u32x4& rs) const { rs[2] = pt < total ? w_bytes : 0u; }
 };
 
 template <int NV, int WAVES, int WCOLS, int DEPTH, int NSLOT>
@@ -123,7 +198,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
     const unsigned lds0 = unsigned(reinterpret_cast<uintptr_t>((lds_ptr)smem));
     // byte addresses / float offsets of the three LDS regions
     const int x_floats = ROWS * p.d, h_floats = ROWS * p.hw;
-    const unsigned ring_b = lds0 + unsigned(x_floats + h_floats + wave * ((NSLOT == 3 ? 0 : NSLOT) * STAGE_FLOATS)) * 4u;
+    const unsigned ring_b = lds0 + unsigned(x_floats + h_floats + wave * (G::PACKED ? 0 : STAGE_FLOATS)) * 4u;
     auto buf_b = [&](int which) { return lds0 + (which ? unsigned(x_floats) * 4u : 0u); };
     auto buf_f = [&](int which) { return smem + (which ? x_floats : 0); };
     auto buf_w = [&](int which) { return which ? p.hw : p.d; };   // row length (floats)
@@ -147,12 +222,11 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
     wg_barrier();
 
     // ---- per-lane constants of the fragment reads ----
-    // A fragment of k-step kt, chunk c: row l15, quad 8 kt + 4 c + hi, stored in slot quad ^ l15 (the XOR touches the low four bits)
-    unsigned a_off[2][2];   // [kt & 1][c] -> byte offset inside the 16-quad group of the row
+    unsigned a_off[2][2];   // [kt & 1][c]
 #pragma unroll
     for (int o = 0; o < 2; ++o)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) a_off[o][c] = unsigned(((o * 8 + c * 4 + hi) ^ l15) << 4);
+        for (int c = 0; c < 2; ++c) a_off[o][c] = chain_a_off(o, c, l15, hi);
     // W fragment: block j (16 W rows), chunk c: stage row 16 j + l15, quad 4 c + hi in slot (quad ^ ((row >> 1) & 7))
     unsigned w_off[2];      // [c] -> byte offset inside a stage for block 0; block j adds j * 16 rows
 #pragma unroll
@@ -160,15 +234,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
     // source of a stage: load i covers W rows 8 i .. 8 i + 7, lane -> (row 8 i + lane / 8, slot lane % 8)
     const int d_row = lane >> 3, d_slot = lane & 7;
 
-#ifdef LAMP_TUNING
-    unsigned long long gt[3][4] = {};   // per GEMM step: shader-clock stamps at entry, after the prologue, after the k loop, at exit
-    int gt_i = 0;
-#define CHAIN_STAMP(k) do { if (p.trace) gt[gt_i][k] = __builtin_readcyclecounter(); } while (0)
-#else
-#define CHAIN_STAMP(k) do {} while (0)
-#endif
+    ChainTrace tr;
     auto gemm = [&](const ChainGemm& g) {
-        CHAIN_STAMP(0);
+        tr.stamp(0);
         const int nk = g.K / BK, npass = g.N / PASS_COLS;
         const int total = g.nseg * npass * nk;                // stages of this wave's W stream
         const unsigned src_b = buf_b(g.src) + unsigned(l15) * unsigned(buf_w(g.src)) * 4u;
@@ -205,12 +273,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
         }
         f32x4 R[DEPTH][NLD];
         unsigned p_so = 0;
-        // NSLOT == 0 ("W direct"): no LDS pass for W at all.  A wave is the ONLY consumer of its output columns' weights, and a
-        // lane's 16-byte load of four consecutive k of W row (col0 + 16 j + l15) IS its MFMA fragment: the stream goes global ->
-        // fragment registers, DEPTH stages deep (stage t + DEPTH - 1 is requested, into the set stage t - 1 was multiplied from,
-        // in the gaps between the MFMAs of stage t).  Per instruction the lanes touch 16 rows x 64 bytes; the other half of each
-        // 128-byte line is the next chunk's load, issued right behind it.
-        constexpr bool WDIR = NSLOT == 0 || WPK;
+        // WDIR: the packed stream goes global -> fragment registers, DEPTH stages deep (stage t + DEPTH - 1 is requested, into
+        // the set stage t - 1 was multiplied from, in the gaps between the MFMAs of stage t).
+        constexpr bool WDIR = WPK;
         constexpr int NL = 2 * NB;                 // fragment loads per stage
         f32x4 F[WDIR ? DEPTH : 1][2][NB];
         unsigned f_voff[2][NB];
@@ -218,12 +283,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
         for (int c = 0; c < 2; ++c)
 #pragma unroll
             for (int j = 0; j < NB; ++j)
-                f_voff[c][j] = WPK ? unsigned((j * nk * 2 + c) * 256 + lane * 4) * 4u : unsigned((16 * j + l15) * ldw + c * 16 + hi * 4) * 4u;
-        auto part_write = [&](f32x4 (&regs)[NLD], int set, int i) {   // registers -> LDS slot
-            const unsigned st_b = ring_b + unsigned((NSLOT == 2 ? set : 0) * STAGE_FLOATS) * 4u;
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 4))
-            lds_write16(st_b + unsigned(i * 1024 + lane * 16), regs[i]);
-#endif
+                f_voff[c][j] = unsigned((j * nk * 2 + c) * 256 + lane * 4) * 4u;
+        auto part_write = [&](f32x4 (&regs)[NLD], int i) {   // registers -> LDS slot
+            lds_write16(ring_b + unsigned(i * 1024 + lane * 16), regs[i]);
         };
         auto part_load = [&](f32x4 (&regs)[NLD], int i) {   // stage pt -> the registers just written out
             regs[i] = buffer_read16_untracked(rsW, d_voff[i], p_so);
@@ -239,18 +301,13 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
                 if (pt < total) rsW = raw_rsrc(w_base(p_seg, p_pass), w_bytes);
             }
             p_so = unsigned(p_kt) * KT_BYTES;
-#if defined(CHAIN_ABL) && (CHAIN_ABL & 1)   // timing experiment: no W traffic
-            rsW[2] = 0u;
-#else
             if (pt >= total) rsW[2] = 0u;   // past the end of the stream: empty descriptor
-#endif
         };
         f32x4 fa[2][2], fw[2][2][NB];   // [fragment set][chunk]([block])
         auto part_read = [&](int set, int kt, int r) {   // one fragment read of the stage in the slot -> fragment set
             const int c = r / (1 + NB), item = r % (1 + NB);
-            const unsigned st_b = ring_b + unsigned((NSLOT == 2 ? set : 0) * STAGE_FLOATS) * 4u;
             if (item == 0) fa[set][c] = lds_read16(src_b + unsigned(kt >> 1) * 256u + a_off[set][c]);   // kt & 1 == stage & 1
-            else fw[set][c][item - 1] = lds_read16(st_b + w_off[c] + unsigned((item - 1) * 16 * BK * 4));
+            else fw[set][c][item - 1] = lds_read16(ring_b + w_off[c] + unsigned((item - 1) * 16 * BK * 4));
         };
         if constexpr (WDIR) {
             // prologue: stages 0 .. DEPTH - 2 requested; A fragments of stage 0
@@ -276,7 +333,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
         });
         wait_vmcnt<(DEPTH - 1) * NLD>();
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) part_write(R[0], 0, i);
+        for (int i = 0; i < NLD; ++i) part_write(R[0], i);
         sgpr_guard(rsW, p_so);
 #pragma unroll
         for (int i = 0; i < NLD; ++i) part_load(R[0], i);
@@ -284,7 +341,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
         static_for<0, G::NRD>([&](auto Rr) { part_read(0, 0, decltype(Rr)::value); });
         }
 
-        CHAIN_STAMP(1);
+        tr.stamp(1);
         for (int seg = 0; seg < g.nseg; ++seg) {
             for (int pass = 0; pass < npass; ++pass) {
                 const int col0 = pass * PASS_COLS + wave * WCOLS;   // this wave's first output column of the pass
@@ -310,59 +367,17 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
                         // memory instructions then issue in the shadow of its own MFMAs.  sched_barrier pins the written order.
                         if constexpr (WDIR) {
                             constexpr int jl = (j + DEPTH - 1) % DEPTH;   // the set stage t - 1 was multiplied from
-#if defined(CHAIN_SPREAD) && CHAIN_SPREAD
-                            // The NL loads of stage t + DEPTH - 1 one every NMF / NL gaps instead of in the first NL: sixteen waves
-                            // that all reach their loads together fill the texture addresser's queue (one KiB-sized load
-                            // occupies it ~16 cycles) and sit behind it with their MFMAs unissued.
-                            constexpr int LSTEP = G::NMF / NL;
-                            // DEPTH 2: a load is consumed one step after its request, so the step-wide wait becomes one counted
-                            // wait in front of the first MFMA that reads each load: the NL - 1 - li younger loads of its stage
-                            // plus the ones this step has issued so far may stay in flight -- always NL - 1
-                            if constexpr (DEPTH > 2) wait_vmcnt<(DEPTH - 2) * NL>();
-                            wait_lgkmcnt<0>();
-                            static_for<0, G::NMF>([&](auto I) {
-                                constexpr int i = decltype(I)::value, c = i / (4 * NB), comp = (i % (4 * NB)) / NB, jb = i % NB;
-                                if constexpr (DEPTH == 2 && comp == 0) {
-                                    wait_vmcnt<NL - 1>();
-                                    __builtin_amdgcn_sched_barrier(0);
-                                }
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 2))
-                                acc[jb] = __builtin_amdgcn_mfma_f32_16x16x4f32(F[j][c][jb][comp], fa[set][c][comp], acc[jb], 0, 0, 0);
-#else
-                                asm volatile("" ::"v"(F[j][c][jb]), "v"(fa[set][c]));
-#endif
-                                __builtin_amdgcn_sched_barrier(0);
-                                if constexpr (i % LSTEP == 0) {            // stage t + DEPTH - 1 -> set jl
-                                    constexpr int li = i / LSTEP;
-                                    F[jl][li / NB][li % NB] = buffer_read16_untracked(rsW, f_voff[li / NB][li % NB], p_so);
-                                } else if constexpr (i == 1 || i == 2) {   // A fragments of stage t + 1
-                                    fa[setn][i - 1] = lds_read16(src_b + unsigned(ktn >> 1) * 256u + a_off[setn][i - 1]);
-                                } else if constexpr (i == (NL - 1) * LSTEP + 1) {
-                                    part_book();
-                                }
-                                __builtin_amdgcn_sched_barrier(0);
-                            });
-                            return;
-#endif
                             // stage t (set j) has landed when at most the DEPTH - 2 younger stages are outstanding
                             wait_vmcnt<(DEPTH - 2) * NL>();
                             wait_lgkmcnt<0>();
                             static_for<0, G::NMF>([&](auto I) {
                                 constexpr int i = decltype(I)::value, c = i / (4 * NB), comp = (i % (4 * NB)) / NB, jb = i % NB;
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 2))
                                 acc[jb] = __builtin_amdgcn_mfma_f32_16x16x4f32(F[j][c][jb][comp], fa[set][c][comp], acc[jb], 0, 0, 0);
-#else
-                                asm volatile("" ::"v"(F[j][c][jb]), "v"(fa[set][c]));
-#endif
                                 __builtin_amdgcn_sched_barrier(0);
                                 if constexpr (i < NL) {                    // stage t + DEPTH - 1 -> set jl
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 16))
                                     F[jl][i / NB][i % NB] = buffer_read16_untracked(rsW, f_voff[i / NB][i % NB], p_so);
-#endif
                                 } else if constexpr (i < NL + 2) {         // A fragments of stage t + 1
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 8))
                                     fa[setn][i - NL] = lds_read16(src_b + unsigned(ktn >> 1) * 256u + a_off[setn][i - NL]);
-#endif
                                 } else if constexpr (i == NL + 2) {
                                     part_book();
                                 }
@@ -373,15 +388,11 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
                         wait_lgkmcnt<0>();
                         static_for<0, G::NMF>([&](auto I) {
                             constexpr int i = decltype(I)::value, c = i / (4 * NB), comp = (i % (4 * NB)) / NB, jb = i % NB;
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 2))
                             acc[jb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fw[set][c][jb][comp], fa[set][c][comp], acc[jb], 0, 0, 0);
-#else
-                            asm volatile("" ::"v"(fw[set][c][jb]), "v"(fa[set][c]));
-#endif
                             __builtin_amdgcn_sched_barrier(0);
                             if constexpr (i < NLD) {                       // registers of stage t + 1 -> LDS
                                 if constexpr (i == 0) wait_vmcnt<(DEPTH - 1) * NLD>();   // the oldest stage in flight has landed
-                                part_write(R[jn], setn, i);
+                                part_write(R[jn], i);
                             } else if constexpr (i < NLD + G::NRD) {      // ... and back as fragments
                                 part_read(setn, ktn, i - NLD);
                             } else if constexpr (i < 2 * NLD + G::NRD) {  // stage t + 1 + DEPTH into the registers written out
@@ -415,7 +426,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
                 }
 #pragma unroll
                 for (int c = 0; c < 2; ++c) keep_alive(fa[0][c]);
-                CHAIN_STAMP(2);
+                tr.stamp(2);
                 // ---- epilogue of the pass: lane (row l15, hi) holds columns col0 + 16 j + 4 hi .. + 3 of its row ----
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
@@ -439,10 +450,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
         }
         wait_vmcnt<0>();   // the empty requests past the end of the stream still write their registers
         wg_barrier();      // dst complete for every wave; src free to be overwritten by the next step
-        CHAIN_STAMP(3);
-#ifdef LAMP_TUNING
-        ++gt_i;
-#endif
+        tr.gemm_done();
     };
 
     // LayerNorm of the panel in place (LDS), one wave per row as in layernorm_kernel: lane l holds the float4 columns l + 64 i.
@@ -523,46 +531,24 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_kernel(ChainParam
         wg_barrier();
     };
 
-#ifdef LAMP_TUNING
-    unsigned long long t[6] = {};
-    const unsigned long long c_begin = __builtin_readcyclecounter();
-    if (p.trace) t[0] = wall_clock64();
-#endif
+    tr.begin(p.trace);
     gemm(p.fc);
-#ifdef LAMP_TUNING
-    if (p.trace) t[1] = wall_clock64();
-#endif
+    tr.step(1);
     layernorm(p.ln1, 0);
-#ifdef LAMP_TUNING
-    if (p.trace) t[2] = wall_clock64();
-#endif
+    tr.step(2);
     if (p.has_ffn) {
         gemm(p.w1);
-#ifdef LAMP_TUNING
-        if (p.trace) t[3] = wall_clock64();
-#endif
+        tr.step(3);
         gemm(p.w2);
-#ifdef LAMP_TUNING
-        if (p.trace) t[4] = wall_clock64();
-#endif
+        tr.step(4);
         layernorm(p.ln2, 0);
     }
-#ifdef LAMP_TUNING
-    if (p.trace && tid == 0) {
-        unsigned long long* o = p.trace + size_t(blockIdx.x) * 24;
-        t[5] = wall_clock64();
-        for (int i = 0; i < 6; ++i) o[i] = t[i];
-        o[6] = __builtin_readcyclecounter() - c_begin;   // shader cycles from t[0] to t[5]: the clock the chain ran at
-        o[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        for (int gi = 0; gi < 3; ++gi)   // wave 0's shader-clock stamps inside the three GEMM steps, relative to the kernel's start
-            for (int k = 0; k < 4; ++k) o[8 + gi * 4 + k] = gt[gi][k] - c_begin;
-    }
-#endif
+    tr.end();
 }
 
 
 // =====================================================================================================================
-// Round 5: the chain on PACKED weights (lamp_pack_weight; geometries with NSLOT == 4).
+// Round 5: the chain on PACKED weights (lamp_pack_weight; geometry 12).
 //
 // What the per-wave stamps of the kernel above showed (profiles/r05_chain.txt): the four waves of a SIMD do NOT interleave their
 // MFMAs -- the issue arbiter stays with the oldest ready wave, so wave 0 runs its whole k loop nearly alone (8.9 k cycles for
@@ -650,19 +636,16 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_packed_kernel(Cha
     wait_vmcnt<0>();
     wg_barrier();
 
-    unsigned a_off[2][2];   // A fragment of k-step kt, chunk c: row l15, quad 8 kt + 4 c + hi in slot quad ^ l15: [kt & 1][c]
+    unsigned a_off[2][2];   // [kt & 1][c]
 #pragma unroll
     for (int o = 0; o < 2; ++o)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) a_off[o][c] = unsigned(((o * 8 + c * 4 + hi) ^ l15) << 4);
+        for (int c = 0; c < 2; ++c) a_off[o][c] = chain_a_off(o, c, l15, hi);
 
-#ifdef LAMP_TUNING
-    unsigned long long gt[3][4] = {};
-    int gt_i = 0;
-#endif
+    ChainTrace tr;
     // One GEMM step: dst = act(src . W^T + bias) (+ dst); bias_at: float offset of the bias vector in LDS, or -1.
     auto gemm = [&](const ChainGemm& g, int bias_at) {
-        CHAIN_STAMP(0);
+        tr.stamp(0);
         const int nk = g.K / BK, npass = g.N / PASS_COLS, total = npass * nk;
         const unsigned w_bytes = unsigned(g.N) * unsigned(g.K) * 4u;
         u32x4 rsW = raw_rsrc(g.Wp[0], w_bytes);
@@ -673,18 +656,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_packed_kernel(Cha
             for (int j = 0; j < NB; ++j) f_voff[c][j] = unsigned((j * nk * 2 + c) * 256 + lane * 4) * 4u;
         // stream position: stage pt = (pass, kt) lives at byte ((pass * PASS_COLS + wave * WCOLS) / 16 * nk + kt) * 2048 of the
         // packed matrix (+ the lane's f_voff)
-        const unsigned pass_jump = unsigned(PASS_COLS / 16 - 1) * unsigned(nk) * 2048u + 2048u;
-        unsigned s_off = unsigned(wave * (WCOLS / 16)) * unsigned(nk) * 2048u;
-        int pt = 0, p_kt = 0, p_wrap = 0;
-        auto adv_a = [&]() { ++pt; ++p_kt; p_wrap = p_kt == nk ? 1 : 0; };
-        auto adv_b = [&]() { s_off += p_wrap ? pass_jump : 2048u; p_kt = p_wrap ? 0 : p_kt; };
-        auto adv_c = [&]() {
-#if defined(CHAIN_ABL) && (CHAIN_ABL & 1)
-            rsW[2] = 0u;
-#else
-            rsW[2] = pt < total ? w_bytes : 0u;   // past the end of the stream: empty descriptor (zeros, no memory access)
-#endif
-        };
+        ChainStream<2048u> ws{w_bytes, unsigned(PASS_COLS / 16 - 1) * unsigned(nk) * 2048u + 2048u,
+                              unsigned(wave * (WCOLS / 16)) * unsigned(nk) * 2048u, nk, total};
         f32x4 F[DEPTH][2][NB], fa[2][2];
         unsigned a_cur[2][2];
         const unsigned src_b = buf_b(g.src) + unsigned(l15) * unsigned(buf_w(g.src)) * 4u;
@@ -695,18 +668,18 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_packed_kernel(Cha
         // prologue: stages 0 .. DEPTH - 2 requested, A fragments of stage 0
         static_for<0, DEPTH - 1>([&](auto J) {
             constexpr int j = decltype(J)::value;
-            sgpr_guard(rsW, s_off);
+            sgpr_guard(rsW, ws.s_off);
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int jb = 0; jb < NB; ++jb) F[j][c][jb] = buffer_read16_untracked(rsW, f_voff[c][jb], s_off);
-            adv_a(); adv_b(); adv_c();
+                for (int jb = 0; jb < NB; ++jb) F[j][c][jb] = buffer_read16_untracked(rsW, f_voff[c][jb], ws.s_off);
+            ws.adv_a(); ws.adv_b(); ws.adv_c(rsW);
         });
 #pragma unroll
         for (int c = 0; c < 2; ++c) fa[0][c] = lds_read16(a_cur[0][c]);
         wait_vmcnt<(DEPTH - 2) * NL>();
         wait_lgkmcnt<0>();
-        CHAIN_STAMP(1);
+        tr.stamp(1);
         for (int pass = 0; pass < npass; ++pass) {
             const int col0 = pass * PASS_COLS + wave * WCOLS;
             f32x4 acc[NB];
@@ -721,25 +694,17 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_packed_kernel(Cha
                     constexpr int a_imm = (j + 1 == DEPTH) ? 0 : ((j + 1) >> 1) * 256;  // next stage's quad pair, relative to a_cur
                     static_for<0, NMF>([&](auto I) {
                         constexpr int i = decltype(I)::value, c = i / (4 * NB), comp = (i % (4 * NB)) / NB, jb = i % NB;
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 2))
                         acc[jb] = __builtin_amdgcn_mfma_f32_16x16x4f32(F[j][c][jb][comp], fa[set][c][comp], acc[jb], 0, 0, 0);
-#else
-                        asm volatile("" ::"v"(F[j][c][jb]), "v"(fa[set][c]));
-#endif
                         __builtin_amdgcn_sched_barrier(0);
                         // one operation in the shadow of each MFMA (28 free issue cycles): even gaps the loads of stage
                         // t + DEPTH - 1, gaps 1 and 3 the A fragments of stage t + 1, then the bookkeeping in three parts
                         if constexpr (i % 2 == 0 && i / 2 < NL) {
                             constexpr int li = i / 2;
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 16))
-                            F[jl][li / NB][li % NB] = buffer_read16_untracked(rsW, f_voff[li / NB][li % NB], s_off);
-#endif
+                            F[jl][li / NB][li % NB] = buffer_read16_untracked(rsW, f_voff[li / NB][li % NB], ws.s_off);
                         } else if constexpr (i == 1 || i == 3) {
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 8))
                             fa[setn][i / 2] = lds_read16_off<a_imm>(a_cur[setn][i / 2]);
-#endif
                         } else if constexpr (i == 2 * NL + 1) {
-                            adv_a();
+                            ws.adv_a();
                         } else if constexpr (i == 2 * NL + 2) {
                             // the address registers of the parity whose last read of this group is behind us move on to the next group
                             if constexpr (j == DEPTH - 2) {
@@ -750,9 +715,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_packed_kernel(Cha
                                 a_cur[1][1] = src_b + a_off[1][1] + q_next;
                             }
                         } else if constexpr (i == 2 * NL + 3) {
-                            adv_b();
+                            ws.adv_b();
                         } else if constexpr (i == 2 * NL + 5) {
-                            adv_c();
+                            ws.adv_c(rsW);
                         } else if constexpr (i == NMF - 1) {
                             // the next stage's operands: its W registers (all but the DEPTH - 2 younger stages landed) and its
                             // A fragments -- waited for behind this stage's last MFMA
@@ -772,7 +737,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_packed_kernel(Cha
             });
 #pragma unroll
             for (int c = 0; c < 2; ++c) keep_alive(fa[0][c]);
-            CHAIN_STAMP(2);
+            tr.stamp(2);
             // ---- epilogue of the pass: lane (row l15, hi) holds columns col0 + 16 j + 4 hi .. + 3 of its row ----
             f32x4 bv[NB], rv[NB];
             unsigned at[NB];
@@ -801,10 +766,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_packed_kernel(Cha
         }
         wait_vmcnt<0>();   // the empty requests past the end of the stream still write their registers
         wg_barrier();      // dst complete for every wave; src free to be overwritten by the next step
-        CHAIN_STAMP(3);
-#ifdef LAMP_TUNING
-        ++gt_i;
-#endif
+        tr.gemm_done();
     };
 
     // LayerNorm of the panel in place, one wave per row as in layernorm_kernel (lane l: float4 columns l + 64 i); gain, shift,
@@ -867,41 +829,19 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void chain_packed_kernel(Cha
         wg_barrier();
     };
 
-#ifdef LAMP_TUNING
-    unsigned long long t[6] = {};
-    const unsigned long long c_begin = __builtin_readcyclecounter();
-    if (p.trace) t[0] = wall_clock64();
-#endif
+    tr.begin(p.trace);
     gemm(p.fc, -1);
-#ifdef LAMP_TUNING
-    if (p.trace) t[1] = wall_clock64();
-#endif
+    tr.step(1);
     layernorm(p.ln1, c_g1, c_be1);
-#ifdef LAMP_TUNING
-    if (p.trace) t[2] = wall_clock64();
-#endif
+    tr.step(2);
     if (p.has_ffn) {
         gemm(p.w1, c_b1);
-#ifdef LAMP_TUNING
-        if (p.trace) t[3] = wall_clock64();
-#endif
+        tr.step(3);
         gemm(p.w2, c_b2);
-#ifdef LAMP_TUNING
-        if (p.trace) t[4] = wall_clock64();
-#endif
+        tr.step(4);
         layernorm(p.ln2, c_g2, c_be2);
     }
-#ifdef LAMP_TUNING
-    if (p.trace && tid == 0) {
-        unsigned long long* o = p.trace + size_t(blockIdx.x) * 24;
-        t[5] = wall_clock64();
-        for (int i = 0; i < 6; ++i) o[i] = t[i];
-        o[6] = __builtin_readcyclecounter() - c_begin;
-        o[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        for (int gi = 0; gi < 3; ++gi)
-            for (int k = 0; k < 4; ++k) o[8 + gi * 4 + k] = gt[gi][k] - c_begin;
-    }
-#endif
+    tr.end();
 }
 
 
@@ -988,29 +928,15 @@ __global__ __launch_bounds__(512, 2) void chain_rows4_kernel(ChainParams p) {
     wait_vmcnt<0>();
     wg_barrier();
 
-#ifdef LAMP_TUNING
-    unsigned long long gt[3][4] = {};
-    int gt_i = 0;
-#endif
+    ChainTrace tr;
     auto gemm = [&](const ChainGemm& g, int bias_at) {
-        CHAIN_STAMP(0);
+        tr.stamp(0);
         const int nc = g.K / 16, npass = g.N / 512, total = npass * nc;   // stage = one chunk of 16 k x this wave's 64 columns: 4 KiB
         const unsigned w_bytes = unsigned(g.N) * unsigned(g.K) * 4u;
         u32x4 rsW = raw_rsrc(g.Wq[0], w_bytes);
         const unsigned f_voff = unsigned(lane) * 16u;   // quad q of the stage: + q KiB (instruction offset)
-        const unsigned pass_jump = 7u * unsigned(nc) * 4096u + 4096u;
-        unsigned s_off = unsigned(wave) * unsigned(nc) * 4096u;
-        int pt = 0, p_kt = 0, p_wrap = 0;
-        auto adv_a = [&]() { ++pt; ++p_kt; p_wrap = p_kt == nc ? 1 : 0; };
-        auto adv_b = [&]() { s_off += p_wrap ? pass_jump : 4096u; p_kt = p_wrap ? 0 : p_kt; };
-        auto adv_c = [&]() {
-#if defined(CHAIN_ABL) && (CHAIN_ABL & 1)
-            rsW[2] = 0u;
-#else
-            rsW[2] = pt < total ? w_bytes : 0u;
-#endif
-        };
-        auto wload = [&](f32x4& dst, auto Q) { dst = buffer_read16_untracked_off<decltype(Q)::value * 1024>(rsW, f_voff, s_off); };
+        ChainStream<4096u> ws{w_bytes, 7u * unsigned(nc) * 4096u + 4096u, unsigned(wave) * unsigned(nc) * 4096u, nc, total};
+        auto wload = [&](f32x4& dst, auto Q) { dst = buffer_read16_untracked_off<decltype(Q)::value * 1024>(rsW, f_voff, ws.s_off); };
         f32x4 F[DEPTH][4];
         float fa[2][G];
         // A operand of chunk ch, row group g: ONE register -- lane (block b = l >> 2, i = l & 3) holds X[4 g + i][16 ch + b], and the
@@ -1031,14 +957,14 @@ __global__ __launch_bounds__(512, 2) void chain_rows4_kernel(ChainParams p) {
         // prologue
         static_for<0, DEPTH - 1>([&](auto J) {
             constexpr int j = decltype(J)::value;
-            sgpr_guard(rsW, s_off);
+            sgpr_guard(rsW, ws.s_off);
             static_for<0, 4>([&](auto Q) { wload(F[j][decltype(Q)::value], Q); });
-            adv_a(); adv_b(); adv_c();
+            ws.adv_a(); ws.adv_b(); ws.adv_c(rsW);
         });
         static_for<0, G>([&](auto GG) { aread(std::integral_constant<int, 0>{}, GG, std::integral_constant<int, 0>{}); });
         wait_vmcnt<(DEPTH - 2) * 4>();
         wait_lgkmcnt<0>();
-        CHAIN_STAMP(1);
+        tr.stamp(1);
         for (int pass = 0; pass < npass; ++pass) {
             const int col = pass * 512 + wave * 64 + lane;   // this lane's output column
             f32x4 acc[G];
@@ -1052,26 +978,20 @@ __global__ __launch_bounds__(512, 2) void chain_rows4_kernel(ChainParams p) {
                     static_for<0, NMF>([&](auto I) {
                         // MFMA i of the chunk: component jj of quad q, row group gg -- k = 16 ch + 4 q + jj in the library's order
                         constexpr int i = decltype(I)::value, jj = i / (4 * G), q = (i / G) % 4, gg = i % G;
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 2))
                         acc[gg] = __builtin_amdgcn_mfma_f32_4x4x1f32(fa[set][gg], F[j][q][jj], acc[gg], 4, 4 * q + jj, 0);
-#endif
                         __builtin_amdgcn_sched_barrier(0);
                         // one operation per gap: the four loads of stage t + 3, the G reads of stage t + 1, the bookkeeping, the
                         // address registers (third step of a group: all its reads are behind us), the wait for stage t + 1
                         if constexpr (i < 8 && i % 2 == 0) {
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 16))
                             wload(F[jl][i / 2], std::integral_constant<int, i / 2>{});
-#endif
                         } else if constexpr (i < 2 * G && i % 2 == 1 && i != NMF - 1) {
-#if !(defined(CHAIN_ABL) && (CHAIN_ABL & 8))
                             aread(std::integral_constant<int, setn>{}, std::integral_constant<int, i / 2>{}, std::integral_constant<int, jn>{});
-#endif
                         } else if constexpr (i == 8) {
-                            adv_a();
+                            ws.adv_a();
                         } else if constexpr (i == 10) {
-                            adv_b();
+                            ws.adv_b();
                         } else if constexpr (i == 12) {
-                            adv_c();
+                            ws.adv_c(rsW);
                         } else if constexpr (i >= 14 && i % 2 == 0 && (i - 14) / 2 < G && j == DEPTH - 2) {
                             a_cur[(i - 14) / 2] = a_lane((i - 14) / 2) + q_next;
                         } else if constexpr (i == NMF - 1) {
@@ -1085,7 +1005,7 @@ __global__ __launch_bounds__(512, 2) void chain_rows4_kernel(ChainParams p) {
             if (pass + 1 == npass) wait_vmcnt<0>();
             static_for<0, DEPTH - 1>([&](auto J) { static_for<0, 4>([&](auto Q) { keep_alive(F[decltype(J)::value][decltype(Q)::value]); }); });
             static_for<0, G>([&](auto GG) { keep_alive(fa[0][decltype(GG)::value]); });
-            CHAIN_STAMP(2);
+            tr.stamp(2);
             // ---- epilogue of the pass: register i of acc[gg] = row 4 gg + i, this lane's column ----
             const unsigned drow = unsigned(buf_w(g.dst)) * 4u;
             float rv[G][4];
@@ -1118,10 +1038,7 @@ __global__ __launch_bounds__(512, 2) void chain_rows4_kernel(ChainParams p) {
         }
         wait_vmcnt<0>();
         wg_barrier();
-        CHAIN_STAMP(3);
-#ifdef LAMP_TUNING
-        ++gt_i;
-#endif
+        tr.gemm_done();
     };
 
     auto layernorm = [&](const ChainLN& n, int g_at, int be_at) {
@@ -1183,28 +1100,16 @@ __global__ __launch_bounds__(512, 2) void chain_rows4_kernel(ChainParams p) {
         wg_barrier();
     };
 
-#ifdef LAMP_TUNING
-    unsigned long long t[6] = {};
-    const unsigned long long c_begin = __builtin_readcyclecounter();
-    if (p.trace) t[0] = wall_clock64();
-#endif
+    tr.begin(p.trace);
     gemm(p.fc, -1);
-#ifdef LAMP_TUNING
-    if (p.trace) t[1] = wall_clock64();
-#endif
+    tr.step(1);
     layernorm(p.ln1, c_g1, c_be1);
-#ifdef LAMP_TUNING
-    if (p.trace) t[2] = wall_clock64();
-#endif
+    tr.step(2);
     if (p.has_ffn) {
         gemm(p.w1, c_b1);
-#ifdef LAMP_TUNING
-        if (p.trace) t[3] = wall_clock64();
-#endif
+        tr.step(3);
         gemm(p.w2, c_b2);
-#ifdef LAMP_TUNING
-        if (p.trace) t[4] = wall_clock64();
-#endif
+        tr.step(4);
         if (p.wout_late) {   // H is dead from here on (the W2 step ended with a barrier): the read-out rows move in
             load_mod_rows(p.ln2.w_out, p.ln2.n_labels, c_wout, d);
             wait_vmcnt<0>();
@@ -1212,17 +1117,7 @@ __global__ __launch_bounds__(512, 2) void chain_rows4_kernel(ChainParams p) {
         }
         layernorm(p.ln2, c_g2, c_be2);
     }
-#ifdef LAMP_TUNING
-    if (p.trace && tid == 0) {
-        unsigned long long* o = p.trace + size_t(blockIdx.x) * 24;
-        t[5] = wall_clock64();
-        for (int i = 0; i < 6; ++i) o[i] = t[i];
-        o[6] = __builtin_readcyclecounter() - c_begin;
-        o[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        for (int gi = 0; gi < 3; ++gi)
-            for (int k = 0; k < 4; ++k) o[8 + gi * 4 + k] = gt[gi][k] - c_begin;
-    }
-#endif
+    tr.end();
 }
 
 #ifdef LAMP_TUNING
@@ -1230,50 +1125,31 @@ static unsigned long long* g_chain_trace = nullptr;
 extern "C" __attribute__((visibility("default"))) void lamp_debug_set_chain_trace(unsigned long long* buf) { g_chain_trace = buf; }
 static int g_chain_mode = -1;   // -1 = heuristic, 0 = never, 1 = whenever the shape allows
 extern "C" __attribute__((visibility("default"))) void lamp_debug_force_chain(int mode) { g_chain_mode = mode; }
-static int g_chain_geom = -1;   // -1 = production choice (0, or the packed geometry when a weight pack is given), else an index into the table
+static int g_chain_geom = -1;   // -1 = production choice, else one of the geometry numbers below (a packed one without packs runs
+                                // geometry 0; a retired number makes launch_chain return LAMP_E_UNSUPPORTED)
 extern "C" __attribute__((visibility("default"))) void lamp_debug_chain_geometry(int idx) { g_chain_geom = idx; }
 #endif
 
-// Geometries (waves, columns per wave and pass, register sets, LDS slots per wave).  Production = the first one: SIXTEEN waves
-// (a 1024-thread workgroup, four waves per SIMD) of 32 columns each -- 57.4 us against 59.8-60.1 for eight waves x 64 columns
-// (profiles/r04_chain.txt): twice the waves to cover each other's LDS / memory waits for twice the A-fragment reads.
+// Geometries, by the numbers the profiles and the tuning hooks know them by (the retired ones: csrc/experiments/README.md):
+//    0      chain_kernel<NV, 16, 32, 2, 1>: native weights through one LDS slot per wave.  SIXTEEN waves (a 1024-thread workgroup,
+//           four waves per SIMD) of 32 columns each: twice the waves of the eight-wave shapes to cover each other's LDS / memory
+//           waits for twice the A-fragment reads (profiles/r04_chain.txt).
+//    8      chain_kernel<NV, 16, 32, 4, 3>: the packed stream, LayerNorm / bias operands from global memory -- where the
+//           operands of geometry 12 do not fit LDS beside the panel
+//   12      chain_packed_kernel<NV, 16, 32, 4>: what a caller-provided weight pack selects
+//   11      chain_packed_kernel<NV, 16, 32, 2>, tuning build only: the same kernel on two register sets of the W stream instead
+//           of four -- the one alternative depth kept forceable, so that the parity test still proves the counted waits of the
+//           k loop for a second DEPTH (it costs no kernel code: the template takes it as it stands)
+//   15-20   chain_rows4_kernel<NV, 1 .. 6>: panels of 4 to 24 rows from format-1 packs
 // (Four waves x 128 columns -- one wave per SIMD, 430 registers -- was tried and is gone: the allocator parks part of the
 // W stream's registers in AGPRs and copies them right behind the untracked loads, before the data has landed: wrong
 // results, and 92 us.  The inline-assembly loads are only safe while their destination registers stay put.)
-#define LAMP_CHAIN_GEOMS(X) X(0, 16, 32, 2, 1) X(1, 8, 32, 4, 2) X(2, 8, 32, 2, 2) X(3, 8, 32, 4, 1) X(4, 8, 64, 2, 1) \
-    X(5, 16, 32, 2, 0) X(6, 8, 64, 4, 0) X(7, 16, 32, 2, 3) X(8, 16, 32, 4, 3) X(9, 8, 64, 2, 3) X(10, 8, 64, 4, 3) \
-    X(11, 16, 32, 2, 4) X(12, 16, 32, 4, 4) X(13, 8, 64, 2, 4) X(14, 8, 64, 4, 4)
-#ifndef LAMP_CHAIN_PACKED_GEOM
-#define LAMP_CHAIN_PACKED_GEOM 12   // the geometry a caller-provided weight pack selects in the product build
-#endif
-static bool chain_geom_packed(int idx) { return idx >= 7 && idx <= 20; }   // 15-20: chain_rows4_kernel with 1-6 row groups (format-1 packs)
-static bool chain_geom_lds_operands(int idx) { return idx >= 11 && idx <= 14; }   // chain_packed_kernel: LayerNorm / bias operands in LDS
-#if LAMP_CHAIN_PACKED_GEOM == 11
-#define LAMP_CHAIN_PACKED_CASE(X) X(11, 16, 32, 2, 4)
-#elif LAMP_CHAIN_PACKED_GEOM == 12
-#define LAMP_CHAIN_PACKED_CASE(X) X(12, 16, 32, 4, 4)
-#elif LAMP_CHAIN_PACKED_GEOM == 13
-#define LAMP_CHAIN_PACKED_CASE(X) X(13, 8, 64, 2, 4)
-#else
-#define LAMP_CHAIN_PACKED_CASE(X) X(14, 8, 64, 4, 4)
-#endif
-struct ChainGeomInfo {
-    int waves, pass_cols, ring_floats;
-};
-static ChainGeomInfo chain_geom(int idx) {
-    switch (idx) {
-#define X(I, W, C, D, S) \
-    case I: return ChainGeomInfo{W, ChainGeom<W, C, D, S>::PASS_COLS, ChainGeom<W, C, D, S>::RING_FLOATS};
-        LAMP_CHAIN_GEOMS(X)
-#undef X
-        default: return ChainGeomInfo{0, 0, 0};
-    }
-}
-static int chain_geom_index(bool have_pack = false) {
+using ChainGeom0 = ChainGeom<16, 32, 2, 1>;
+static int chain_geom_index(bool have_pack) {
 #ifdef LAMP_TUNING
-    if (g_chain_geom >= 0) return (chain_geom_packed(g_chain_geom) && !have_pack) ? 0 : g_chain_geom;
+    if (g_chain_geom >= 0) return (g_chain_geom >= 8 && !have_pack) ? 0 : g_chain_geom;
 #endif
-    return have_pack ? LAMP_CHAIN_PACKED_GEOM : 0;
+    return have_pack ? 12 : 0;
 }
 
 // Shapes the fused chain takes: widths that tile the passes and the swizzles, everything resident in 160 KiB of LDS, and
@@ -1300,14 +1176,12 @@ static int rows4_groups(int64_t M, int d, int k_h, int dff, bool has_ffn, const 
     // one to three row groups up to 3072 rows; 3073-4096 rows belong to the sixteen-row panels of chain_packed_kernel (same
     // MFMA count, the 16x16x4 instruction at a higher clock); five and six row groups carry the chain to 6144 rows
     if (G < 1 || G > 6 || (G == 4 && !forced) || M > int64_t(4 * G) * 65535 || d % 512 || k_h % 64 || (has_ffn && dff % 512)) return 0;
-    const int hw = has_ffn ? (k_h > dff ? k_h : dff) : k_h;
-    const size_t base = size_t(4 * G) * size_t(d + hw) + size_t(5) * d + size_t(has_ffn ? dff : 0), rows = size_t(4 * G) * d;
-    const size_t limit = size_t(160) * 1024 / 4;
-    if (base + (res_mod ? rows : 0) + (w_out ? rows : 0) <= limit) return G;
+    const int hw = has_ffn ? (k_h > dff ? k_h : dff) : k_h, ops_dff = has_ffn ? dff : 0;
+    if (chain_lds(4 * G, d, hw, ops_dff, res_mod, w_out).bytes() <= CHAIN_LDS_LIMIT) return G;
     // The operand rows do not fit beside the panel (20-row panels with d_ff = 1024): both have a dead region of H to live in --
     // the modulo-residual rows the columns past k_h while the fc step runs, the read-out rows all of H after the W2 step.
-    const bool ra = res_mod && has_ffn && hw >= k_h + d, wl = w_out && has_ffn && size_t(4 * G) * hw >= rows;
-    if (base + (res_mod && !ra ? rows : 0) + (w_out && !wl ? rows : 0) > limit) return 0;
+    const bool ra = res_mod && has_ffn && hw >= k_h + d, wl = w_out && has_ffn && hw >= d;
+    if (chain_lds(4 * G, d, hw, ops_dff, res_mod, w_out, ra, wl).bytes() > CHAIN_LDS_LIMIT) return 0;
     if (res_alias) *res_alias = ra;
     if (wout_late) *wout_late = wl;
     return G;
@@ -1318,13 +1192,12 @@ bool chain_applies(int64_t M, int d, int k_h, int dff, bool has_ffn, const lamp_
     (void)M; (void)d; (void)k_h; (void)dff; (void)has_ffn; (void)pk; (void)res_mod; (void)w_out;
     return false;
 #else
-    const ChainGeomInfo gi = chain_geom(chain_geom_index());
     const int hw = has_ffn ? (k_h > dff ? k_h : dff) : k_h;
-    // N of every GEMM = whole passes; K of every GEMM = whole groups of DEPTH <= 4 stages (128 k) and whole 1 KiB row pieces.
-    // (The product geometries tile 512 columns per pass: d_model 512 only; the 256-wide tuning geometries take d_model 256.)
-    if (M <= 0 || gi.waves == 0 || d % gi.pass_cols || k_h % 256 || (has_ffn && (dff % gi.pass_cols || dff % 256)) || d % 256 || d > 512)
-        return false;
-    if (size_t(ROWS) * size_t(d + hw) * 4 + size_t(gi.ring_floats) * 4 > size_t(160) * 1024) return false;
+    // N of every GEMM = whole passes of 512 columns (d_model 512 only); K of every GEMM = whole groups of DEPTH <= 4 stages
+    // (128 k) and whole 1 KiB row pieces.  The panel has to fit beside the ring of geometry 0, whichever geometry runs.
+    constexpr int PASS_COLS = ChainGeom0::PASS_COLS;
+    if (M <= 0 || d % PASS_COLS || k_h % 256 || (has_ffn && (dff % PASS_COLS || dff % 256)) || d % 256 || d > 512) return false;
+    if (chain_lds(ROWS, d, hw, 0, false, false).panel_bytes(ChainGeom0::RING_FLOATS) > CHAIN_LDS_LIMIT) return false;
 #ifdef LAMP_TUNING
     if (g_chain_mode == 0) return false;
     if (g_chain_mode == 1) return true;
@@ -1346,14 +1219,11 @@ bool chain_applies(int64_t M, int d, int k_h, int dff, bool has_ffn, const lamp_
 #endif
 }
 
-template <int NV, int WAVES, int WCOLS, int DEPTH, int NSLOT>
-static int launch_chain_geom(const ChainParams& p, size_t lds, unsigned grid, hipStream_t s) {
-    void (*kern)(ChainParams);
-    if constexpr (NSLOT == 4) kern = chain_packed_kernel<NV, WAVES, WCOLS, DEPTH>;
-    else kern = chain_kernel<NV, WAVES, WCOLS, DEPTH, NSLOT>;
+template <void (*KERN)(ChainParams)>
+static int launch_chain_kernel(const ChainParams& p, unsigned block, size_t lds, unsigned grid, hipStream_t s) {
     static AttrOnce once;
-    if (int e = once.set(reinterpret_cast<const void*>(kern), 160 * 1024)) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, s, p);
+    if (int e = once.set(reinterpret_cast<const void*>(KERN), CHAIN_LDS_LIMIT)) return e;
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(block), lds, s, p);
     return int(hipGetLastError());
 }
 
@@ -1403,65 +1273,44 @@ int launch_chain(const float* A, int64_t lda, int k_h, const float* res, int64_t
     const double fl = 2.0 * double(M) * (double(d) * k_h + (ffn ? 2.0 * double(d) * dff : 0.0));
     const double by = 4.0 * (double(M) * (k_h + 2.0 * d) + double(d) * k_h + (ffn ? 2.0 * double(d) * dff : 0.0));
     const int nv = (d / 4 + 63) / 64;   // d in {256, 512}: 1 or 2 float4 per lane in the LayerNorm
+    const ChainLN& lnl = ffn ? p.ln2 : p.ln1;   // the LayerNorm that may carry the read-out
+    const bool res_mod = p.ln1.res != nullptr, read_out = lnl.w_out != nullptr;
     // Panels of 4 G rows (chain_rows4_kernel) when they spread the rows over more CUs than sixteen-row panels would
-    {
-        const ChainLN& lnl = ffn ? p.ln2 : p.ln1;
-        const int G = rows4_groups(M, d, k_h, dff, ffn != nullptr, have_pack4 ? pk : nullptr, p.ln1.res != nullptr, lnl.w_out != nullptr,
-                                   &p.res_alias, &p.wout_late);
-        const size_t lds4 = (size_t(4 * G) * size_t(p.d + p.hw) + size_t(5) * d + size_t(ffn ? dff : 0) +
-                             (p.ln1.res && !p.res_alias ? size_t(4 * G) * d : 0) + (lnl.w_out && !p.wout_late ? size_t(4 * G) * d : 0)) * 4;
-        if (G > 0) {
-            ProfScope prof(LAMP_K_GEMM, fl, by, s);
-            const unsigned grid4 = unsigned((M + 4 * G - 1) / (4 * G));
-            void (*kern)(ChainParams) = nullptr;
-            switch (nv * 10 + G) {
-                case 11: kern = chain_rows4_kernel<1, 1>; break;
-                case 12: kern = chain_rows4_kernel<1, 2>; break;
-                case 13: kern = chain_rows4_kernel<1, 3>; break;
-                case 14: kern = chain_rows4_kernel<1, 4>; break;
-                case 15: kern = chain_rows4_kernel<1, 5>; break;
-                case 16: kern = chain_rows4_kernel<1, 6>; break;
-                case 21: kern = chain_rows4_kernel<2, 1>; break;
-                case 22: kern = chain_rows4_kernel<2, 2>; break;
-                case 23: kern = chain_rows4_kernel<2, 3>; break;
-                case 24: kern = chain_rows4_kernel<2, 4>; break;
-                case 25: kern = chain_rows4_kernel<2, 5>; break;
-                case 26: kern = chain_rows4_kernel<2, 6>; break;
-                default: return LAMP_E_UNSUPPORTED;
-            }
-            static AttrOnce once[12];
-            if (int e = once[(nv - 1) * 6 + G - 1].set(reinterpret_cast<const void*>(kern), 160 * 1024)) return e;
-            hipLaunchKernelGGL(kern, dim3(grid4), dim3(512), lds4, s, p);
-            return int(hipGetLastError());
+    const int G = rows4_groups(M, d, k_h, dff, ffn != nullptr, have_pack4 ? pk : nullptr, res_mod, read_out, &p.res_alias, &p.wout_late);
+    if (G > 0) {
+        ProfScope prof(LAMP_K_GEMM, fl, by, s);
+        const size_t lds4 = chain_lds(4 * G, d, p.hw, ffn ? dff : 0, res_mod, read_out, p.res_alias, p.wout_late).bytes();
+        const unsigned grid4 = unsigned((M + 4 * G - 1) / (4 * G));
+        switch (nv * 10 + G) {
+#define X(NV, GG) \
+    case NV * 10 + GG: return launch_chain_kernel<chain_rows4_kernel<NV, GG>>(p, 512, lds4, grid4, s);
+            X(1, 1) X(1, 2) X(1, 3) X(1, 4) X(1, 5) X(1, 6) X(2, 1) X(2, 2) X(2, 3) X(2, 4) X(2, 5) X(2, 6)
+#undef X
+            default: return LAMP_E_UNSUPPORTED;
         }
+    }
 #ifdef LAMP_TUNING
-        if (g_chain_geom >= 15) return LAMP_E_UNSUPPORTED;   // a forced 4x4x1 geometry that does not fit this call
+    if (g_chain_geom >= 15) return LAMP_E_UNSUPPORTED;   // a forced 4x4x1 geometry that does not fit this call
 #endif
-    }
     int gidx = chain_geom_index(have_pack);
-    size_t lds = size_t(ROWS) * size_t(p.d + p.hw) * 4 + size_t(chain_geom(gidx).ring_floats) * 4;
-    if (chain_geom_lds_operands(gidx)) {
-        // + the LayerNorm / bias vectors, the modulo residual rows and the read-out rows (chain_packed_kernel)
-        const ChainLN& lnl = ffn ? p.ln2 : p.ln1;
-        const size_t with_ops = lds + (size_t(5) * d + size_t(ffn ? dff : 0) + (p.ln1.res ? size_t(ROWS) * d : 0) + (lnl.w_out ? size_t(ROWS) * d : 0)) * 4;
-        if (with_ops <= size_t(160) * 1024) lds = with_ops;
-        else gidx = 8;   // does not fit beside the panel: the packed stream with the operands from global memory
-    }
+    const ChainLds l = chain_lds(ROWS, d, p.hw, ffn ? dff : 0, res_mod, read_out);
+    // the operands of chain_packed_kernel do not fit beside the panel: the packed stream with the operands from global memory
+    if ((gidx == 12 || gidx == 11) && l.bytes() > CHAIN_LDS_LIMIT) gidx = 8;
     ProfScope prof(LAMP_K_GEMM, fl, by, s);
     const unsigned grid = unsigned((M + ROWS - 1) / ROWS);
-#define X(I, W, C, D, S) \
-    case I: return nv <= 1 ? launch_chain_geom<1, W, C, D, S>(p, lds, grid, s) : launch_chain_geom<2, W, C, D, S>(p, lds, grid, s);
-    switch (gidx) {
+    switch (nv * 100 + gidx) {
+        case 100: return launch_chain_kernel<chain_kernel<1, 16, 32, 2, 1>>(p, 1024, l.panel_bytes(ChainGeom0::RING_FLOATS), grid, s);
+        case 200: return launch_chain_kernel<chain_kernel<2, 16, 32, 2, 1>>(p, 1024, l.panel_bytes(ChainGeom0::RING_FLOATS), grid, s);
+        case 108: return launch_chain_kernel<chain_kernel<1, 16, 32, 4, 3>>(p, 1024, l.panel_bytes(0), grid, s);
+        case 208: return launch_chain_kernel<chain_kernel<2, 16, 32, 4, 3>>(p, 1024, l.panel_bytes(0), grid, s);
+        case 112: return launch_chain_kernel<chain_packed_kernel<1, 16, 32, 4>>(p, 1024, l.bytes(), grid, s);
+        case 212: return launch_chain_kernel<chain_packed_kernel<2, 16, 32, 4>>(p, 1024, l.bytes(), grid, s);
 #ifdef LAMP_TUNING
-        LAMP_CHAIN_GEOMS(X)
-#else
-        X(0, 16, 32, 2, 1)
-        X(8, 16, 32, 4, 3)
-        LAMP_CHAIN_PACKED_CASE(X)
+        case 111: return launch_chain_kernel<chain_packed_kernel<1, 16, 32, 2>>(p, 1024, l.bytes(), grid, s);
+        case 211: return launch_chain_kernel<chain_packed_kernel<2, 16, 32, 2>>(p, 1024, l.bytes(), grid, s);
 #endif
         default: return LAMP_E_UNSUPPORTED;
     }
-#undef X
 }
 
 // W [N, K] (leading dimension ldw) -> the order a chain kernel streams it in, one contiguous KiB per load instruction:

@@ -459,12 +459,12 @@ def test_decoder_chain_launch_is_bit_identical(dev, tuning, monkeypatch, name, B
     assert max_abs_diff(got, ref) < TOL_LOGIT
 
 
-@pytest.mark.parametrize('geometry', [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20])
+@pytest.mark.parametrize('geometry', [0, 8, 11, 12, 15, 16, 17, 18, 19, 20])
 def test_decoder_chain_every_geometry_is_bit_identical(dev, tuning, monkeypatch, geometry):
-    """Every geometry of the chain launch (tuning build) -- waves x columns per wave, register sets of the W stream, LDS slots
-    (0-4), W fragments straight from the native layout (5, 6), from the packed weights (7-10), and the round-5 kernel on packed
-    weights with the LayerNorm / bias operands in LDS (11-14), panels of 4 to 24 rows on the 4x4x1 MFMA (15-20): same k-order -- the bits of the separate
-    launches, ragged batch with a partial last panel."""
+    """Every geometry of the chain launch the product routes to, forced in the tuning build -- native weights through one LDS
+    slot per wave (0), the packed stream with the operands from global memory (8), the round-5 kernel on packed weights with
+    the LayerNorm / bias operands in LDS (12; 11: the same kernel on two register sets, tuning build only), panels of 4 to 24 rows on the 4x4x1 MFMA (15-20): same k-order -- the bits of the
+    separate launches, ragged batch with a partial last panel."""
     import ctypes
     from lamp_amd import _native as N
     cfg = list(CONFIGS['reuters_ragged'])

@@ -413,12 +413,9 @@ def chain():
     geom = lib.lamp_debug_chain_geometry
     geom.argtypes = [ctypes.c_int]
     geom.restype = None
-    GEOMS = {0: '16 waves x 32 cols, 2 reg sets, 1 slot', 1: '8 x 32, 4 sets, 2 slots', 2: '8 x 32, 2 sets, 2 slots',
-             3: '8 x 32, 4 sets, 1 slot', 4: '8 waves x 64 cols, 2 sets, 1 slot',
-             5: 'W direct: 16 x 32, 2 sets', 6: 'W direct: 8 x 64, 4 sets', 7: 'W packed: 16 x 32, 2 sets',
-             8: 'W packed: 16 x 32, 4 sets', 9: 'W packed: 8 x 64, 2 sets', 10: 'W packed: 8 x 64, 4 sets',
-             11: 'packed kernel: 16 x 32, 2 sets', 12: 'packed kernel: 16 x 32, 4 sets', 13: 'packed kernel: 8 x 64, 2 sets',
-             14: 'packed kernel: 8 x 64, 4 sets', 15: '4x4x1 kernel: 4-row panels', 16: '4x4x1 kernel: 8-row panels',
+    # the geometries the product routes to (chain.hip; the retired ones: lamp_amd/csrc/experiments/README.md)
+    GEOMS = {0: 'native weights: 16 waves x 32 cols, 2 reg sets, 1 LDS slot', 8: 'W packed: 16 x 32, 4 sets, operands from global memory',
+             11: 'packed kernel: 16 x 32, 2 sets (tuning build only)', 12: 'packed kernel: 16 x 32, 4 sets', 15: '4x4x1 kernel: 4-row panels', 16: '4x4x1 kernel: 8-row panels',
              17: '4x4x1 kernel: 12-row panels', 18: '4x4x1 kernel: 16-row panels', 19: '4x4x1 kernel: 20-row panels',
              20: '4x4x1 kernel: 24-row panels'}
     if len(sys.argv) > 4:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A -DLAMP_TUNING build of the CURRENT sources with extra flags on chosen translation units, for kernel micro-benchmarks:
-#     EXTRA="-DCHAIN_ABL=1" bash tools/build_tuning_variant.sh abl1 chain.hip     -> lamp_amd/build/liblamp_tuning_abl1.so
+#     EXTRA="-DLAMP_NO_CHAIN=1" bash tools/build_tuning_variant.sh nochain chain.hip     -> lamp_amd/build/liblamp_tuning_nochain.so
 # (the other units are taken from the regular tuning build's objects: run python -m lamp_amd.build first)
 set -eu
 NAME=$1; shift
