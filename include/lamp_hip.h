@@ -523,6 +523,37 @@ int lamp_onehot_front_bwd(const int64_t* src_seq, int32_t B, int32_t T, const la
                           float dropout_p, uint32_t seed, const float* dP, float* dz, float* partials, size_t partials_bytes,
                           lamp_stream_t stream);
 
+/* ---- the evaluation's metrics (utils/evals.py:316-407 compute_metrics) ----------------------------------------------
+ * probs / targets: fp32 [n_rows, L] row-major with row strides ld_probs / ld_targets (elements, >= L), device-resident, not
+ * modified.  Scores are probabilities: [0, 1] is the contract of these entry points; targets are 0 / 1.
+ *
+ * lamp_ranking_metrics replaces, per label column, roc_auc_score (compute_auc, utils/evals.py:283-298),
+ * precision_recall_curve + auc (compute_aupr, :228-243) and the recall at FDR <= fdr_cutoff (compute_fdr, :208-225) by ONE
+ * sort of the column.  With the column sorted by score descending, equal scores collapsed into groups k = 1..G, tp_k / fp_k
+ * the cumulative positives / negatives through group k, P = tp_G, N = fp_G, tp_0 = fp_0 = 0, q_k = tp_k / (tp_k + fp_k),
+ * q_0 = 1, r_k = tp_k / P:
+ *   auc[l]        = sum_k (fp_k - fp_{k-1}) (tp_k + tp_{k-1}) / (2 P N)   64-bit integer numerator, one fp64 division;
+ *                   NaN when P == 0 or N == 0
+ *   aupr[l]       = sum_k (r_k - r_{k-1}) (q_k + q_{k-1}) / 2             fp64, fixed summation order; NaN when P == 0
+ *   fdr_recall[l] = r_k of the lowest-scored group with 1 - q_k <= fdr_cutoff (fp64), 0 when there is none; NaN when P == 0
+ *   n_pos / n_neg = P / N (nullable)
+ * A column holding a NaN score, a score outside [0, 1] or a target other than 0 / 1 is unranked: NaN in all three, 0 in
+ * n_pos / n_neg; the other columns are unaffected.  Deterministic: the same bits from run to run and under any permutation
+ * of the rows.  n_rows < 2^31.  The workspace needs no alignment. */
+size_t lamp_ranking_metrics_workspace_bytes(int64_t n_rows, int32_t L);
+int lamp_ranking_metrics(const float* probs, int64_t ld_probs, const float* targets, int64_t ld_targets, int64_t n_rows,
+                         int32_t L, double fdr_cutoff, double* auc, double* aupr, double* fdr_recall, int64_t* n_pos,
+                         int64_t* n_neg, void* workspace, size_t workspace_bytes, lamp_stream_t stream);
+
+/* The integer counts behind the thresholded figures (compute_tp_fp_fn and the per-sample loops of utils/evals.py:347-357),
+ * with prediction = (score, NaN read as 0) >= threshold and gold = target != 0:
+ *   label_tp / label_fp / label_fn [L];  sample_tp, sample_pred (predicted labels), sample_gold (gold labels) and
+ *   sample_mismatch (labels where prediction != gold) [n_rows].  All outputs are written in full. */
+int lamp_threshold_counts(const float* probs, int64_t ld_probs, const float* targets, int64_t ld_targets, int64_t n_rows,
+                          int32_t L, float threshold, int32_t* label_tp, int32_t* label_fp, int32_t* label_fn,
+                          int32_t* sample_tp, int32_t* sample_pred, int32_t* sample_gold, int32_t* sample_mismatch,
+                          lamp_stream_t stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline) ------ */
 enum lamp_kernel_class {
     LAMP_K_EMBED = 0, LAMP_K_GEMM = 1, LAMP_K_ATTN = 2, LAMP_K_LAYERNORM = 3, LAMP_K_DIAG = 4,

@@ -166,6 +166,9 @@ PROTOTYPES = {
     'lamp_onehot_front_bwd_partials_bytes': (_sz, [_i32, _i32, _i32, _i32]),
     'lamp_onehot_front_bwd': (C.c_int, [_vp, _i32, _i32, C.POINTER(OnehotFrontend), _i32, _f, C.c_uint32, _vp, _vp, _vp,
                                         _sz, _vp]),
+    'lamp_ranking_metrics_workspace_bytes': (_sz, [_i64, _i32]),
+    'lamp_ranking_metrics': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'lamp_threshold_counts': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _f] + [_vp] * 7 + [_vp]),
     'lamp_prof_enable': (C.c_int, [_i32]),
     'lamp_prof_reset': (C.c_int, []),
     'lamp_prof_read': (C.c_int, [_i32, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double),

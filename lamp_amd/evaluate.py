@@ -156,7 +156,7 @@ def _produce(it, n_labels, batch_size, prefetch, all_targets, out_q, pin, device
 
 
 def test_epoch(model, batches, n_labels, batch_size, device, pad_last_batch=True, int_preds=False, streams=1,
-               prefetch=8, world_size=1, rank=0, group=None, timeline=None, merge_stage=False):
+               prefetch=8, world_size=1, rank=0, group=None, timeline=None, merge_stage=False, device_results=None):
     """-> (all_predictions (n, L) cpu, all_targets (n, L) cpu, bce_total float), as test.py:16-78 returns
     them.  `batches` yields ((src_seq, src_pos), adj, tgt) like lamp_amd.data.EvalBatcher.
 
@@ -177,7 +177,12 @@ def test_epoch(model, batches, n_labels, batch_size, device, pad_last_batch=True
     the issuing thread makes one call per stage instead of one per batch and the kernels see `prefetch` times the rows.
     One-hot genomics models (LAMP(onehot=True)) are the exception: their encoder length is half the padded
     length, so their results depend on it by the reference's own definition.  Each of their batches is padded to its own
-    longest sequence, as the reference's DataLoader does, and merge_stage is refused for them."""
+    longest sequence, as the reference's DataLoader does, and merge_stage is refused for them.
+
+    `device_results` (a dict, optional) receives what this rank computed, still on the device: 'probs' and 'targets', float32
+    (rows, L) matrices of this rank's rows, and 'rows' = (first, last + 1) of them in the split -- the whole split when
+    world_size == 1, so that lamp_amd.metrics.compute_metrics runs on them without the 2 n L floats going to the host and back.
+    Both are complete once the current stream has caught up; the return values are the same with and without it."""
     if merge_stage and getattr(model, 'onehot', False):
         raise ValueError("merge_stage pads batches to the stage's longest one, which changes a one-hot model's results")
     import time
@@ -198,6 +203,7 @@ def test_epoch(model, batches, n_labels, batch_size, device, pad_last_batch=True
     r_lo, r_hi = min(b_lo * batch_size, n), min(b_hi * batch_size, n)
     probs_d = torch.empty((max(r_hi - r_lo, 1), n_labels), dtype=torch.float32, device=device)
     row_loss_d = torch.empty((max(r_hi - r_lo, 1),), dtype=torch.float32, device=device)
+    targets_d = torch.empty_like(probs_d) if device_results is not None else None
     for lane in lanes:
         lane.wait_stream(main)    # the buffers (and the model's weights) are ready on every lane
     stages, stop = queue.Queue(maxsize=2), threading.Event()
@@ -206,7 +212,7 @@ def test_epoch(model, batches, n_labels, batch_size, device, pad_last_batch=True
                                 args=(it, n_labels, batch_size, max(int(prefetch), 1), all_targets, stages, pin, device, stop, bool(merge_stage), ring))
     producer.start()
     try:
-        _issue(model, stages, lanes, device, batch_size, pad_last_batch, int_preds, probs_d, row_loss_d, r_lo)
+        _issue(model, stages, lanes, device, batch_size, pad_last_batch, int_preds, probs_d, row_loss_d, r_lo, targets_d)
     finally:
         stop.set()          # an exception on this side must not leave the producer blocked on a full queue
         producer.join()
@@ -226,11 +232,14 @@ def test_epoch(model, batches, n_labels, batch_size, device, pad_last_batch=True
             real = min(lo + batch_size, r_hi) - lo
             bce_total += float(row_loss[lo - r_lo:lo - r_lo + real].sum()) / (real * n_labels)
     _return_ring(ring)    # (after the copies above: the device has consumed every upload of this epoch)
+    if device_results is not None:
+        device_results.update(probs=probs_d[:r_hi - r_lo], targets=targets_d[:r_hi - r_lo], rows=(r_lo, r_hi))
     return _combine_ranks(all_predictions, all_targets, bce_total, n, n_labels, world_size, device, group)
 
 
-def _issue(model, stages, lanes, device, batch_size, pad_last_batch, int_preds, probs_d, row_loss_d, r_lo):
-    """The issuing side: upload a stage, then forward + sigmoid / BCE per batch into the epoch's result buffers.  Buffers that
+def _issue(model, stages, lanes, device, batch_size, pad_last_batch, int_preds, probs_d, row_loss_d, r_lo, targets_d=None):
+    """The issuing side: upload a stage, then forward + sigmoid / BCE per batch into the epoch's result buffers (and, with
+    `targets_d`, the stage's gold rows into the epoch's device target matrix, device to device).  Buffers that
     cross streams are handed to the caching allocators' own bookkeeping (record_stream for device blocks; pinned blocks are
     not reused before the copies that read them have run), so nothing here waits for the device."""
     while True:
@@ -246,6 +255,9 @@ def _issue(model, stages, lanes, device, batch_size, pad_last_batch, int_preds, 
             ids_d = st.ids.to(device, non_blocking=True) if st.ids is not None else None
             gold_d = st.gold.to(device, non_blocking=True)
             uploaded = lanes[0].record_event()
+            if targets_d is not None:
+                for (_, lo, real, _, _, row, _) in st.items:
+                    targets_d[lo - r_lo:lo - r_lo + real].copy_(gold_d[row:row + real], non_blocking=True)
         st.slot.uploaded = uploaded      # the producer may refill this slot's pinned buffers once these copies have run
         if st.merged is not None:
             rows, t_max = st.merged

@@ -1,0 +1,153 @@
+"""The numbers an evaluation reports (reference: utils/evals.py:316-407 compute_metrics), computed on the MI355X.
+
+The reference calls compute_metrics after every test_epoch, on valid and on test, with all_metrics=True: per label column one
+roc_auc_score, one precision_recall_curve + auc and a second precision_recall_curve for the recall at FDR <= 0.5 -- three
+sklearn sorts of the column on one CPU thread.  Here the prediction matrix stays where evaluate.test_epoch left it: one
+key-only segmented sort of all columns and one walk over each sorted column give the three per-label figures
+(csrc/metrics.hip: lamp_ranking_metrics), one more pass over the two matrices gives the integer counts behind the five
+thresholded figures (lamp_threshold_counts).  The per-label results come back in one copy; the means / medians over L
+doubles are taken on the host.
+
+Definitions (include/lamp_hip.h spells them out): today's sklearn without the removed `reorder`
+keyword.  Scores are probabilities -- [0, 1] is the contract; a column holding a NaN score, a score outside [0, 1] or a target
+other than 0 / 1 is unranked (NaN), as the reference skipped such labels on ValueError.  A label without positives has NaN
+AUC / AUPR / FDR recall, one without negatives NaN AUC only; the aggregates run over the finite entries.
+
+There is no CPU path: without a HIP device compute_metrics raises (N.require_device).
+"""
+import numpy as np
+import torch
+
+from . import _native as N
+
+RANKING_KEYS = ('meanAUC', 'medianAUC', 'meanAUPR', 'medianAUPR', 'allAUC', 'allAUPR', 'meanFDR', 'medianFDR')
+
+
+def _matrix(t):
+    """fp32 (n, L) device view whose labels are contiguous (a row stride is passed on) -> (tensor, row stride)."""
+    if t.dim() != 2:
+        raise ValueError('expected an (n, L) matrix, got shape %s' % (tuple(t.shape),))
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.size(1) > 1 and t.stride(1) != 1 or t.stride(0) < t.size(1):
+        t = t.contiguous()
+    return t, max(int(t.stride(0)), int(t.size(1)))
+
+
+def _ranking_buffer(probs, targets, fdr_cutoff):
+    """-> float64 (5, L) device buffer: rows auc, aupr, fdr recall, then n_pos and n_neg as int64 bit patterns."""
+    N.require_device(probs, targets)
+    p, ldp = _matrix(probs)
+    t, ldt = _matrix(targets)
+    if p.shape != t.shape:
+        raise ValueError('predictions %s and targets %s differ in shape' % (tuple(p.shape), tuple(t.shape)))
+    n, L = p.shape
+    lib = N.lib()
+    nbytes = lib.lamp_ranking_metrics_workspace_bytes(n, L)
+    if nbytes == 0:
+        raise ValueError('ranking metrics: unsupported shape (%d, %d)' % (n, L))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)   # per call: gigabytes at genomics sizes, not worth keeping
+    out = torch.empty((5, L), dtype=torch.float64, device=p.device)
+    counts = out[3:].view(torch.int64)
+    N.check(lib.lamp_ranking_metrics(N.ptr(p), ldp, N.ptr(t), ldt, n, L, float(fdr_cutoff), N.ptr(out[0]), N.ptr(out[1]),
+                                     N.ptr(out[2]), N.ptr(counts[0]), N.ptr(counts[1]), N.ptr(ws), nbytes, N.stream()),
+            'lamp_ranking_metrics')
+    return out
+
+
+def ranking_metrics(probs, targets, fdr_cutoff=0.5):
+    """Per-label (auc, aupr, fdr_recall, n_pos, n_neg) of (n, L) device matrices: float64 / int64 tensors of length L on the
+    device (views of one buffer), nothing synchronised."""
+    out = _ranking_buffer(probs, targets, fdr_cutoff)
+    counts = out[3:].view(torch.int64)
+    return out[0], out[1], out[2], counts[0], counts[1]
+
+
+def _counts_buffer(probs, targets, threshold):
+    """-> int32 device buffer: the (3, L) label counts, then the (4, n) sample counts."""
+    N.require_device(probs, targets)
+    p, ldp = _matrix(probs)
+    t, ldt = _matrix(targets)
+    if p.shape != t.shape:
+        raise ValueError('predictions %s and targets %s differ in shape' % (tuple(p.shape), tuple(t.shape)))
+    n, L = p.shape
+    buf = torch.empty(3 * L + 4 * n, dtype=torch.int32, device=p.device)
+    lab, ex = buf[:3 * L].view(3, L), buf[3 * L:].view(4, n)
+    N.check(N.lib().lamp_threshold_counts(N.ptr(p), ldp, N.ptr(t), ldt, n, L, float(threshold), N.ptr(lab[0]), N.ptr(lab[1]),
+                                          N.ptr(lab[2]), N.ptr(ex[0]), N.ptr(ex[1]), N.ptr(ex[2]), N.ptr(ex[3]), N.stream()),
+            'lamp_threshold_counts')
+    return buf
+
+
+def threshold_counts(probs, targets, threshold):
+    """-> (label counts int32 (3, L): tp, fp, fn;  sample counts int32 (4, n): tp, predicted, gold, mismatches) on the device."""
+    n, L = probs.shape
+    buf = _counts_buffer(probs, targets, threshold)
+    return buf[:3 * L].view(3, L), buf[3 * L:].view(4, n)
+
+
+def thresholded_from_counts(lab, ex, n_labels):
+    """The five thresholded figures from the integer counts (numpy int arrays (3, L) and (4, n)), with the conventions of
+    run_eval.multilabel_metrics: example-based F1 over samples with a gold or a predicted label, macro-F1 over labels with
+    tp + fp + fn > 0, NaN where nothing is left."""
+    lab, ex = lab.astype(np.int64), ex.astype(np.int64)
+    tp, fp, fn = lab
+    ex_tp, ex_pred, ex_gold, ex_mis = ex
+    n = ex.shape[1]
+    nan = float('nan')
+    ex_den = ex_pred + ex_gold
+    ex_ok = ex_den > 0
+    lab_den = 2 * tp + fp + fn
+    lab_ok = lab_den > 0
+    return {
+        'ACC': float(np.count_nonzero(ex_mis == 0)) / n,
+        'HA': float(n * n_labels - int(ex_mis.sum())) / float(n * n_labels),
+        'ebF1': float(np.mean(2.0 * ex_tp[ex_ok] / ex_den[ex_ok])) if ex_ok.any() else nan,
+        'miF1': 2.0 * float(tp.sum()) / float(lab_den.sum()) if lab_den.sum() > 0 else nan,
+        'maF1': float(np.mean(2.0 * tp[lab_ok] / lab_den[lab_ok])) if lab_ok.any() else nan,
+    }
+
+
+def aggregate(values):
+    """(mean, median, variance) over the finite entries, as compute_auc / compute_aupr / compute_fdr take them over the labels
+    they did not skip (utils/evals.py:294-297); NaN when no label could be ranked."""
+    v = np.asarray(values, dtype=np.float64)
+    v = v[np.isfinite(v)]
+    if v.size == 0:
+        return float('nan'), float('nan'), float('nan')
+    return float(np.mean(v)), float(np.median(v)), float(np.var(v))
+
+
+def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapsed=0.0, all_metrics=True, device=None,
+                    fdr_cutoff=0.5):
+    """utils/evals.py:316-407 for the binary-relevance decoders: a dict with the reference's keys -- ACC, HA, ebF1, miF1, maF1,
+    meanAUC, medianAUC, meanAUPR, medianAUPR, allAUC, allAUPR, meanFDR, medianFDR, loss, time.  allAUC / allAUPR are float64
+    arrays of length L (NaN for a label that cannot be ranked); all_metrics=False gives 0 for the ranking entries, as the
+    reference does.  (n, L) tensors of probabilities in [0, 1] and 0 / 1 targets, on the CPU (uploaded once, to `device` or the
+    current HIP device) or on the device; the inputs are not modified."""
+    if not all_predictions.is_cuda:
+        if not torch.cuda.is_available():
+            N.require_device(all_predictions)      # raises: HIP device only
+        device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        all_predictions = all_predictions.to(device)
+    if not all_targets.is_cuda:
+        all_targets = all_targets.to(all_predictions.device)
+    with torch.cuda.device(all_predictions.device):
+        n, L = all_predictions.shape
+        counts_d = _counts_buffer(all_predictions, all_targets, br_threshold)
+        ranked_d = _ranking_buffer(all_predictions, all_targets, fdr_cutoff) if all_metrics else None
+        counts = counts_d.cpu().numpy()
+        out = thresholded_from_counts(counts[:3 * L].reshape(3, L), counts[3 * L:].reshape(4, n), L)
+        if all_metrics:
+            per_label = ranked_d.cpu().numpy()    # auc, aupr, fdr recall (and the two count rows): one copy
+            auc, aupr, fdr = per_label[0].copy(), per_label[1].copy(), per_label[2].copy()
+            out['meanAUC'], out['medianAUC'], _ = aggregate(auc)
+            out['meanAUPR'], out['medianAUPR'], _ = aggregate(aupr)
+            out['allAUC'], out['allAUPR'] = auc, aupr
+            out['meanFDR'], out['medianFDR'], _ = aggregate(fdr)
+        else:
+            for k in RANKING_KEYS:
+                out[k] = 0
+    out['loss'] = loss
+    out['time'] = elapsed
+    return out

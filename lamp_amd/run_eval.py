@@ -3,7 +3,7 @@ on the MI355X path.
 
     python -m lamp_amd.run_eval -data data/reuters/train_valid_test.pt -dataset reuters \
            -d_model 512 -d_inner_hid 512 -n_layers_enc 2 -n_head 4 -label_mask prior \
-           [-checkpoint results/.../model.chkpt] [-split test] [-batch_size 32] [-streams 2] [-gpus N]
+           [-checkpoint results/.../model.chkpt] [-split test] [-batch_size 32] [-streams 2] [-gpus N] [-all_metrics]
 
 -gpus N starts one process per GPU (rendezvous on 127.0.0.1; "nccl" = RCCL for the final gather only); every rank
 evaluates its contiguous share of the batches -- the forward path needs no collective (lamp_amd/sharding.py).
@@ -14,8 +14,9 @@ embedding for bibtext / delicious / bookmarks / sider :104-105, n_head2 = n_head
 built from the dataset exactly as main.py:53-88 does (vocabulary sizes, max sequence length, prior label
 adjacency from the train split).  Metrics are the thresholded multi-label basics the reference prints first
 (utils/evals.py:316-372: subset accuracy, Hamming accuracy, example-/micro-/macro-F1 at -br_threshold, with the
-reference's conventions for empty samples / labels); the sklearn-based ranking metrics are CPU post-processing
-outside this path.
+reference's conventions for empty samples / labels); with -all_metrics also the ranking metrics the reference computes with
+all_metrics=True (:208-298: mean / median AUC, AUPR and recall at FDR <= 0.5 over the labels, and the per-label arrays), on the
+device (lamp_amd/metrics.py).
 """
 import argparse
 import json
@@ -59,6 +60,9 @@ def parse(argv=None):
     ap.add_argument('-prefetch', type=int, default=8, help='batches per stage of the evaluation epoch (padded by the producer thread while the device runs the previous stage)')
     ap.add_argument('-merge_stages', action='store_true',
                     help='one forward per stage instead of one per batch (same predictions, targets and losses bit for bit)')
+    ap.add_argument('-all_metrics', action='store_true',
+                    help='also report meanAUC / medianAUC / meanAUPR / medianAUPR / meanFDR / medianFDR and the per-label allAUC / '
+                         'allAUPR (computed on the device; with -gpus N by rank 0 after the combine)')
     ap.add_argument('-seed', type=int, default=0, help='weight init seed when no checkpoint is given')
     ap.add_argument('-gpus', type=int, default=1, help='processes (one per GPU) the batches are sharded over')
     opt = ap.parse_args(argv)
@@ -175,16 +179,25 @@ def main(argv=None):
     split = data[opt.split]
     batches = D.EvalBatcher(split['src'], split['tgt'], opt.batch_size)
     torch.cuda.synchronize()
+    on_device = {} if opt.all_metrics and world == 1 else None   # one rank holds the whole split: nothing goes back up
     t0 = time.perf_counter()
     preds, targets, bce_total = test_epoch(model, batches, n_labels, opt.batch_size, device, streams=opt.streams,
                                            prefetch=opt.prefetch, merge_stage=opt.merge_stages,
-                                           world_size=world, rank=rank, group=plane.group)
+                                           world_size=world, rank=rank, group=plane.group,
+                                           device_results=on_device)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     out = {'split': opt.split, 'n_samples': batches.n_insts, 'n_labels': n_labels, 'n_batches': len(batches),
            'bce_total': bce_total, 'seconds': dt, 'samples_per_s': batches.n_insts / dt,
            'checkpoint': opt.checkpoint, 'onehot': opt.onehot, 'n_gpus': world, 'backend': plane.backend, 'backend_note': plane.note}
     out.update(multilabel_metrics(preds, targets, opt.br_threshold))
+    if opt.all_metrics and rank == 0:
+        from .metrics import RANKING_KEYS, compute_metrics
+        t1 = time.perf_counter()
+        m = (compute_metrics(on_device['probs'], on_device['targets'], bce_total, opt.br_threshold) if on_device else
+             compute_metrics(preds, targets, bce_total, opt.br_threshold, device=device))
+        out.update({k: (m[k].tolist() if hasattr(m[k], 'tolist') else m[k]) for k in RANKING_KEYS})
+        out['metrics_seconds'] = time.perf_counter() - t1
     if rank == 0:
         print(json.dumps(out), flush=True)
     plane.close()
