@@ -554,6 +554,49 @@ int lamp_threshold_counts(const float* probs, int64_t ld_probs, const float* tar
                           int32_t* sample_tp, int32_t* sample_pred, int32_t* sample_gold, int32_t* sample_mismatch,
                           lamp_stream_t stream);
 
+/* ---- the training step around the model (train.py:37-48, main.py:99) ------------------------------------------------ */
+
+/* train.py:37-44 forward AND backward in one launch: F.sigmoid(pred), F.binary_cross_entropy_with_logits(.., reduction='mean')
+ * of the final prediction and of every int_preds intermediate, the weighted sum `loss` and its `loss.backward()` down to the
+ * logits.  logits / dlogits / weights: HOST arrays of n_mats (<= 8) device matrices [n_rows, L] (contiguous) and their loss
+ * weights (1 for the final prediction = matrix 0, int_pred_weight for the others); targets [n_rows, L].
+ *   probs[r * ld_probs + i]            = sigmoid(logits[0][r, i])                          (nullable; ld_probs >= L)
+ *   dlogits[k][r, i]                   = weights[k] * (sigmoid(x) - t) / (n_rows * L)      (array and entries nullable)
+ *   row_loss[k * ld_row_loss + r]      = sum_i max(x,0) - x*t + log1p(exp(-|x|)),  x = logits[k][r, i], t = targets[r, i]
+ * The 'mean' of matrix k is sum_r row_loss[k, r] / (n_rows * L), taken by the caller.  Every sum runs in an order fixed by L
+ * alone (no atomics): a row's probabilities and loss sums do not depend on the batch it is in, and neither do its gradients
+ * up to the 1 / (n_rows * L) factor.  A NaN logit gives NaN in its own row only. */
+int lamp_bce_logits_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
+                          const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
+                          int64_t ld_row_loss, lamp_stream_t stream);
+
+/* lamp_embed_bwd with a fixed summation order, for a training epoch that must be reproducible bit for bit (the embedding
+ * gradient feeds optimizer.step(), train.py:47-48): d_emb[src_seq[t], :] += dout[t, :], the rows of a repeated token added in
+ * ascending position order by ONE writer per table row -- no atomics.  Same arguments and contract as lamp_embed_bwd; the
+ * two differ in the last bits where a token repeats.  Every wave scans the token ids before its own position for an earlier
+ * occurrence (n_tokens^2 / 128 id loads per launch on average): meant for a batch's tokens, not for a corpus. */
+int lamp_embed_bwd_ordered(const int64_t* src_seq, int64_t n_tokens, const float* dout, int32_t d_model, int32_t n_vocab,
+                           int64_t pad_idx, float* d_emb, lamp_stream_t stream);
+
+/* optimizer.step() (train.py:48) for every parameter in one launch per 72 table entries.  entries: HOST array of n device
+ * tensors (fp32, 4-byte aligned, any numel >= 0; 16-byte accesses when all of an entry's pointers allow it).
+ *   LAMP_OPTIM_ADAM: torch.optim.Adam as main.py:99 builds it (no weight decay, no amsgrad), `step` = this update's 1-based
+ *     count:  m = m + (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g g;
+ *             w = w - lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ *   LAMP_OPTIM_SGD:  w = w - lr * g  (exp_avg / exp_avg_sq unused, may be NULL)
+ * The hyper-parameters are doubles: 1 - beta and the bias corrections are taken on the host in double, as torch does,
+ * and rounded to fp32 once.  Elementwise: bit-identical from run to run. */
+enum lamp_optim_kind { LAMP_OPTIM_ADAM = 0, LAMP_OPTIM_SGD = 1 };
+typedef struct lamp_optim_entry {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+} lamp_optim_entry;
+int lamp_optim_step(const lamp_optim_entry* entries, int32_t n, int32_t kind, int64_t step, double lr, double beta1,
+                    double beta2, double eps, lamp_stream_t stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline) ------ */
 enum lamp_kernel_class {
     LAMP_K_EMBED = 0, LAMP_K_GEMM = 1, LAMP_K_ATTN = 2, LAMP_K_LAYERNORM = 3, LAMP_K_DIAG = 4,

@@ -107,6 +107,14 @@ class OnehotFrontend(C.Structure):  # include/lamp_hip.h: lamp_onehot_frontend
                 ('n_vocab', C.c_int32), ('taps', C.c_int32)]
 
 
+class OptimEntry(C.Structure):  # include/lamp_hip.h: lamp_optim_entry
+    _fields_ = [('param', _vp), ('grad', _vp), ('exp_avg', _vp), ('exp_avg_sq', _vp), ('numel', C.c_int64)]
+
+
+LAMP_OPTIM_ADAM, LAMP_OPTIM_SGD = 0, 1
+BCE_TRAIN_MAX_MATS = 8
+
+
 # name -> (restype, argtypes); every function include/lamp_hip.h declares
 _i32, _i64, _sz, _f = C.c_int32, C.c_int64, C.c_size_t, C.c_float
 PROTOTYPES = {
@@ -169,6 +177,9 @@ PROTOTYPES = {
     'lamp_ranking_metrics_workspace_bytes': (_sz, [_i64, _i32]),
     'lamp_ranking_metrics': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'lamp_threshold_counts': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _f] + [_vp] * 7 + [_vp]),
+    'lamp_embed_bwd_ordered': (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i64, _vp, _vp]),
+    'lamp_bce_logits_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
+    'lamp_optim_step': (C.c_int, [C.POINTER(OptimEntry), _i32, _i32, _i64] + [C.c_double] * 4 + [_vp]),
     'lamp_prof_enable': (C.c_int, [_i32]),
     'lamp_prof_reset': (C.c_int, []),
     'lamp_prof_read': (C.c_int, [_i32, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -831,14 +842,15 @@ def diag_logits_bwd(y, w_out, dlogits):
     return dy, dw
 
 
-def embed_bwd(src_seq, dout, n_vocab, pad_idx=-1):
+def embed_bwd(src_seq, dout, n_vocab, pad_idx=-1, ordered=False):
+    """ordered: lamp_embed_bwd_ordered -- repeated tokens summed in position order by one writer per row (no atomics)."""
     require_device(src_seq, dout)
     g = f32c(dout)
     d = g.size(-1)
     seq = src_seq.contiguous()
     d_emb = torch.zeros(n_vocab, d, dtype=torch.float32, device=g.device)
-    check(lib().lamp_embed_bwd(ptr(seq), seq.numel(), ptr(g), d, n_vocab, int(pad_idx), ptr(d_emb), stream()),
-          'lamp_embed_bwd')
+    fn, name = (lib().lamp_embed_bwd_ordered, 'lamp_embed_bwd_ordered') if ordered else (lib().lamp_embed_bwd, 'lamp_embed_bwd')
+    check(fn(ptr(seq), seq.numel(), ptr(g), d, n_vocab, int(pad_idx), ptr(d_emb), stream()), name)
     return d_emb
 
 
@@ -882,6 +894,56 @@ def sigmoid_bce(logits, targets=None, probs_out=None, row_loss_out=None):
     check(lib().lamp_sigmoid_bce_fwd(ptr(x), ptr(z), B, L, ptr(probs), ptr(row_loss), stream()),
           'lamp_sigmoid_bce_fwd')
     return probs, row_loss
+
+
+def bce_logits_train(logits, weights, targets, probs_out=None, row_loss_out=None, want_grads=True, want_probs=True):
+    """lamp_bce_logits_train (train.py:37-44 forward and backward in one launch).  logits: the final prediction followed by
+    the int_preds intermediates, each (B, L); weights: their loss weights; targets (B, L).
+    -> (probs (B, L) = sigmoid(logits[0]) or None, [dlogits_k] or None, row_loss (len(logits), B)).
+    probs_out: a (B, L) fp32 view with unit column stride (its row stride may be wider: a block of rows of an epoch-wide
+    matrix); row_loss_out: a (len(logits), B) fp32 view with unit column stride."""
+    n = len(logits)
+    if not 1 <= n <= BCE_TRAIN_MAX_MATS or len(weights) != n:
+        raise ValueError('bce_logits_train takes 1..%d logit matrices and one weight each' % BCE_TRAIN_MAX_MATS)
+    require_device(targets, probs_out, row_loss_out, *logits)
+    B, L = logits[0].shape
+    xs = [f32c(x.detach()) for x in logits]
+    z = f32c(targets)
+    if any(tuple(x.shape) != (B, L) for x in xs) or tuple(z.shape) != (B, L):
+        raise ValueError('bce_logits_train: every logit matrix and the targets must be (%d, %d)' % (B, L))
+    dev = xs[0].device
+    probs = probs_out if probs_out is not None else torch.empty((B, L), dtype=torch.float32, device=dev) if want_probs else None
+    row_loss = row_loss_out if row_loss_out is not None else torch.empty((n, B), dtype=torch.float32, device=dev)
+    if probs is not None and (tuple(probs.shape) != (B, L) or probs.dtype != torch.float32 or (L > 1 and probs.stride(1) != 1) or
+            (B > 1 and probs.stride(0) < L)):
+        raise ValueError('bce_logits_train: probs_out must be a (%d, %d) fp32 view with unit column stride' % (B, L))
+    if (tuple(row_loss.shape) != (n, B) or row_loss.dtype != torch.float32 or (B > 1 and row_loss.stride(1) != 1) or
+            (n > 1 and row_loss.stride(0) < B)):
+        raise ValueError('bce_logits_train: row_loss_out must be a (%d, %d) fp32 view with unit column stride' % (n, B))
+    grads = [torch.empty_like(x) for x in xs] if want_grads else None
+    xp = (_vp * n)(*[x.data_ptr() for x in xs])
+    gp = (_vp * n)(*[g.data_ptr() for g in grads]) if want_grads else None
+    wp = (C.c_float * n)(*[float(w) for w in weights])
+    check(lib().lamp_bce_logits_train(xp, wp, gp, n, z.data_ptr(), B, L, ptr(probs), probs.stride(0) if probs is not None and B > 1 else L,
+                                      row_loss.data_ptr(), row_loss.stride(0) if n > 1 else B, stream()),
+          'lamp_bce_logits_train')
+    return probs, grads, row_loss
+
+
+def optim_step(entries, kind, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+    """lamp_optim_step over [(param, grad, exp_avg, exp_avg_sq)] (the last two None for SGD): contiguous fp32 device tensors
+    of one device, updated in place.  The table is rebuilt from the live pointers on every call."""
+    n = len(entries)
+    if n == 0:
+        return
+    arr = (OptimEntry * n)()
+    for i, (p, g, m, v) in enumerate(entries):
+        e = arr[i]
+        e.param, e.grad, e.numel = p.data_ptr(), g.data_ptr(), p.numel()
+        if m is not None:
+            e.exp_avg, e.exp_avg_sq = m.data_ptr(), v.data_ptr()
+    check(lib().lamp_optim_step(arr, n, int(kind), int(step), float(lr), float(beta1), float(beta2), float(eps), stream()),
+          'lamp_optim_step')
 
 
 # ------------------------------------------------------------------ profiling

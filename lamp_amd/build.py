@@ -30,7 +30,7 @@ LIB = os.path.join(HERE, 'liblamp_hip.so')
 LIB_TUNING = os.path.join(HERE, 'liblamp_hip_tuning.so')
 SOURCES = ['gemm.hip', 'gemm_gen.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_general.hip', 'attention_sparse.hip',
            'pointwise.hip',
-           'backward.hip', 'chain.hip', 'conv.hip', 'metrics.hip', 'api.hip']
+           'backward.hip', 'chain.hip', 'conv.hip', 'metrics.hip', 'train_step.hip', 'api.hip']
 TUNING_SOURCES = {'gemm.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_sparse.hip', 'chain.hip'}
 TUNING_ONLY = ['experiments/slab.hip']   # experiments kept bit-identical and benchmarkable, never part of the product library
 HEADERS = [os.path.join(CSRC, 'lamp_kernels.h'), os.path.join(CSRC, 'lamp_asm.h'), os.path.join(HERE, '..', 'include', 'lamp_hip.h')]
@@ -123,6 +123,7 @@ def built_toolchain():
 
 
 GUARD_KERNELS = ('chain', 'slab', 'attn_tile')   # kernels with inline-assembly loads: registers must stay where the loads land
+LEAN_UNITS = ('train_step.hip',)   # units whose kernels must use neither scratch nor AGPRs (checked at every build)
 
 
 def _resource_problems(source, tuning):
@@ -209,6 +210,10 @@ def build(force=False, verbose=False):
     tobjs = [os.path.join(OBJ, s.replace('.hip', '.tuning.o' if s in TUNING_SOURCES else '.o')) for s in SOURCES]
     tobjs += [os.path.join(OBJ, _stem(s).replace('.hip', '.tuning.o')) for s in TUNING_ONLY]
     problems = verify(verbose)
+    for s in LEAN_UNITS:
+        for name, r in kernel_resources(s).items():
+            if r.get('agpr', 0) or r.get('scratch', 0):
+                problems.append('%s: %s uses %d AGPRs / %d bytes of scratch' % (s, name, r.get('agpr', 0), r.get('scratch', 0)))
     if problems:
         for lib in (LIB, LIB_TUNING):   # never leave a library of unsound kernels behind
             if os.path.exists(lib):

@@ -63,11 +63,18 @@ class _Slot(object):
 # device), so an epoch borrows a ring of this process and gives it back; concurrent epochs each get their own.
 _RINGS = []
 _RINGS_LOCK = threading.Lock()
+# The producer may overwrite a slot's pinned buffers only once the copies that read them have been ISSUED (then it waits for
+# their event): with STAGE_QUEUE stages waiting in the queue, one in the issuing thread's hands and one being filled, a ring
+# shorter than STAGE_QUEUE + 2 would hand out a slot whose copies are not issued yet (`uploaded` still None: no wait, silently
+# corrupted inputs).  lamp_amd/train.py shares the queue, the ring and this relation.
+STAGE_QUEUE = 2
+RING_SLOTS = 4
+assert RING_SLOTS >= STAGE_QUEUE + 2, 'the pinned ring must be at least two slots longer than the stage queue'
 
 
 def _borrow_ring():
     with _RINGS_LOCK:
-        return _RINGS.pop() if _RINGS else [_Slot() for _ in range(4)]
+        return _RINGS.pop() if _RINGS else [_Slot() for _ in range(RING_SLOTS)]
 
 
 def _return_ring(ring):
@@ -99,7 +106,7 @@ def _produce(it, n_labels, batch_size, prefetch, all_targets, out_q, pin, device
     try:
         if pin:
             torch.cuda.set_device(device)    # pinned allocations belong to THIS rank's device context, not to device 0's
-        ring, n_stage = ring if ring is not None else [_Slot() for _ in range(4)], 0
+        ring, n_stage = ring if ring is not None else [_Slot() for _ in range(RING_SLOTS)], 0
         while not stop.is_set():
             host = []
             for _ in range(stage_batches(n_stage, prefetch)):
@@ -206,7 +213,7 @@ def test_epoch(model, batches, n_labels, batch_size, device, pad_last_batch=True
     targets_d = torch.empty_like(probs_d) if device_results is not None else None
     for lane in lanes:
         lane.wait_stream(main)    # the buffers (and the model's weights) are ready on every lane
-    stages, stop = queue.Queue(maxsize=2), threading.Event()
+    stages, stop = queue.Queue(maxsize=STAGE_QUEUE), threading.Event()
     ring = _borrow_ring()
     producer = threading.Thread(target=_produce, name='lamp-eval-producer', daemon=True,
                                 args=(it, n_labels, batch_size, max(int(prefetch), 1), all_targets, stages, pin, device, stop, bool(merge_stage), ring))

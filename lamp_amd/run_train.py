@@ -1,0 +1,285 @@
+"""Training runner: the reference's `main.py` + `runner.run_model` flow (without -test_only) for encoder=graph /
+decoder=graph, on the MI355X path.
+
+    python -m lamp_amd.run_train -data data/reuters/train_valid_test.pt -dataset reuters -batch_size 32 \
+           -d_model 512 -n_layers_enc 2 -n_head 4 -label_mask prior -epoch 50 -dropout 0.1 -lr 0.0002 [-int_preds] \
+           [-lr_decay 0.9 -lr_step_size 10] [-save_mode best] [-load_pretrained] [-name run1] [-results_dir results/]
+
+Flag names and derived defaults are config_args.py's for everything on this path (n_layers_dec = n_layers_enc :87-88,
+test_batch_size = batch_size :93-94, d_k = d_v = d_model / n_head :96-99, dec_dropout = dropout :101-102, no position
+embedding for bibtext / delicious / bookmarks / sider :104-105, d_inner_hid = 2 d_model :110-111, n_head2 = n_head :135-136,
+-int_preds only with the graph decoder :213-216, the one-hot encoder for the genomics datasets :90-91, and the results
+directory name :121-227).  Two deliberate differences: -data names the dataset file itself (as run_eval does; the reference
+joins -dataroot and -dataset), and -decoder defaults to 'graph', the decoder this path serves (the reference's default 'sa_m'
+exists in its argparse only).
+
+Per epoch, as runner.py:36-92: scheduler.step() first (:38, when -lr_decay > 0), train_epoch (lamp_amd/train.py),
+evaluate.test_epoch on valid and test, the metrics of all three splits on the device (lamp_amd/metrics.py), one JSON line, a
+row of losses.csv (epoch, train, valid, test loss, each summed batch means / instances as the reference reports them), and the
+checkpoint {'model': state_dict, 'settings': opt, 'epoch': i} under utils.save_model's rule (utils/utils.py:228-241).  That
+rule's `valid_loss >= min(valid_losses)` is kept as written: the list already holds the current loss, so -save_mode best
+rewrites model.chkpt after EVERY epoch -- the reference's behaviour, not a selection of the best epoch.  As in the reference
+(runner.py:85) nothing is saved when the results directory's name contains 'test'.  The file loads in
+`run_eval -checkpoint` and in the reference's `main.py -load_pretrained`.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import warnings
+
+import torch
+
+from . import data as D
+from .run_eval import ONEHOT_DATASETS
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('-data', required=True, help='train_valid_test.pt in the reference format')
+    ap.add_argument('-dataset', type=str, default='reuters')
+    ap.add_argument('-results_dir', type=str, default='results/')
+    ap.add_argument('-epoch', type=int, default=50)
+    ap.add_argument('-batch_size', type=int, default=64)
+    ap.add_argument('-test_batch_size', type=int, default=-1)
+    ap.add_argument('-d_model', type=int, default=512)
+    ap.add_argument('-d_inner_hid', type=int, default=-1)
+    ap.add_argument('-d_k', type=int, default=-1)
+    ap.add_argument('-d_v', type=int, default=-1)
+    ap.add_argument('-n_head', type=int, default=8)
+    ap.add_argument('-n_head2', type=int, default=0)
+    ap.add_argument('-n_layers_enc', type=int, default=5)
+    ap.add_argument('-n_layers_dec', type=int, default=None)
+    ap.add_argument('-optim', type=str, choices=['adam', 'sgd'], default='adam')
+    ap.add_argument('-lr', type=float, default=0.0002)
+    ap.add_argument('-lr_step_size', type=int, default=1)
+    ap.add_argument('-lr_decay', type=float, default=0)
+    ap.add_argument('-dropout', type=float, default=0.1)
+    ap.add_argument('-dec_dropout', type=float, default=-1)
+    ap.add_argument('-no_dec_self_att', action='store_true')
+    ap.add_argument('-loss', type=str, choices=['ce', 'adv', 'ranking'], default='ce')
+    ap.add_argument('-save_mode', type=str, choices=['all', 'best'], default='best')
+    ap.add_argument('-encoder', type=str, choices=['rnn', 'graph', 'emb', 'mlp'], default='graph')
+    ap.add_argument('-decoder', type=str, choices=['sa_m', 'rnn_m', 'sa_b', 'graph', 'mlp'], default='graph')
+    ap.add_argument('-label_mask', type=str, choices=['none', 'inveye', 'prior'], default='none')
+    ap.add_argument('-br_threshold', type=float, default=0.5)
+    ap.add_argument('-no_enc_pos_embedding', action='store_true')
+    ap.add_argument('-int_preds', action='store_true')
+    ap.add_argument('-load_pretrained', action='store_true')
+    ap.add_argument('-int_pred_weight', type=float, default=0.2)
+    ap.add_argument('-attns_loss', action='store_true')
+    ap.add_argument('-name', type=str, default=None)
+    # this runner's own
+    ap.add_argument('-optim_impl', choices=['lamp', 'torch'], default=DEFAULT_OPTIM_IMPL,
+                    help='lamp = lamp_amd.optim (one lamp_optim_step launch per step); torch = torch.optim (fused=True for adam)')
+    ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4], help='batches in flight in the valid / test epochs')
+    ap.add_argument('-prefetch', type=int, default=8, help='batches per stage of the producer thread')
+    ap.add_argument('-seed', type=int, default=0, help='torch.manual_seed: weight init, shuffling, dropout seeds')
+    ap.add_argument('-gpus', type=int, default=1)
+    opt = ap.parse_args(argv)
+    return derive(opt)
+
+
+# torch's fused Adam: lamp_optim_step has not been shown to beat it same-box (nothing is measured yet; tools/bench_train_epoch.py
+# is the tool that would), and without a measured win the default stays torch's
+DEFAULT_OPTIM_IMPL = 'torch'
+
+
+def derive(opt):
+    """config_args.py:80-259 for the flags above."""
+    if opt.gpus != 1:
+        raise NotImplementedError('-gpus %d: multi-GPU training is out of scope here -- no gradient collective exists in this '
+                                  'library (run_eval -gpus N shards evaluation, which needs none)' % opt.gpus)
+    if opt.n_layers_dec is None:
+        opt.n_layers_dec = opt.n_layers_enc
+    opt.onehot = opt.dataset in ONEHOT_DATASETS
+    if opt.test_batch_size <= 0:
+        opt.test_batch_size = opt.batch_size
+    if opt.d_v == -1:
+        opt.d_v = int(opt.d_model / opt.n_head)
+    if opt.d_k == -1:
+        opt.d_k = int(opt.d_model / opt.n_head)
+    if opt.dec_dropout == -1:
+        opt.dec_dropout = opt.dropout
+    if opt.dataset in ('bibtext', 'delicious', 'bookmarks', 'sider'):
+        opt.no_enc_pos_embedding = True
+    if opt.d_inner_hid == -1:
+        opt.d_inner_hid = int(opt.d_model * 2)
+    if opt.decoder in ('mlp', 'rnn_m'):
+        opt.n_head = 1
+        opt.d_k = opt.d_model
+    name = 'enc_' + opt.encoder + '.dec_' + opt.decoder
+    name += '.%s.%s.%s.%s' % (opt.d_model, opt.d_inner_hid, opt.d_k, opt.d_v)
+    name += '.nlayers_%s_%s' % (opt.n_layers_enc, opt.n_layers_dec)
+    name += '.nheads_' + str(opt.n_head)
+    if opt.n_head2 == 0:
+        opt.n_head2 = opt.n_head
+    else:
+        name += '_' + str(opt.n_head2)
+    opt.proj_share_weight = opt.decoder != 'mlp'
+    if opt.proj_share_weight:
+        name += '.proj_share'
+    name += '.bsz_' + str(opt.batch_size)
+    name += '.loss_' + str(opt.loss)
+    name += '.' + str(opt.optim)
+    name += '.lr_' + str(opt.lr).split('.')[1]
+    if opt.lr_decay > 0:
+        name += '.decay_' + str(opt.lr_decay).replace('.', '') + '_' + str(opt.lr_step_size)
+    name += '.drop_' + ('%.2f' % opt.dropout).split('.')[1] + '_' + ('%.2f' % opt.dec_dropout).split('.')[1]
+    if opt.decoder == 'graph' and opt.no_dec_self_att:
+        name += '.no_dec_self_att'
+    if opt.decoder == 'graph' and not opt.no_dec_self_att:
+        name += '.' + opt.label_mask + 'mask'
+    opt.dec_dropout2 = False
+    if opt.attns_loss:
+        name += '.attns_loss'
+    if opt.decoder == 'graph' and opt.int_preds:
+        name += '.int_preds_' + str(opt.int_pred_weight).replace('.', '')
+    else:
+        opt.int_preds = False
+    if opt.name:
+        name += '.' + str(opt.name)
+    opt.model_name = os.path.join(opt.results_dir, opt.dataset, name)
+    opt.data_type = opt.dataset
+    opt.d_word_vec = opt.d_model
+    opt.matching_mlp = False
+    if opt.decoder in ('mlp', 'sa_b', 'graph'):
+        opt.binary_relevance = True
+    elif opt.decoder in ('sa_m', 'rnn_m'):
+        opt.binary_relevance = False
+    if opt.encoder != 'graph' or opt.decoder != 'graph':
+        raise NotImplementedError("run_train trains encoder='graph' with decoder='graph' (the binary-relevance branch, "
+                                  "train.py:33-50); the '%s' encoder / '%s' decoder%s not served here" %
+                                  (opt.encoder, opt.decoder, ' (crit / log-softmax branch, train.py:52-66) are'
+                                   if not opt.binary_relevance else ' are'))
+    if opt.d_model % opt.n_head:
+        raise ValueError('d_model must be divisible by n_head')
+    return opt
+
+
+def build_model(opt, data, device):
+    """main.py:53-88."""
+    from .Models import LAMP
+    n_src, n_labels = D.vocabulary_sizes(data)
+    opt.src_vocab_size, opt.tgt_vocab_size = n_src, n_labels
+    opt.max_token_seq_len_e = data['settings'].max_seq_len
+    adj = (D.prior_adjacency_device(data['train']['tgt'], len(data['dict']['tgt']), device).cpu()
+           if opt.label_mask == 'prior' else None)
+    return LAMP(n_src, n_labels, opt.max_token_seq_len_e, n_labels, proj_share_weight=opt.proj_share_weight,
+                embs_share_weight=True, d_k=opt.d_k, d_v=opt.d_v, d_model=opt.d_model, d_word_vec=opt.d_word_vec,
+                d_inner_hid=opt.d_inner_hid, n_layers_enc=opt.n_layers_enc, n_layers_dec=opt.n_layers_dec, n_head=opt.n_head,
+                n_head2=opt.n_head2, dropout=opt.dropout, dec_dropout=opt.dec_dropout, dec_dropout2=opt.dec_dropout2,
+                encoder=opt.encoder, decoder=opt.decoder, onehot=opt.onehot, no_enc_pos_embedding=opt.no_enc_pos_embedding,
+                no_dec_self_att=opt.no_dec_self_att, loss=opt.loss, label_adj_matrix=adj, label_mask=opt.label_mask,
+                int_preds=opt.int_preds)
+
+
+def build_optimizer(model, opt):
+    """main.py:99 (the reference builds this Adam whatever -optim says; -optim sgd gets the plain update here)."""
+    params = list(model.get_trainable_parameters())
+    if opt.optim_impl == 'lamp':
+        from . import optim
+        return optim.Adam(params, betas=(0.9, 0.98), lr=opt.lr) if opt.optim == 'adam' else optim.SGD(params, lr=opt.lr)
+    if opt.optim == 'adam':
+        return torch.optim.Adam(params, betas=(0.9, 0.98), lr=opt.lr, fused=True)
+    return torch.optim.SGD(params, lr=opt.lr)
+
+
+def checkpoint_settings(opt):
+    """The Namespace that travels in the checkpoint: plain values only, so that it unpickles anywhere."""
+    return argparse.Namespace(**{k: v for k, v in vars(opt).items() if isinstance(v, (bool, int, float, str, type(None)))})
+
+
+def save_model(opt, epoch_i, model, valid_loss, valid_losses):
+    """utils/utils.py:228-241, `>=` included (see the module docstring).  -> the path written, or None."""
+    checkpoint = {'model': model.state_dict(), 'settings': checkpoint_settings(opt), 'epoch': epoch_i}
+    if opt.save_mode == 'all':
+        path = opt.model_name + '/accu_{accu:3.3f}.chkpt'.format(accu=100 * valid_loss)
+        torch.save(checkpoint, path)
+        return path
+    if opt.save_mode == 'best':
+        path = opt.model_name + '/model.chkpt'
+        if valid_loss >= min(valid_losses):
+            torch.save(checkpoint, path)
+            return path
+    return None
+
+
+def _json_metrics(m):
+    return {k: (v.tolist() if hasattr(v, 'tolist') else v) for k, v in m.items() if k not in ('allAUC', 'allAUPR')}
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    opt = parse(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit('lamp_amd.run_train needs an MI355X: no HIP device visible (there is no CPU path)')
+    from . import hostcpu
+    from .evaluate import test_epoch
+    from .metrics import compute_metrics
+    from .train import TrainBatcher, train_epoch
+    hostcpu.fit_intra_op_threads()
+    device = torch.device('cuda', torch.cuda.current_device())
+    data = D.load_dataset(opt.data)
+    torch.manual_seed(opt.seed)
+    model = build_model(opt, data, device)
+    opt.total_num_parameters = int(sum(p.numel() for p in model.parameters() if p.requires_grad))
+    model = model.to(device)       # (before the optimizer: torch's fused Adam wants device parameters at construction)
+    optimizer = build_optimizer(model, opt)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=opt.lr_step_size, gamma=opt.lr_decay, last_epoch=-1)
+    os.makedirs(opt.model_name, exist_ok=True)
+    if opt.load_pretrained:   # main.py:117-119
+        ckpt = torch.load(opt.model_name + '/model.chkpt', map_location='cpu', weights_only=False)
+        model.load_state_dict(ckpt['model'])
+    train_data = TrainBatcher(data['train']['src'], data['train']['tgt'], opt.batch_size, shuffle=True, drop_last=True)
+    valid_data = D.EvalBatcher(data['valid']['src'], data['valid']['tgt'], opt.test_batch_size)
+    test_data = D.EvalBatcher(data['test']['src'], data['test']['tgt'], opt.test_batch_size)
+    n_labels = opt.tgt_vocab_size
+    valid_losses, history = [], []
+    with open(os.path.join(opt.model_name, 'losses.csv'), 'w+') as loss_file:
+        for epoch_i in range(opt.epoch):
+            if scheduler and opt.lr_decay > 0:   # runner.py:38
+                with warnings.catch_warnings():
+                    warnings.simplefilter('ignore')
+                    scheduler.step()
+            out = {'epoch': epoch_i + 1, 'lr': optimizer.param_groups[0]['lr']}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            on_dev = {}
+            _, _, train_loss = train_epoch(model, train_data, optimizer, opt, device=device, prefetch=opt.prefetch,
+                                           device_results=on_dev)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            train_loss = train_loss / train_data.n_insts
+            metrics = {'train': compute_metrics(on_dev['probs'], on_dev['targets'], train_loss, opt.br_threshold, dt / 60)}
+            out.update(train_loss=train_loss, train_seconds=dt,
+                       train_samples_per_s=sum(real for _, real in on_dev['batches']) / dt)
+            losses = {}
+            for split, batches in (('valid', valid_data), ('test', test_data)):
+                t0 = time.perf_counter()
+                on_dev = {}
+                _, _, loss = test_epoch(model, batches, n_labels, opt.test_batch_size, device, streams=opt.streams,
+                                        prefetch=opt.prefetch, int_preds=opt.int_preds, device_results=on_dev)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                losses[split] = loss / batches.n_insts
+                metrics[split] = compute_metrics(on_dev['probs'], on_dev['targets'], losses[split], opt.br_threshold, dt / 60)
+                out['%s_loss' % split] = losses[split]
+                out['%s_samples_per_s' % split] = batches.n_insts / dt
+            valid_losses.append(losses['valid'])
+            out['metrics'] = {k: _json_metrics(v) for k, v in metrics.items()}
+            out['checkpoint'] = None
+            if 'test' not in opt.model_name:   # runner.py:85
+                out['checkpoint'] = save_model(opt, epoch_i, model, losses['valid'], valid_losses)
+            loss_file.write('%d,%s,%s,%s\n' % (epoch_i + 1, train_loss, losses['valid'], losses['test']))
+            loss_file.flush()
+            history.append(out)
+            print(json.dumps(out), flush=True)
+    return history
+
+
+if __name__ == '__main__':
+    main()

@@ -44,6 +44,10 @@ DEFER_WEIGHT_GRADS = True
 # of one Python round trip per launch: the reuters step is ~190 launches and was bound by the issuing thread
 # (tools/bench_train.py: host_issue_ms_per_step).  Same kernels, same bits; False = the per-launch route below.
 COMPOSITE_CALLS = True
+# The embedding gradient through lamp_embed_bwd_ordered (one writer per table row, repeated tokens in position order) instead of
+# the atomic scatter-add: lamp_amd/train.py switches it on for its epochs, which are reproducible bit for bit.  False = the
+# route as it always was.
+ORDERED_EMBED_GRAD = False
 
 
 def _plain(*tensors):
@@ -232,7 +236,7 @@ class _EmbedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         (src_seq,) = ctx.saved_tensors
-        d_emb = N.embed_bwd(src_seq, dout, ctx.n_vocab, pad_idx=Constants.PAD) if ctx.needs_input_grad[2] else None
+        d_emb = N.embed_bwd(src_seq, dout, ctx.n_vocab, pad_idx=Constants.PAD, ordered=ORDERED_EMBED_GRAD) if ctx.needs_input_grad[2] else None
         return None, None, d_emb, None  # the position table is frozen (lamp/Models.py:97-107)
 
 
