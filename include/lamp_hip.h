@@ -73,9 +73,16 @@ enum lamp_mask_kind {
                                     compute the allowed (query, key) pairs only (csrc/attention_sparse.hip) instead of visiting every
                                     key tile.  Set by the caller from the mask's density (lamp_amd/Decoders.py); exact either way. */
 
+#define LAMP_MASK_SELF_RAGGED 2  /* the call is a self-attention over ragged rows padded to a common length (the live encoder,
+                                    lamp_fwd_options): queries are padded as far as keys, so lq says nothing about the sample.
+                                    The kernel is then chosen without looking at lq or lk (always csrc/attention_small.hip, whose
+                                    key split follows each sample's own key count; one share when the mask brings no key counts):
+                                    a sample's bits do not depend on how far its batch was padded.  Heads wider than 128
+                                    (d_k or d_v > 128) run the general kernel whatever the flag says: the guarantee ends there. */
+
 typedef struct lamp_mask {
     int32_t kind;
-    int32_t flags;               /* LAMP_MASK_SPARSE_ROWS or 0 */
+    int32_t flags;               /* LAMP_MASK_SPARSE_ROWS | LAMP_MASK_SELF_RAGGED, or 0 */
     const void* ptr;
     int64_t stride_b;
     int64_t stride_q;
@@ -466,6 +473,45 @@ int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src
                  int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux,
                  void* workspace, size_t workspace_bytes, lamp_stream_t stream);
 
+/* Options of lamp_forward_opts / lamp_onehot_forward_opts.  NULL, or a zeroed struct, is lamp_forward as it is.
+ *   enc_self_attn != 0: the encoder's self-attention is LIVE -- the feature->feature step of the published model.  The
+ *     reference computes the block and then overwrites its output (lamp/Layers.py:16-18: `enc_output = pos_ffn(enc_input)`);
+ *     with this flag a layer is  h, attn = slf_attn(x, x, x, mask);  out = pos_ffn(h)  instead.  The encoder then runs the
+ *     padded [B, T, d_model] layout: every position is a query (a PAD query's zero row attends uniformly over its sample's
+ *     live keys, as the definition gives), each sample's keys stop at its last non-PAD token, and a sample whose tokens are
+ *     all PAD comes out NaN.  m->enc0_emb_w1 must be NULL (a live layer 0 does not start with W1).  aux->enc_self_attn, when
+ *     given, receives the maps of the attention that was used.
+ *   enc_mask (nullable): one byte mask per sample for the encoder's self-attention in place of the key-padding rule of
+ *     lamp/Encoders.py:82 -- the per-sample input graphs of lamp/Encoders.py:85-89.  LAMP_MASK_U8 with stride_b != 0,
+ *     element (b, q, k) at ptr[b * stride_b + q * stride_q + k] over the padded T x T square, nonzero = blocked, no tile list.
+ *     Needs the flag above or aux->enc_self_attn (otherwise nothing reads it: LAMP_E_UNSUPPORTED).
+ *   enc_chain_packs (nullable): host array of n_layers_enc packs of (slf_attn.fc, pos_ffn.w_1, pos_ffn.w_2), as
+ *     lamp_model.chain_packs holds them for the decoder: the live layer's row-local tail then runs as one chain launch where
+ *     the decoder's would.  Same bits with and without. */
+#define LAMP_FWD_PACKED_ENCODER 1  /* lamp_fwd_options.flags, with enc_self_attn: run the live encoder on the PACKED non-PAD token
+                                      rows plus one PAD row per sample (csrc/attention_ragged.hip: queries as ragged as keys, no PAD
+                                      position computed) where it applies -- no enc_mask, no encoder maps, no one-hot front end,
+                                      every encoder layer with more than one head, d_k == d_v <= 128, T <= ~16 k -- else the padded
+                                      layout as without the flag.  Same definition, other kernel: results agree within rounding,
+                                      not bit for bit, with the padded route; a sample's bits do not depend on T or B either way. */
+
+typedef struct lamp_fwd_options {
+    int32_t enc_self_attn;
+    int32_t flags;               /* LAMP_FWD_PACKED_ENCODER or 0 */
+    const lamp_mask* enc_mask;
+    const lamp_chain_pack* enc_chain_packs;
+} lamp_fwd_options;
+
+/* lamp_forward_workspace_bytes / lamp_forward with options (a live encoder needs query and attention-output rows for
+ * max(T, n_labels) positions per sample instead of n_labels).  Sized and carved from the same layout; micro-batching and
+ * the bit-for-bit independence of a sample from B and from the split hold as for lamp_forward.  The live self-attention runs
+ * under LAMP_MASK_SELF_RAGGED, so a sample's bits do not depend on T either (d_k, d_v <= 128). */
+size_t lamp_forward_opts_workspace_bytes(const lamp_model* m, const lamp_fwd_options* opts, int32_t micro_batch, int32_t T,
+                                         int32_t want_attn);
+int lamp_forward_opts(const lamp_model* m, const lamp_fwd_options* opts, const int64_t* src_seq, const int64_t* src_pos,
+                      int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
+                      size_t workspace_bytes, lamp_stream_t stream);
+
 /* ---- the one-hot genomics encoder (GraphEncoder(onehot=True), lamp/Encoders.py:46-51,68-73) ----------------------
  * For src_seq / src_pos int64 [B, T] over a vocabulary of n_vocab (9) symbols, with T2 = T / 2:
  *   y1 = conv1(E[src]^T)[:, :, :T]            Conv1d(n_vocab, d, 16, padding 8)
@@ -494,6 +540,14 @@ size_t lamp_onehot_forward_workspace_bytes(const lamp_model* m, const lamp_oneho
 int lamp_onehot_forward(const lamp_model* m, const lamp_onehot_frontend* fe, const int64_t* src_seq, const int64_t* src_pos,
                         int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
                         size_t workspace_bytes, lamp_stream_t stream);
+
+/* lamp_onehot_forward with options (lamp_fwd_options above; enc_mask then covers the T2 x T2 square). */
+size_t lamp_onehot_forward_opts_workspace_bytes(const lamp_model* m, const lamp_onehot_frontend* fe, const lamp_fwd_options* opts,
+                                                int32_t micro_batch, int32_t T, int32_t want_attn);
+int lamp_onehot_forward_opts(const lamp_model* m, const lamp_onehot_frontend* fe, const lamp_fwd_options* opts,
+                             const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T, float* logits,
+                             float* enc_output, const lamp_aux* aux, void* workspace, size_t workspace_bytes,
+                             lamp_stream_t stream);
 
 /* Building blocks of the one-hot encoder (training, module-by-module use).  Padded layout "xpad": [B * (T2 + 16) + 16, d]
  * rows, sample b's row q at b * (T2 + 16) + 8 + q, every other row 0.

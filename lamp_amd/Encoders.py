@@ -6,7 +6,10 @@ PyTorch on the device.  MLPEncoder (:16-27) and RNNEncoder (:112-137) are the re
 8f n4): plain PyTorch modules with the reference's parameter names and shapes, so every ``main.py -encoder`` choice
 constructs and reference checkpoints load; they run wherever their tensors live.  Per-sample input graphs (``adj``,
 :81-85) only shape the encoder's attention maps -- its attention OUTPUT is dead compute -- and are served as a generic
-uint8 mask on the module-by-module route when maps are requested (logits identical either way).  The genomics
+uint8 mask on the module-by-module route when maps are requested (logits identical either way).  With
+``enc_self_attn=True`` the attention output is LIVE (Layers.EncoderLayer: the paper's feature->feature step, which the
+reference's code never trains): every layer attends under the key-padding mask, or under ``adj`` when it is given, and
+the graphs then reach the predictions.  The genomics
 one-hot branch (onehot=True, :46-51,68-73: conv1 -> ReLU(dropout) -> max-pool -> conv2 -> ReLU + positions) runs on
 csrc/conv.hip; it serves the reference's 9-symbol DNA vocabulary with position rows and no enc_transform.
 """
@@ -21,8 +24,9 @@ from .Layers import EncoderLayer
 class GraphEncoder(nn.Module):
     def __init__(self, n_src_vocab, n_max_seq, n_layers=6, n_head=8, d_k=64, d_v=64, d_word_vec=512,
                  d_model=512, d_inner_hid=1024, onehot=False, enc_transform='', dropout=0.1,
-                 no_enc_pos_embedding=False):
+                 no_enc_pos_embedding=False, enc_self_attn=False):
         super().__init__()
+        self.enc_self_attn = bool(enc_self_attn)
         if onehot:
             if n_src_vocab != ONEHOT_VOCAB:
                 # conv1 has 9 input channels: the reference fails at its first forward for any other vocabulary
@@ -53,7 +57,8 @@ class GraphEncoder(nn.Module):
             self.position_enc = nn.Embedding(n_position, d_word_vec, padding_idx=Constants.PAD)
             self.position_enc.weight.data = utils.position_encoding_init(n_position, d_word_vec)
         self.layer_stack = nn.ModuleList(
-            EncoderLayer(d_model, d_inner_hid, n_head, d_k, d_v, dropout=dropout) for _ in range(n_layers))
+            EncoderLayer(d_model, d_inner_hid, n_head, d_k, d_v, dropout=dropout, live_attn=self.enc_self_attn)
+            for _ in range(n_layers))
 
     def forward(self, src_seq, adj, src_pos, return_attns=False):
         pos_table = self.position_enc.weight if hasattr(self, 'position_enc') else None
@@ -72,17 +77,18 @@ class GraphEncoder(nn.Module):
         else:
             x = N.embed(src_seq, src_pos, self.src_word_emb.weight, pos_table)
         attns = []
-        pad_mask, keep = (N.key_token_mask(src_seq, src_seq.size(1)) if return_attns else (None, None))
-        if adj and return_attns:
+        live = self.enc_self_attn
+        pad_mask, keep = (N.key_token_mask(src_seq, src_seq.size(1)) if return_attns or live else (None, None))
+        if adj and (return_attns or live):
             # per-sample input graphs (lamp/Encoders.py:81-85): inside each sample's n x n corner the self-attention mask
-            # is the complement of its adjacency instead of the key-padding pattern.  The encoder's self-attention OUTPUT
-            # is discarded (lamp/Layers.py:16-18), so this only ever shows in the returned attention maps.
-            T = src_seq.size(1)
-            m = utils.get_attn_padding_mask(src_seq, src_seq).to(torch.uint8).contiguous()
-            for i, a in enumerate(adj):
-                n = a.size(0)
-                m[i, :n, :n] = utils.swap_0_1(a.to(m.device), 1, 0).to(torch.uint8)
-            pad_mask, keep = m, None
+            # is the complement of its adjacency instead of the key-padding pattern.  In the dead mode the encoder's
+            # self-attention OUTPUT is discarded (lamp/Layers.py:16-18), so this only ever shows in the returned maps.
+            pad_mask, keep = adj_attn_mask(src_seq, adj), None
+        if live:
+            # the live attention's kernel is chosen from the sample, not from the padded length (LAMP_MASK_SELF_RAGGED)
+            if not isinstance(pad_mask, N.Mask):
+                pad_mask, keep = N.make_mask(pad_mask, src_seq.size(0), src_seq.size(1), src_seq.size(1))
+            pad_mask.flags |= N.LAMP_MASK_SELF_RAGGED
         for layer in self.layer_stack:
             x, a = layer(x, slf_attn_mask=pad_mask, need_attn=return_attns)
             if return_attns:
@@ -93,6 +99,16 @@ class GraphEncoder(nn.Module):
 
 
 ONEHOT_VOCAB = 9   # PAD, UNK, BOS, EOS and five bases
+
+
+def adj_attn_mask(src_seq, adj):
+    """lamp/Encoders.py:82,85-89: the encoder self-attention's uint8 mask [B, T, T] (nonzero = blocked) -- the key-padding
+    pattern, with the complement of sample i's adjacency in its n x n corner."""
+    m = utils.get_attn_padding_mask(src_seq, src_seq).to(torch.uint8).contiguous()
+    for i, a in enumerate(adj):
+        n = a.size(0)
+        m[i, :n, :n] = utils.swap_0_1(a.to(m.device), 1, 0).to(torch.uint8)
+    return m
 
 
 def onehot_input(enc, src_seq, src_pos):

@@ -8,15 +8,24 @@ class EncoderLayer(nn.Module):
     """Token-state update.  In the reference the self-attention's OUTPUT is computed and then
     overwritten by ``pos_ffn(enc_input)`` (lamp/Layers.py:16-18): only its attention map is ever
     observable.  ``need_attn=False`` therefore skips the block entirely and returns ``None`` for the
-    map; the default keeps the reference's return value."""
+    map; the default keeps the reference's return value.
 
-    def __init__(self, d_model, d_inner_hid, n_head, d_k, d_v, dropout=0.1):
+    ``live_attn=True`` is the feature->feature step of the published model, which the reference's code never runs: the
+    attention's output feeds ``pos_ffn`` -- ``h, attn = slf_attn(x, x, x, mask); out = pos_ffn(h)`` -- and its parameters
+    train.  Same parameters, names and shapes in both modes."""
+
+    def __init__(self, d_model, d_inner_hid, n_head, d_k, d_v, dropout=0.1, live_attn=False):
         super().__init__()
+        self.live_attn = bool(live_attn)
         self.slf_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
         self.pos_ffn = PositionwiseFeedForward(d_model, d_inner_hid, dropout=dropout)
 
     def forward(self, enc_input, slf_attn_mask=None, need_attn=True):
         attn = None
+        if self.live_attn:
+            self.slf_attn.need_attn = need_attn
+            h, attn = self.slf_attn(enc_input, enc_input, enc_input, attn_mask=slf_attn_mask)
+            return self.pos_ffn(h), (attn if need_attn else None)
         if need_attn:
             _, attn = self.slf_attn(enc_input, enc_input, enc_input, attn_mask=slf_attn_mask)
         return self.pos_ffn(enc_input), attn

@@ -4,6 +4,12 @@
 kernel launches for a 2+2-layer model instead of the reference's ~140 ATen ops, no
 per-forward mask materialisation, no head split/merge copies, and the discarded encoder
 self-attention (lamp/Layers.py:16-18) is simply not computed unless its maps are requested.
+
+``enc_self_attn=True`` switches the encoder's self-attention ON: the feature->feature message passing of the published
+model, which the reference's code computes and then overwrites -- its ``w_qs / w_ks / w_vs / fc / layer_norm`` never train
+there.  It is this project's own switch (last keyword, default off: every reference call constructs the reference's model),
+served by ``lamp_forward_opts`` in eval and by lamp_amd/training.py in training; parameters and ``state_dict`` are the same in
+both modes.
 """
 import ctypes as C
 
@@ -18,14 +24,30 @@ from .Encoders import GraphEncoder, MLPEncoder, RNNEncoder
 from .SubLayers import XavierLinear
 
 
+def _chain_pack(fc, w1, w2, keep):
+    """lamp_chain_pack of one sub-chain's (fc, w_1, w_2) in both formats; the packed tensors are appended to `keep`."""
+    ptrs = []
+    for fmt in (0, 1):
+        trio = [N.weight_pack(w, fmt) for w in (fc, w1, w2)]
+        if any(t is None for t in trio):
+            trio = [None] * 3
+        keep.append(trio)
+        ptrs += [N.ptr(t) for t in trio]
+    return N.ChainPack(*ptrs)
+
+
 class LAMP(nn.Module):
     def __init__(self, n_src_vocab, n_tgt_vocab, n_max_seq_e, n_max_seq_d, n_layers_enc=6, n_layers_dec=6,
                  n_head=8, n_head2=8, d_word_vec=512, d_model=512, d_inner_hid=1024, d_k=64, d_v=64,
                  dropout=0.1, dec_dropout=0.1, dec_dropout2=0.1, proj_share_weight=True,
                  embs_share_weight=True, encoder='selfatt', decoder='sa_m', enc_transform='', onehot=False,
                  no_enc_pos_embedding=False, no_dec_self_att=False, loss='ce', label_adj_matrix=None,
-                 label_mask=None, matching_mlp=False, graph_conv=False, attn_type='softmax', int_preds=False):
+                 label_mask=None, matching_mlp=False, graph_conv=False, attn_type='softmax', int_preds=False,
+                 enc_self_attn=False):
         super().__init__()
+        if enc_self_attn and encoder != 'graph':
+            raise NotImplementedError('enc_self_attn=True belongs to the graph encoder, not to encoder=%r' % (encoder,))
+        self.enc_self_attn = bool(enc_self_attn)
         if d_model != d_word_vec:
             raise ValueError('d_model must equal d_word_vec (residual connections)')
         self.decoder_type = decoder
@@ -37,7 +59,7 @@ class LAMP(nn.Module):
             self.encoder = GraphEncoder(
                 n_src_vocab, n_max_seq_e, n_layers=n_layers_enc, n_head=n_head, d_word_vec=d_word_vec,
                 d_model=d_model, d_k=d_k, d_v=d_v, d_inner_hid=d_inner_hid, onehot=onehot, dropout=dropout,
-                no_enc_pos_embedding=no_enc_pos_embedding, enc_transform=enc_transform)
+                no_enc_pos_embedding=no_enc_pos_embedding, enc_transform=enc_transform, enc_self_attn=enc_self_attn)
         elif encoder == 'mlp':
             self.encoder = MLPEncoder(
                 n_src_vocab, n_max_seq_e, n_layers=n_layers_enc, n_head=n_head, d_word_vec=d_word_vec, d_model=d_model,
@@ -176,6 +198,13 @@ class LAMP(nn.Module):
                     out += [att.fc.weight, ff.w_1.weight, ff.w_2.weight]
         return out
 
+    def _enc_chain_weights(self):
+        out = []
+        for l in self.encoder.layer_stack:
+            if getattr(l.slf_attn, 'fc', None) is not None:
+                out += [l.slf_attn.fc.weight, l.pos_ffn.w_1.weight, l.pos_ffn.w_2.weight]
+        return out
+
     def _native_model(self):
         """Build (and cache, keyed on every weight's data_ptr) the lamp_model struct."""
         replica = getattr(self, '_is_replica', False)
@@ -192,15 +221,19 @@ class LAMP(nn.Module):
         hoist = self.cache_layer0_query and not replica   # the hoisted projection needs a one-off stream sync
         packs = self.use_chain_packs and not replica      # weights-only repacks: same one-off cost, same staleness rule
         onehot = bool(getattr(self.encoder, 'onehot', False))
-        fold = self.fold_embedding and not replica and len(self.encoder.layer_stack) > 0 and not onehot   # weights-only tables, likewise
+        live = self.enc_self_attn
+        # weights-only tables, likewise; a live layer 0 starts with the attention, not with W1: nothing to fold into
+        fold = self.fold_embedding and not replica and len(self.encoder.layer_stack) > 0 and not onehot and not live
         sparse = bool(self.use_sparse_label_attention and self.use_mask_bits and self.decoder.label_rows_sparse)
         key = tuple(p.data_ptr() for p in params) + (N.ptr(mask), N.ptr(bits), N.ptr(tiles), self.use_label_tiles,
-                                                      hoist, self.use_mask_bits, packs, fold, sparse)
+                                                      hoist, self.use_mask_bits, packs, fold, sparse, live)
         if hoist:  # the hoisted projection below is stale once either operand changes
             l0 = self.decoder.layer_stack[0].enc_attn
             key += (self.decoder.tgt_word_emb.weight._version, l0.w_qs.weight._version)
         if packs:
             key += tuple(w._version for w in self._chain_weights())
+            if live:
+                key += tuple(w._version for w in self._enc_chain_weights())
         if fold:
             key += tuple(w._version for w in self._fold_weights() if w is not None)
         if onehot:   # the tap table and W2's repack are weights-only: rebuilt per weight version
@@ -250,15 +283,18 @@ class LAMP(nn.Module):
                 for j, (att, ff) in enumerate(((l.enc_attn, l.pos_ffn1), (getattr(l, 'slf_attn', None), l.pos_ffn2))):
                     if att is None or getattr(att, 'fc', None) is None:
                         continue
-                    ptrs = []
-                    for fmt in (0, 1):
-                        trio = [N.weight_pack(w, fmt) for w in (att.fc.weight, ff.w_1.weight, ff.w_2.weight)]
-                        if any(t is None for t in trio):
-                            trio = [None] * 3
-                        pack_keep.append(trio)
-                        ptrs += [N.ptr(t) for t in trio]
-                    pack_arr[2 * i + j] = N.ChainPack(*ptrs)
+                    pack_arr[2 * i + j] = _chain_pack(att.fc.weight, ff.w_1.weight, ff.w_2.weight, pack_keep)
             m.chain_packs = pack_arr
+            torch.cuda.current_stream().synchronize()
+        enc_pack_arr = None
+        if packs and live and len(enc.layer_stack) > 0:
+            # the live encoder layers' row-local tails are the same sub-chain (lamp_fwd_options.enc_chain_packs)
+            enc_pack_arr = (N.ChainPack * len(enc.layer_stack))()
+            pack_keep = pack_keep if pack_keep is not None else []
+            for i, l in enumerate(enc.layer_stack):
+                if getattr(l.slf_attn, 'fc', None) is None:
+                    continue
+                enc_pack_arr[i] = _chain_pack(l.slf_attn.fc.weight, l.pos_ffn.w_1.weight, l.pos_ffn.w_2.weight, pack_keep)
             torch.cuda.current_stream().synchronize()
         fold_keep = None
         if fold:
@@ -283,7 +319,7 @@ class LAMP(nn.Module):
             fe = N.onehot_frontend(t1, b1c, w2c, b2c, w2p)
             onehot_keep = (fe, t1, w2c, b1c, b2c, w2p)
             torch.cuda.current_stream().synchronize()
-        built = (m, enc_arr, dec_arr, q0, pack_arr, pack_keep, fold_keep, onehot_keep)
+        built = (m, enc_arr, dec_arr, q0, pack_arr, pack_keep, fold_keep, onehot_keep, enc_pack_arr)
         if not replica:
             self._native_cache = (key, built)
         return built
@@ -329,7 +365,7 @@ class LAMP(nn.Module):
             raise NotImplementedError('per-sample input graphs (adj) are not served with the one-hot encoder')
         if not self._fused:
             return self._forward_composite(src, adj, tgt_seq, return_attns, int_preds)
-        if adj and return_attns and not int_preds and not self.training:
+        if adj and return_attns and not int_preds and not self.training and not self.enc_self_attn:
             # per-sample input graphs only shape the encoder's attention MAPS (its output is dead compute): the maps come
             # from the module-by-module route, everything else from the fused launcher below, which may ignore `adj`
             return self._forward_composite(src, adj, tgt_seq, return_attns, int_preds)
@@ -343,7 +379,7 @@ class LAMP(nn.Module):
             # train.py:36: the autograd-recording path (HIP kernels forward and backward, lamp_amd/training.py)
             from . import training
             return training.forward_train(self, src_seq, src_pos, return_attns=bool(return_attns and not int_preds),
-                                          int_preds=bool(int_preds))
+                                          int_preds=bool(int_preds), adj=adj if self.enc_self_attn else None)
         dev = src_seq.device
         seq = src_seq.long().contiguous()
         pos = src_pos.long().contiguous()
@@ -383,7 +419,24 @@ class LAMP(nn.Module):
             aux = N.Aux(a0, a1, a2, None, 0, 0)
 
         lib = N.lib()
-        if fe is not None:
+        opts = None
+        if self.enc_self_attn:
+            # the live encoder self-attention (lamp_fwd_options): per-sample input graphs ride along as one byte mask
+            opts = N.FwdOptions(1, N.LAMP_FWD_PACKED_ENCODER if self.use_packed_live_encoder else 0, None, built[8])
+            if adj:
+                from .Encoders import adj_attn_mask
+                m8 = adj_attn_mask(seq, adj)
+                mstruct = N.Mask(N.LAMP_MASK_U8, 0, m8.data_ptr(), T * T, T, None, 0, 0)
+                keep += [m8, mstruct]
+                opts.enc_mask = C.pointer(mstruct)
+        if opts is not None and fe is not None:
+            def ws_bytes(mb):
+                return lib.lamp_onehot_forward_opts_workspace_bytes(C.byref(model), C.byref(fe), C.byref(opts), mb, T_in,
+                                                                    int(want_attn))
+        elif opts is not None:
+            def ws_bytes(mb):
+                return lib.lamp_forward_opts_workspace_bytes(C.byref(model), C.byref(opts), mb, T, int(want_attn))
+        elif fe is not None:
             def ws_bytes(mb):
                 return lib.lamp_onehot_forward_workspace_bytes(C.byref(model), C.byref(fe), mb, T_in, int(want_attn))
         else:
@@ -395,7 +448,16 @@ class LAMP(nn.Module):
         whole = fixed + (per_sample - fixed) * B + 4096
         budget = max(per_sample + 4096, min(whole, self.workspace_limit_bytes))
         ws = N.workspace(budget, dev)
-        if fe is not None:
+        if opts is not None and fe is not None:
+            N.check(lib.lamp_onehot_forward_opts(C.byref(model), C.byref(fe), C.byref(opts), seq.data_ptr(), pos.data_ptr(), B,
+                                                 T_in, logits.data_ptr(), enc_output.data_ptr(),
+                                                 C.byref(aux) if aux is not None else None, ws.data_ptr(), ws.numel(),
+                                                 N.stream()), 'lamp_onehot_forward_opts')
+        elif opts is not None:
+            N.check(lib.lamp_forward_opts(C.byref(model), C.byref(opts), seq.data_ptr(), pos.data_ptr(), B, T,
+                                          logits.data_ptr(), enc_output.data_ptr(), C.byref(aux) if aux is not None else None,
+                                          ws.data_ptr(), ws.numel(), N.stream()), 'lamp_forward_opts')
+        elif fe is not None:
             N.check(lib.lamp_onehot_forward(C.byref(model), C.byref(fe), seq.data_ptr(), pos.data_ptr(), B, T_in,
                                             logits.data_ptr(), enc_output.data_ptr(), C.byref(aux) if aux is not None else None,
                                             ws.data_ptr(), ws.numel(), N.stream()), 'lamp_onehot_forward')
@@ -420,6 +482,9 @@ class LAMP(nn.Module):
     # Fold encoder layer 0's first FFN matrix into the embedding tables (weights-only: Emb . W1^T and Pos . W1^T + b1, one
     # GEMM fewer per forward; results move in the last bits, a re-association).  False = the unfolded route.
     fold_embedding = True
+    # Live encoder (enc_self_attn=True) on the packed token rows (csrc/attention_ragged.hip) instead of the padded layout.  Off:
+    # it measured slower than the padded route on the ragged reuters batch, so it ships behind this switch.
+    use_packed_live_encoder = False
     # Skip fully blocked 32x32 tiles of the label graph in the label->label attention.
     use_label_tiles = True
     # Compute only the allowed (query, key) pairs of a sparse, unstructured label graph (csrc/attention_sparse.hip; the

@@ -17,7 +17,8 @@ TUNING_LIB_PATH = os.path.join(_HERE, 'liblamp_hip_tuning.so')
 
 ABI_VERSION = 5
 LAMP_MASK_NONE, LAMP_MASK_U8, LAMP_MASK_KEY_TOKENS_I64, LAMP_MASK_BITS_U32 = 0, 1, 2, 3
-LAMP_MASK_SPARSE_ROWS = 1   # lamp_mask.flags (include/lamp_hip.h)
+LAMP_MASK_SPARSE_ROWS, LAMP_MASK_SELF_RAGGED = 1, 2   # lamp_mask.flags (include/lamp_hip.h)
+LAMP_FWD_PACKED_ENCODER = 1                            # lamp_fwd_options.flags
 K_EMBED, K_GEMM, K_ATTN, K_LAYERNORM, K_DIAG, K_COUNT = 0, 1, 2, 3, 4, 5
 KERNEL_CLASS_NAMES = ('embed', 'gemm', 'attention', 'layernorm', 'diag_readout')
 
@@ -102,6 +103,11 @@ class Aux(C.Structure):
                 ('n_int_preds', C.c_int32), ('reserved', C.c_int32)]
 
 
+class FwdOptions(C.Structure):  # include/lamp_hip.h: lamp_fwd_options
+    _fields_ = [('enc_self_attn', C.c_int32), ('flags', C.c_int32), ('enc_mask', C.POINTER(Mask)),
+                ('enc_chain_packs', C.POINTER(ChainPack))]
+
+
 class OnehotFrontend(C.Structure):  # include/lamp_hip.h: lamp_onehot_frontend
     _fields_ = [('t1', _vp), ('conv1_b', _vp), ('conv2_w', _vp), ('conv2_b', _vp), ('conv2_pack', _vp),
                 ('n_vocab', C.c_int32), ('taps', C.c_int32)]
@@ -163,6 +169,13 @@ PROTOTYPES = {
     'lamp_sigmoid_bce_fwd': (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     'lamp_forward_workspace_bytes': (_sz, [C.POINTER(Model), _i32, _i32, _i32]),
     'lamp_forward': (C.c_int, [C.POINTER(Model), _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(Aux), _vp, _sz, _vp]),
+    'lamp_forward_opts_workspace_bytes': (_sz, [C.POINTER(Model), C.POINTER(FwdOptions), _i32, _i32, _i32]),
+    'lamp_forward_opts': (C.c_int, [C.POINTER(Model), C.POINTER(FwdOptions), _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(Aux),
+                                    _vp, _sz, _vp]),
+    'lamp_onehot_forward_opts_workspace_bytes': (_sz, [C.POINTER(Model), C.POINTER(OnehotFrontend), C.POINTER(FwdOptions),
+                                                       _i32, _i32, _i32]),
+    'lamp_onehot_forward_opts': (C.c_int, [C.POINTER(Model), C.POINTER(OnehotFrontend), C.POINTER(FwdOptions), _vp, _vp, _i32,
+                                           _i32, _vp, _vp, C.POINTER(Aux), _vp, _sz, _vp]),
     'lamp_onehot_forward_workspace_bytes': (_sz, [C.POINTER(Model), C.POINTER(OnehotFrontend), _i32, _i32, _i32]),
     'lamp_onehot_forward': (C.c_int, [C.POINTER(Model), C.POINTER(OnehotFrontend), _vp, _vp, _i32, _i32, _vp, _vp,
                                       C.POINTER(Aux), _vp, _sz, _vp]),

@@ -126,6 +126,7 @@ static void attn_mask(AttnParams& a, const lamp_mask* mask) {
     a.tiles = (mask && !a.P) ? mask->tile_list : nullptr;
     a.tiles_stride = mask ? mask->tile_list_stride : 0;
     a.sparse_rows = mask && (mask->flags & LAMP_MASK_SPARSE_ROWS) != 0;
+    a.self_ragged = mask && (mask->flags & LAMP_MASK_SELF_RAGGED) != 0;
     a.allowed_pairs = mask ? mask->allowed_pairs : 0;
 }
 
@@ -790,12 +791,14 @@ struct FwdDims {
     int n_ahead;             // decoder layers whose enc-attention K / V are projected right after the encoder, or 0
     int fe_rows;             // one-hot front end: padded conv2 input rows per sample, else 0
     bool w2_repack;          // one-hot front end without a caller-packed conv2 weight
+    bool live;               // the encoder's self-attention output is used (lamp_fwd_options::enc_self_attn)
 };
 
 // The model checks the workspace sizes share with the forward.  T_in: tokens per sample; the one-hot front end `fe`
 // halves them.  The K/V-ahead buffers are counted for every decoder layer of a token model: the forward drops them
 // (n_ahead = 0) when it does not project ahead.
-static int fwd_dims(const lamp_model* m, const lamp_onehot_frontend* fe, int T_in, bool want_attn, FwdDims* g) {
+static int fwd_dims(const lamp_model* m, const lamp_onehot_frontend* fe, int T_in, bool want_attn, FwdDims* g,
+                    bool live = false) {
     if (!m) return LAMP_E_NULL;
     const int T = fe ? T_in / 2 : T_in;
     if (m->d_model <= 0 || m->d_inner <= 0 || m->d_k <= 0 || m->d_v <= 0 || m->n_labels <= 0 || T <= 0 ||
@@ -809,9 +812,9 @@ static int fwd_dims(const lamp_model* m, const lamp_onehot_frontend* fe, int T_i
         h = std::max(h, l.enc_attn.n_head);
         if (l.slf_attn.present) h = std::max(h, l.slf_attn.n_head);
     }
-    const int L = m->n_labels, R = std::max(T, L);
-    *g = FwdDims{T, L, R, want_attn ? R : L, m->d_model, m->d_inner, h, m->d_k, m->d_v, fe ? 0 : m->n_layers_dec,
-                 fe ? T + 16 : 0, fe && !fe->conv2_pack};
+    const int L = m->n_labels, R = std::max(T + (live ? 1 : 0), L);   // live, packed: + one PAD row per sample
+    *g = FwdDims{T, L, R, want_attn || live ? R : L, m->d_model, m->d_inner, h, m->d_k, m->d_v, fe ? 0 : m->n_layers_dec,
+                 fe ? T + 16 : 0, fe && !fe->conv2_pack, live};
     return 0;
 }
 
@@ -825,6 +828,7 @@ struct FwdScratch {
     unsigned long long* granules;   // the plan's hand-off words inside the merged plan + gather launch: 2 mb + 2
     int *row_tok, *row_pos;         // [mb T + 1] each: token / position of every packed row, for the gathered residual
     float *K_ahead[GEMM_MAX_SEG / 2], *V_ahead[GEMM_MAX_SEG / 2];   // K/V ahead
+    int* live_rows;     // live encoder on the packed rows: n_tok + mb, counted on the device (attention_ragged.hip)
     float* fe_x;        // the one-hot front end's zero-padded channel-last conv2 input
     float* w2;          // conv2's packed weight
 };
@@ -835,7 +839,8 @@ static void fwd_layout(const FwdDims& g, Carver& c, FwdScratch& w) {
     c.take(&w.H, size_t(g.R) * g.dff, g.dff);
     mha_layout(c, w.mha, g.Rq, g.R, g.h, g.dk, g.dv, false);
     c.take(&w.Y, size_t(g.L) * d);
-    c.take(&w.Xp, T * d, d);
+    c.take(&w.Xp, (T + (g.live ? 1 : 0)) * d, d);
+    if (g.live) c.take(&w.live_rows, 0, 4);
     take_plan(c, &w.plan_ints, g.T);
     c.take(&w.granules, 4, 4);
     c.take(&w.row_tok, 2 * T, 2);
@@ -876,6 +881,9 @@ struct Pass {
     lamp_mask label_mask;
     const float* xk = nullptr;   // what the decoder's K / V projections read: x or the packed rows
     int n_int = 0;               // intermediate predictions written so far
+    const lamp_mask* enc_mask = nullptr;             // the encoder self-attention's mask: &pad_mask, or this micro-batch's
+                                                     // slice of lamp_fwd_options::enc_mask
+    const lamp_chain_pack* enc_packs = nullptr;      // lamp_fwd_options::enc_chain_packs
 };
 
 // GraphEncoder.forward (lamp/Encoders.py:64-110) on the packed non-PAD token rows (+ ONE shared PAD row: all PAD positions
@@ -911,6 +919,42 @@ static int encode_packed(Pass& p) {
     return 0;
 }
 
+// The LIVE encoder (lamp_fwd_options) on the packed rows: lamp/Layers.py:16 with its output kept, no PAD position computed.
+// All PAD positions of one sample hold the same rows at every layer, so each sample has ONE PAD row (row n_tok + b) that is a
+// query like its live rows; keys are the live rows.  Q / K / V come from one 3-segment GEMM over the device-counted rows, the
+// attention is attention_ragged.hip, the row-local tail the separate launches (the chain launch takes a host row count), and
+// a last launch scatters into the padded encoder output.
+static int encode_packed_live(Pass& p) {
+    const lamp_model* m = p.m;
+    const FwdScratch& w = p.w;
+    const int d = p.g.d, dff = p.g.dff, T = p.g.T, dk = p.g.dk, dv = p.g.dv;
+    const int64_t Mub = int64_t(p.nb) * (T + 1);   // what the launches are sized for; the live count is *w.live_rows
+    const EmbedFold fold{nullptr, nullptr, dff, nullptr, nullptr, nullptr};
+    LAMP_CK(launch_embed_plan(p.seq, p.pos, m->position_enc != nullptr, p.nb, T, m->src_word_emb, m->n_src_vocab,
+                              m->position_enc, m->n_position, d, p.sp, w.granules, w.Xp, p.s, &fold));
+    LAMP_CK(launch_pad_rows(m->src_word_emb, m->position_enc, d, p.nb, p.sp, w.Xp, w.live_rows, p.s));
+    for (int i = 0; i < m->n_layers_enc; ++i) {
+        const lamp_mha_weights& a = m->enc_layers[i].slf_attn;
+        const int hdk = a.n_head * dk, hdv = a.n_head * dv;
+        const float* W[3] = {a.w_qs, a.w_ks, a.w_vs};
+        float* C[3] = {w.mha.Q, w.mha.K, w.mha.V};
+        LAMP_CK(linear(w.Xp, Mub, d, d, W, 3, hdk, d, nullptr, nullptr, 0, 0, C, hdk, p.s, w.live_rows));
+        LAMP_CK(launch_attn_ragged_self(w.mha.Q, w.mha.K, w.mha.V, w.mha.A, p.nb, a.n_head, T, dk, dv, p.sp, p.s));
+        const float* Wfc[1] = {a.fc};
+        float* Cx[1] = {w.Xp};
+        LAMP_CK(linear(w.mha.A, Mub, hdv, hdv, Wfc, 1, d, hdv, nullptr, w.Xp, d, 0, Cx, d, p.s, w.live_rows));
+        LayerNormParams ln{w.Xp, Mub, d, a.ln_g, a.ln_b, w.Xp};
+        ln.m_dev = w.live_rows;
+        LAMP_CK(launch_layernorm(ln, p.s));
+        FfnParams f{w.Xp, Mub, d, dff, &m->enc_layers[i].pos_ffn, w.Xp, w.H};
+        f.rows_dev = w.live_rows;
+        LAMP_CK(ffn_core(f, p.s));
+    }
+    LAMP_CK(launch_scatter_rows(w.Xp, d, p.nb, T, p.sp, p.x, p.s));
+    p.xk = w.Xp;
+    return 0;
+}
+
 // lamp/Encoders.py:68-73, the one-hot front end in place of the embedding gather: tap gather + ReLU + pair max, then conv2
 // as an implicit GEMM whose epilogue adds b2, applies the ReLU and adds the position row, straight into the encoder rows.
 static int encode_onehot_front(const Pass& p) {
@@ -923,8 +967,10 @@ static int encode_onehot_front(const Pass& p) {
 }
 
 // The encoder on the padded [nb, T, d] rows: when the dead encoder self-attention's maps are wanted (layer 0's map reads the
-// embedded rows, so they are written), with wide heads, or behind the one-hot front end.  The enc-dec attention still stops
-// at each sample's last real key.
+// embedded rows, so they are written), with wide heads, behind the one-hot front end, or with the LIVE self-attention
+// (g.live: its output feeds pos_ffn instead of being dropped -- every padded position is a query, a PAD query's zero row
+// attends uniformly over its sample's live keys; each sample's keys stop at its last real one).  The enc-dec attention
+// still stops at each sample's last real key.
 static int encode_padded(Pass& p) {
     const lamp_model* m = p.m;
     const FwdScratch& w = p.w;
@@ -941,15 +987,26 @@ static int encode_padded(Pass& p) {
     }
     for (int i = 0; i < m->n_layers_enc; ++i) {
         const lamp_enc_layer& l = m->enc_layers[i];
-        if (p.aux && p.aux->enc_self_attn && p.aux->enc_self_attn[i]) {
+        float* map = p.aux && p.aux->enc_self_attn ? p.aux->enc_self_attn[i] : nullptr;
+        FfnParams f{p.x, Me, d, dff, &l.pos_ffn, p.x, w.H};   // lamp/Layers.py:18
+        if (p.g.live) {
+            // lamp/Layers.py:16 with its output kept: x <- slf_attn(x, x, x), then pos_ffn(x).  The row-local tail
+            // (fc + residual -> LayerNorm -> W1 -> W2 + residual -> LayerNorm) is the decoder's sub-chain.
+            MhaCall a{p.x, p.x, p.nb, T, T, d, p.g.dk, p.g.dv, &l.slf_attn, p.enc_mask, p.x, map, p.B, int(p.b0)};
+            a.keys = &p.sp;
+            bool ffn_ran = false;
+            LAMP_CK(mha_attend(a, w.mha, p.s));
+            LAMP_CK(mha_tail(a, w.mha, &f, p.enc_packs ? p.enc_packs + i : nullptr, &ffn_ran, p.s));
+            if (!ffn_ran) LAMP_CK(ffn_core(f, p.s));
+            continue;
+        }
+        if (map) {
             // lamp/Layers.py:16 -- only the attention map of this block is ever observable.  Maps are
             // (h*B, T, T) over the WHOLE batch: this micro-batch fills rows h*B + b0 + b.
-            MhaCall a{p.x, p.x, p.nb, T, T, d, p.g.dk, p.g.dv, &l.slf_attn, &p.pad_mask, nullptr, p.aux->enc_self_attn[i],
-                      p.B, int(p.b0)};
+            MhaCall a{p.x, p.x, p.nb, T, T, d, p.g.dk, p.g.dv, &l.slf_attn, p.enc_mask, nullptr, map, p.B, int(p.b0)};
             a.keys = &p.sp;
             LAMP_CK(mha_attend(a, w.mha, p.s));
         }
-        FfnParams f{p.x, Me, d, dff, &l.pos_ffn, p.x, w.H};   // lamp/Layers.py:18
         f.hidden_ready = folded && i == 0;
         LAMP_CK(ffn_core(f, p.s));
     }
@@ -1005,7 +1062,10 @@ static int decoder_layer(Pass& p, int i) {
     bool ffn_ran = false;
     FfnParams f1{Y, Md, d, dff, &l.pos_ffn1, Y, w.H}, f2{Y, Md, d, dff, &l.pos_ffn2, Y, w.H};
     f2.n_labels = L;
-    if (last) { f2.w_out = m->w_out; f2.logits = p.logits + p.b0 * L; }   // the read-out (lamp/Models.py:124-126)
+    // the read-out (lamp/Models.py:124-126) rides in the last LayerNorm.  Not with the live encoder: there it is the read-out
+    // launch the module-by-module route ends with, so that the two routes agree bit for bit (the fused one sums in another order)
+    const bool fused_readout = last && !g.live;
+    if (fused_readout) { f2.w_out = m->w_out; f2.logits = p.logits + p.b0 * L; }
 
     // input->label messages (lamp/Layers.py:35); layer 0's query is the label table itself (its LayerNorm kernel adds the
     // shared residual)
@@ -1029,6 +1089,7 @@ static int decoder_layer(Pass& p, int i) {
         LAMP_CK(mha_tail(slf, w.mha, &f2, pk ? pk + 1 : nullptr, &ffn_ran, p.s));
     }
     if (!ffn_ran) LAMP_CK(ffn_core(f2, p.s));   // lamp/Layers.py:45
+    if (last && !fused_readout) LAMP_CK(launch_diag(Y, m->w_out, p.nb, L, d, p.logits + p.b0 * L, p.s));
     if (!last) LAMP_CK(int_pred(p));   // all but the last (lamp/Models.py:130)
     return 0;
 }
@@ -1045,7 +1106,7 @@ static int onehot_check(const lamp_model* m, const lamp_onehot_frontend* fe, int
 // The argument checks of lamp_forward and lamp_onehot_forward (fe), all before any launch.
 static int check_forward(const lamp_model* m, const lamp_onehot_frontend* fe, const int64_t* src_seq, const int64_t* src_pos,
                          int32_t B, int32_t T_in, const float* logits, const float* enc_output, const lamp_aux* aux,
-                         const void* workspace, FwdDims* g) {
+                         const void* workspace, FwdDims* g, const lamp_fwd_options* o = nullptr) {
     if (fe) LAMP_CK(onehot_check(m, fe, T_in));
     if (!m || !src_seq || (fe && !src_pos) || !logits || !enc_output || !workspace) return LAMP_E_NULL;
     if (B <= 0 || T_in <= 0) return LAMP_E_DIMS;
@@ -1053,7 +1114,22 @@ static int check_forward(const lamp_model* m, const lamp_onehot_frontend* fe, co
     if (m->position_enc && !src_pos) return LAMP_E_NULL;
     if (m->enc0_emb_w1 && m->position_enc && !m->enc0_pos_w1) return LAMP_E_NULL;
     if (m->n_layers_dec <= 0) return LAMP_E_DIMS;
-    LAMP_CK(fwd_dims(m, fe, T_in, aux && aux->enc_self_attn, g));
+    LAMP_CK(fwd_dims(m, fe, T_in, aux && aux->enc_self_attn, g, o && o->enc_self_attn));
+    if (g->live) {
+        // a live layer 0 starts with the attention, not with W1: the embedding fold has nothing to fold into
+        if (m->enc0_emb_w1) return LAMP_E_UNSUPPORTED;
+        for (int i = 0; i < m->n_layers_enc; ++i) {
+            const lamp_mha_weights& a = m->enc_layers[i].slf_attn;
+            if (!a.w_qs || !a.w_ks || !a.w_vs || !a.ln_g || !a.ln_b || (a.n_head > 1 && !a.fc)) return LAMP_E_NULL;
+            if (a.n_head < 1 || (a.n_head == 1 && m->d_v != m->d_model)) return LAMP_E_DIMS;
+        }
+    }
+    if (o && o->enc_mask) {
+        // one [T, T] byte mask per sample, inside the padded layout
+        LAMP_CK(check_mask(o->enc_mask));
+        if (o->enc_mask->kind != LAMP_MASK_U8 || o->enc_mask->stride_b == 0 || o->enc_mask->tile_list) return LAMP_E_UNSUPPORTED;
+        if (!g->live && !(aux && aux->enc_self_attn)) return LAMP_E_UNSUPPORTED;   // nothing would read it
+    }
     if ((m->d_model & 3) || (m->d_inner & 3) || (m->d_k & 3) || (m->d_v & 3)) return LAMP_E_UNSUPPORTED;
     if (fe && ((fe->conv2_pack && !aligned16(fe->conv2_pack)) || (!fe->conv2_pack && !aligned16(fe->conv2_w)) ||
                !aligned16(fe->t1) || !aligned16(fe->conv1_b) || !aligned16(workspace)))
@@ -1067,7 +1143,7 @@ static int check_forward(const lamp_model* m, const lamp_onehot_frontend* fe, co
 // every micro-batch split.
 static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const FwdDims& g, const int64_t* src_seq,
                    const int64_t* src_pos, int32_t B, int32_t T_in, float* logits, float* enc_output, const lamp_aux* aux,
-                   void* workspace, size_t workspace_bytes, hipStream_t s) {
+                   void* workspace, size_t workspace_bytes, hipStream_t s, const lamp_fwd_options* o = nullptr) {
     const Carver size = fwd_size(g);
     if (workspace_bytes < size.bound(1)) return LAMP_E_WORKSPACE;
     const int64_t mb = std::min<int64_t>(B, (workspace_bytes - size.fixed) / size.per);
@@ -1082,7 +1158,11 @@ static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const Fw
     // Ragged batches.  Every micro-batch first counts its samples' extents on the device (SeqPlan).  Packed: the encoder
     // runs on the packed non-PAD token rows and K / V are projected from them only.  Not packed (the dead encoder
     // self-attention's maps are wanted, wide heads, or the one-hot front end): the padded layout.
-    const bool packed = !(aux && aux->enc_self_attn) && !wide_heads(g.dk, g.dv) && m->n_layers_enc > 0 && !fe;
+    bool packed_live = g.live && o && (o->flags & LAMP_FWD_PACKED_ENCODER) && !o->enc_mask && g.dk == g.dv &&
+                       attn_ragged_applies(g.T, g.dk, g.dv);
+    for (int i = 0; i < m->n_layers_enc && packed_live; ++i) packed_live = m->enc_layers[i].slf_attn.n_head > 1;
+    const bool packed = !(aux && aux->enc_self_attn) && !wide_heads(g.dk, g.dv) && m->n_layers_enc > 0 && !fe &&
+                        (!g.live || packed_live);
     // the label graph: bit-packed rows when the caller provides them (one dword per 32-key tile), else bytes
     const int L = g.L;
     lamp_mask label_mask{LAMP_MASK_NONE, 0, nullptr, 0, 0, nullptr, 0};
@@ -1098,7 +1178,15 @@ static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const Fw
                enc_output + b0 * int64_t(g.T) * g.d, packed, plan_from(w.plan_ints, nb, g.T),
                lamp_mask{LAMP_MASK_KEY_TOKENS_I64, 0, seq, T_in, 0, nullptr, 0}, label_mask};
         p.sp.granules = packed ? w.granules : nullptr;
-        LAMP_CK(packed ? encode_packed(p) : encode_padded(p));
+        lamp_mask enc_mask = p.pad_mask;
+        if (o && o->enc_mask) {
+            enc_mask = *o->enc_mask;
+            enc_mask.ptr = static_cast<const uint8_t*>(enc_mask.ptr) + b0 * enc_mask.stride_b;
+        }
+        if (g.live) enc_mask.flags |= LAMP_MASK_SELF_RAGGED;   // a sample's kernel and key split: its own length, never T
+        p.enc_mask = &enc_mask;
+        p.enc_packs = o ? o->enc_chain_packs : nullptr;
+        LAMP_CK(!packed ? encode_padded(p) : g.live ? encode_packed_live(p) : encode_packed(p));
         if (g.n_ahead)
             LAMP_CK(project_kv_layers(p.xk, int64_t(nb) * g.T, g.d, g.dk, g.dv, m->dec_layers, g.n_ahead, w.K_ahead,
                                       w.V_ahead, s, packed ? p.sp.rows : nullptr, packed ? p.x : nullptr));
@@ -1113,18 +1201,37 @@ size_t lamp_forward_workspace_bytes(const lamp_model* m, int32_t micro_batch, in
     return fwd_size(g).bound(micro_batch);
 }
 
-int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T,
-                 float* logits, float* enc_output, const lamp_aux* aux, void* workspace, size_t workspace_bytes,
-                 lamp_stream_t stream) {
+static int forward_tokens(const lamp_model* m, const lamp_fwd_options* o, const int64_t* src_seq, const int64_t* src_pos,
+                          int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
+                          size_t workspace_bytes, lamp_stream_t stream) {
     FwdDims g;
-    LAMP_CK(check_forward(m, nullptr, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, &g));
+    LAMP_CK(check_forward(m, nullptr, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, &g, o));
     // One launch for every decoder layer's enc-attention K/V projection (they all read the finished encoder output)
     // when the whole batch still fits the workspace with the extra K/V buffers and the weights fit one segment list.
     const bool kv_ahead =
         2 * m->n_layers_dec <= GEMM_MAX_SEG && m->n_layers_dec > 1 && workspace_bytes >= fwd_size(g).bound(size_t(B));
     if (!kv_ahead) g.n_ahead = 0;
     return forward(m, nullptr, g, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes,
-                   hipStream_t(stream));
+                   hipStream_t(stream), o);
+}
+
+int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T,
+                 float* logits, float* enc_output, const lamp_aux* aux, void* workspace, size_t workspace_bytes,
+                 lamp_stream_t stream) {
+    return forward_tokens(m, nullptr, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, stream);
+}
+
+size_t lamp_forward_opts_workspace_bytes(const lamp_model* m, const lamp_fwd_options* opts, int32_t micro_batch, int32_t T,
+                                         int32_t want_attn) {
+    FwdDims g;
+    if (micro_batch <= 0 || fwd_dims(m, nullptr, T, want_attn != 0, &g, opts && opts->enc_self_attn) != 0) return 0;
+    return fwd_size(g).bound(micro_batch);
+}
+
+int lamp_forward_opts(const lamp_model* m, const lamp_fwd_options* opts, const int64_t* src_seq, const int64_t* src_pos,
+                      int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
+                      size_t workspace_bytes, lamp_stream_t stream) {
+    return forward_tokens(m, opts, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------ one-hot genomics encoder (conv.hip)
@@ -1139,9 +1246,27 @@ size_t lamp_onehot_forward_workspace_bytes(const lamp_model* m, const lamp_oneho
 int lamp_onehot_forward(const lamp_model* m, const lamp_onehot_frontend* fe, const int64_t* src_seq, const int64_t* src_pos,
                         int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
                         size_t workspace_bytes, lamp_stream_t stream) {
+    return lamp_onehot_forward_opts(m, fe, nullptr, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes,
+                                    stream);
+}
+
+size_t lamp_onehot_forward_opts_workspace_bytes(const lamp_model* m, const lamp_onehot_frontend* fe, const lamp_fwd_options* opts,
+                                                int32_t micro_batch, int32_t T, int32_t want_attn) {
     FwdDims g;
-    LAMP_CK(check_forward(m, fe, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, &g));
-    return forward(m, fe, g, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, hipStream_t(stream));
+    if (micro_batch <= 0 || onehot_check(m, fe, T) != 0 ||
+        fwd_dims(m, fe, T, want_attn != 0, &g, opts && opts->enc_self_attn) != 0)
+        return 0;
+    return fwd_size(g).bound(micro_batch);
+}
+
+int lamp_onehot_forward_opts(const lamp_model* m, const lamp_onehot_frontend* fe, const lamp_fwd_options* opts,
+                             const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T, float* logits,
+                             float* enc_output, const lamp_aux* aux, void* workspace, size_t workspace_bytes,
+                             lamp_stream_t stream) {
+    FwdDims g;
+    LAMP_CK(check_forward(m, fe, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, &g, opts));
+    return forward(m, fe, g, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, hipStream_t(stream),
+                   opts);
 }
 
 int lamp_conv_pack(const float* w, int32_t c_out, int32_t c_in, int32_t taps, int32_t flip, float* packed,

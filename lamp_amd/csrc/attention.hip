@@ -544,7 +544,10 @@ int launch_attn(const AttnParams& p, hipStream_t s) {
     // at most 256 queries: 16-query blocks on 16x16x4 (attention_small.hip); bit 7 of the tuning hook lifts the limit
     if (sparse)
         rc = launch_attn_sparse(p, s);
-    else if (attn_small_applies(p, (g_force_attn & 0x80) != 0))
+    // self_ragged (the live encoder's padded self-attention): lq is only the padded length, so the 256-query rule would tie a
+    // sample's bits to its batch's padding -- always this kernel, beyond 256 queries too.  Small against attn_kernel / the tile
+    // kernel at 302 x 302 was not measured on its own; the whole live forward moved from 20.7 k to 22.1 k samples/s with it.
+    else if (attn_small_applies(p, (g_force_attn & 0x80) != 0 || p.self_ragged))
         rc = launch_attn_small(p, g_force_attn, s);
     else if (ksplit == 1 && !(g_force_attn & 0x100) && attn_tile_applies(p))   // bit 8 of the tuning hook: attn_kernel instead
         rc = launch_attn_tile(p, s);

@@ -507,7 +507,12 @@ int launch_attn_small(const AttnParams& p_in, int force, hipStream_t s) {
     // workgroups (several query blocks sharing their K / V tiles through L1) measured equal or slower on every shape
     // and exist for the tuning build's every-variant tests only.
     int ksplit = force & 7;
-    if (ksplit != 1 && ksplit != 2 && ksplit != 4) ksplit = nt >= 12 ? 4 : (nt >= 4 ? 2 : 1);
+    if (ksplit != 1 && ksplit != 2 && ksplit != 4) {
+        ksplit = nt >= 12 ? 4 : (nt >= 4 ? 2 : 1);
+        // padded self-attention without per-sample key counts (a per-sample byte mask): lk is the padded length, and a split
+        // chosen from it would tie a sample's bits to its batch's padding
+        if (p.self_ragged && !p.kv_len) ksplit = 1;
+    }
     int qb = (force >> 4) & 7;
     if (qb < 1 || qb > 4) qb = 4 / ksplit;
     (void)nqb;

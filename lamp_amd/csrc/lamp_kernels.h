@@ -68,6 +68,7 @@ struct AttnParams {
     int64_t m_sb, m_sq;
     const int* tiles;      // optional per-32-query-block active key-tile lists (shared masks), or nullptr
     int64_t tiles_stride;
+    int self_ragged;       // lamp_mask.flags & LAMP_MASK_SELF_RAGGED: the kernel choice must not look at lq / lk
     int sparse_rows;       // lamp_mask.flags & LAMP_MASK_SPARSE_ROWS: the shared mask's rows allow few keys, unstructured
     int64_t allowed_pairs; // unblocked entries of that mask (0 = unknown): the FLOPs attention_sparse.hip executes
     // Ragged keys (lamp_forward's enc-dec attention; SeqPlan): sample b has kv_len[b] <= lk keys -- every key past it is a PAD
@@ -89,7 +90,7 @@ bool slab_applies(int64_t M, int N, int K, int nseg, const float* const* Wq);
 int launch_slab_gemm(const GemmParams& p, const float* const* Wq, hipStream_t s);
 int launch_attn(const AttnParams& p, hipStream_t s);
 int launch_attn_general(const AttnParams& p, hipStream_t s);  // any d_k / d_v: scores through memory
-bool attn_small_applies(const AttnParams& p, bool any_lq = false);  // attention_small.hip: lq <= 256 or lk <= 64 (shape-only rule)
+bool attn_small_applies(const AttnParams& p, bool any_lq = false);  // attention_small.hip: lq <= 256 or lk <= 64 (shape-only rule); any_lq: every lq (LAMP_MASK_SELF_RAGGED, the tuning hook)
 int launch_attn_small(const AttnParams& p, int force_ksplit, hipStream_t s);
 // attention_tile.hip: long key sequences, K / V tiles shared by a workgroup through LDS-DMA; the bits of attn_kernel<128, 1, 0, MK>
 bool attn_tile_applies(const AttnParams& p);
@@ -140,6 +141,14 @@ struct SeqPlan {
 };
 int launch_seq_plan(const int64_t* seq, const int64_t* pos, int nb, int T, int64_t seq_stride, bool packed,
                     const SeqPlan& sp, hipStream_t s);
+// attention_ragged.hip: the live encoder on the packed rows with ONE PAD row per sample (row n_tok + b).  launch_pad_rows writes
+// those rows and the live row count n_tok + nb; launch_attn_ragged_self is the self-attention whose queries are as ragged as
+// its keys; launch_scatter_rows writes the padded [nb, T, d] encoder output (and returns the plan's granules to "no epoch").
+bool attn_ragged_applies(int T, int dk, int dv);
+int launch_pad_rows(const float* emb, const float* pos_table, int d, int nb, const SeqPlan& sp, float* x, int* count, hipStream_t s);
+int launch_attn_ragged_self(const float* Q, const float* K, const float* V, float* O, int nb, int H, int T, int dk, int dv,
+                            const SeqPlan& sp, hipStream_t s);
+int launch_scatter_rows(const float* x, int d, int nb, int T, const SeqPlan& sp, float* y, hipStream_t s);
 // The first encoder layer's W1 folded into the embedding tables (lamp_model::enc0_emb_w1 / enc0_pos_w1): the gather kernels then
 // also write that layer's hidden rows, hid[row] = relu(e1[tok] (+ p1[pos])), beside the embedded rows.  hid == nullptr: off.
 struct EmbedFold {

@@ -54,6 +54,9 @@ def parse(argv=None):
     ap.add_argument('-no_dec_self_att', action='store_true')
     ap.add_argument('-no_enc_pos_embedding', action='store_true')
     ap.add_argument('-br_threshold', type=float, default=0.5)
+    ap.add_argument('-enc_self_att', action='store_true',
+                    help="the encoder's self-attention is live (LAMP(enc_self_attn=True)); a run_train checkpoint brings the flag "
+                         "in its settings, this is for bare state dicts")
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4],
                     help='batches in flight (HIP streams); 4 measured best: 36.6 k / 43.3 k / 46.2 k samples/s with 1 / 2 / 4 on a '
                          'reuters-sized split (tools/bench_eval_epoch.py)')
@@ -112,8 +115,16 @@ def load_checkpoint_state(path):
     """state_dict of a reference checkpoint ({'model': state_dict, ...} or a bare state_dict).  Hosts with more than
     one GPU save from inside nn.DataParallel (main.py:106-108 before utils.save_model): `module.`-prefixed keys, which
     LAMP.load_state_dict strips."""
+    return load_checkpoint(path)[0]
+
+
+def load_checkpoint(path):
+    """(state_dict, enc_self_att) of a checkpoint: the flag is run_train's `-enc_self_att` as stored in the checkpoint's
+    'settings'; a checkpoint without the setting (the reference's, a bare state_dict) has it off."""
     ckpt = torch.load(path, map_location='cpu', weights_only=False)
-    return ckpt['model'] if isinstance(ckpt, dict) and 'model' in ckpt else ckpt
+    if isinstance(ckpt, dict) and 'model' in ckpt:
+        return ckpt['model'], bool(getattr(ckpt.get('settings'), 'enc_self_att', False))
+    return ckpt, False
 
 
 def spawn_ranks(n, argv):
@@ -168,13 +179,15 @@ def main(argv=None):
            if opt.label_mask == 'prior' else None)
     d, h = opt.d_model, opt.n_head
     torch.manual_seed(opt.seed)
+    state, live = load_checkpoint(opt.checkpoint) if opt.checkpoint else (None, False)
+    live = live or opt.enc_self_att
     model = LAMP(n_src, n_labels, data['settings'].max_seq_len, n_labels, n_layers_enc=opt.n_layers_enc,
                  n_layers_dec=opt.n_layers_dec, n_head=h, n_head2=opt.n_head2, d_word_vec=d, d_model=d,
                  d_inner_hid=opt.d_inner_hid, d_k=d // h, d_v=d // h, encoder='graph', decoder='graph',
                  no_enc_pos_embedding=opt.no_enc_pos_embedding, no_dec_self_att=opt.no_dec_self_att,
-                 label_adj_matrix=adj, label_mask=opt.label_mask, dec_dropout2=False, onehot=opt.onehot)
-    if opt.checkpoint:
-        model.load_state_dict(load_checkpoint_state(opt.checkpoint))
+                 label_adj_matrix=adj, label_mask=opt.label_mask, dec_dropout2=False, onehot=opt.onehot, enc_self_attn=live)
+    if state is not None:
+        model.load_state_dict(state)
     model = model.to(device).eval()
     split = data[opt.split]
     batches = D.EvalBatcher(split['src'], split['tgt'], opt.batch_size)

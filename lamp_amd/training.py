@@ -581,11 +581,13 @@ def sdpa_train(mod, q, k, v, attn_mask):
     return _SDPAFn.apply(q, k, v, attn_mask, 1.0 / float(mod.temperature), float(mod.dropout.p), seed)
 
 
-def forward_train(model, src_seq, src_pos, return_attns=False, int_preds=False):
+def forward_train(model, src_seq, src_pos, return_attns=False, int_preds=False, adj=None):
     """LAMP.forward (lamp/Models.py:110-137) in training mode, attached to the autograd graph; same return tuples as
     the reference: (logits, enc_output, None) | (..., intermediate_preds) | (..., [enc_attns], [slf_attns, enc_dec]).
     The encoder self-attention is skipped unless its maps are requested: the reference discards its output
-    (lamp/Layers.py:16-18), so its parameters receive no gradient there either.  Intermediate predictions read out
+    (lamp/Layers.py:16-18), so its parameters receive no gradient there either.  With ``LAMP(enc_self_attn=True)`` the
+    block is live -- x <- slf_attn(x, x, x) under the key-padding mask, or under ``adj`` (lamp/Encoders.py:85-89), before
+    pos_ffn -- and its parameters receive gradients through _MHAFn like the decoder's.  Intermediate predictions read out
     through a detached copy of the projection, as the reference does (lamp/Models.py:129-132)."""
     enc, dec = model.encoder, model.decoder
     seq = src_seq.long().contiguous()
@@ -601,8 +603,20 @@ def forward_train(model, src_seq, src_pos, return_attns=False, int_preds=False):
     if not getattr(enc, 'onehot', False):
         x = _EmbedFn.apply(seq, pos, enc.src_word_emb.weight, pos_w)
     enc_attns = []
+    live = bool(getattr(enc, 'enc_self_attn', False))
+    enc_mask, enc_keep = pad_mask, keep
+    if live and adj:
+        from .Encoders import adj_attn_mask
+        enc_mask, enc_keep = N.make_mask(adj_attn_mask(seq, adj), B, T, T)
+    if live:   # (a copy: the decoder's enc-attention keeps the plain key-padding mask)
+        enc_mask = N.Mask(enc_mask.kind, enc_mask.flags | N.LAMP_MASK_SELF_RAGGED, enc_mask.ptr, enc_mask.stride_b,
+                          enc_mask.stride_q, None, 0, 0)
     for layer in enc.layer_stack:
-        if return_attns:
+        if live:
+            x, a = mha_train(layer.slf_attn, x, x, enc_mask, enc_keep, seeds)
+            if return_attns:
+                enc_attns.append(a)
+        elif return_attns:
             enc_attns.append(mha_train(layer.slf_attn, x, x, pad_mask, keep, seeds)[1])
         x = ffn_train(layer.pos_ffn, x, seeds)
     y = _LabelRowsFn.apply(dec.tgt_word_emb.weight, B)
