@@ -247,6 +247,30 @@ int lamp_sdpa_fwd_fast_maps(const float* q, const float* k, const float* v, floa
                             float inv_temperature, const lamp_mask* mask, const lamp_attn_layout* layout,
                             lamp_stream_t stream);
 
+/* The activation of an attention block (the reference's attn_type, lamp/SubLayers.py:17-25, config_args.py:49). */
+#define LAMP_ATTN_SOFTMAX 0
+#define LAMP_ATTN_SIGMOID 1
+
+/* lamp_sdpa_fwd with the activation as an argument.  act == LAMP_ATTN_SOFTMAX: lamp_sdpa_fwd itself, bit for bit.
+ * act == LAMP_ATTN_SIGMOID -- ScaledDotProductAttention(attn_type='sigmoid'), lamp/SubLayers.py:17-25,39:
+ *   S = (Q K^T) * inv_temperature ; P = sigmoid(S), P[blocked] = sigmoid(-inf) = 0 exactly ; O = P V
+ * There is no row normalisation: a fully blocked row is 0 in O and P, not NaN.  `attn` (nullable) receives P in the same
+ * single pass; out and v may both be NULL with attn given (maps only).  d_k, d_v multiples of 4 (else LAMP_E_UNSUPPORTED); up
+ * to 128 one fused kernel serves every shape, beyond that the general three-launch path with the scores in `attn` (required
+ * then).  Any other act: LAMP_E_UNSUPPORTED. */
+int lamp_sdpa_act_fwd(const float* q, const float* k, const float* v, float* out, float* attn,
+                      int32_t B, int32_t H, int32_t lq, int32_t lk, int32_t d_k, int32_t d_v,
+                      float inv_temperature, int32_t act, const lamp_mask* mask, const lamp_attn_layout* layout,
+                      lamp_stream_t stream);
+
+/* lamp_mha_fwd with the activation of its attention as an argument (MultiHeadAttention(attn_type=...), lamp/SubLayers.py:
+ * 65-75): act == LAMP_ATTN_SOFTMAX is lamp_mha_fwd, bit for bit; LAMP_ATTN_SIGMOID computes P = sigmoid(S) with blocked
+ * entries exactly 0 (a fully blocked row contributes 0, not NaN) as lamp_sdpa_act_fwd does.  Same workspace. */
+int lamp_mha_act_fwd(const float* xq, const float* xkv, int32_t B, int32_t lq, int32_t lk,
+                     int32_t d_model, int32_t d_k, int32_t d_v, const lamp_mha_weights* w, int32_t act,
+                     const lamp_mask* mask, float* out, float* attn,
+                     void* workspace, size_t workspace_bytes, lamp_stream_t stream);
+
 /* MultiHeadAttention.forward (lamp/SubLayers.py:77-121), eval mode:
  *   out = LayerNorm( concat_heads(SDPA(xq Wq^T, xkv Wk^T, xkv Wv^T)) Wfc^T + xq )
  * xq [B, lq, d_model], xkv [B, lk, d_model] (may alias xq), out [B, lq, d_model];
@@ -407,6 +431,20 @@ int lamp_mha_bwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, const 
                  void* workspace, size_t workspace_bytes, void* partials, size_t partials_bytes, lamp_reduce_job* job,
                  lamp_stream_t stream);
 
+/* lamp_mha_train_fwd / lamp_mha_bwd with the activation as an argument (lamp/SubLayers.py:17-25,39-41).  LAMP_ATTN_SOFTMAX: the
+ * functions above, bit for bit.  LAMP_ATTN_SIGMOID: P = sigmoid(S) with blocked entries exactly 0 (a fully blocked row is 0, not
+ * NaN), written in the attention's single pass -- lse is unused and may be NULL; the backward's score gradient is
+ * dS = inv_temperature * P * (1 - P) * dP, elementwise (lamp_sigmoid_attn_bwd).  Every other buffer as above. */
+int lamp_mha_train_act_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, int32_t act, const float* xq,
+                           const float* xk, const float* xv, const lamp_mask* mask, float* q, float* k, float* v, float* a,
+                           float* P, float* Pd, float* lse, float* o, float* y, lamp_stream_t stream);
+int lamp_mha_act_bwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, int32_t act, const float* xq, const float* xk,
+                     const float* xv, const float* q, const float* k, const float* v, const float* a, const float* P,
+                     const float* Pd, const float* o, const float* dy, float* dxq, float* d_o, float* da, float* dP, float* dq,
+                     float* dk, float* dv, float* dxk, float* dxv, float* dgamma, float* dbeta, float* dwq, float* dwk,
+                     float* dwv, float* dfc, void* workspace, size_t workspace_bytes, void* partials, size_t partials_bytes,
+                     lamp_reduce_job* job, lamp_stream_t stream);
+
 /* y = LayerNorm(dropout(x) + residual[row % residual_rows]) (residual nullable; residual_rows 0 = one residual row
  * per x row): the dropout, add & norm that closes every sub-layer (lamp/SubLayers.py:113-115,138-140), with neither
  * the dropped tensor nor the sum ever stored.  dropout_p = 0: plain add & norm; otherwise lamp_dropout's counter-based
@@ -442,6 +480,14 @@ int lamp_dropout(const float* x, int64_t n, float p, uint32_t seed, float* y, la
 /* Softmax backward per row of length lk: dS = scale * P * (dP - sum_k P * dP); dS may alias dP. */
 int lamp_softmax_bwd(const float* P, const float* dP, int64_t rows, int32_t lk, float scale, float* dS,
                      lamp_stream_t stream);
+
+/* Backward of the sigmoid attention's activation (lamp/SubLayers.py:17-25,39), elementwise over rows * lk entries:
+ *   dS = scale * P * (1 - P) * dropout_backward(dP)
+ * P = 0 on blocked entries keeps their gradient at exactly 0 (no NaN anywhere).  dropout_p > 0: dP is the gradient of
+ * dropout(P) and lamp_dropout's mask for (`seed`, element index = row * lk + column) is applied on load; 0: dP as it is.
+ * dS may alias dP. */
+int lamp_sigmoid_attn_bwd(const float* P, const float* dP, int64_t rows, int32_t lk, float scale, float dropout_p,
+                          uint32_t seed, float* dS, lamp_stream_t stream);
 
 /* Backward of lamp_diag_logits_fwd: dy[b,i,:] = dlogits[b,i] * w_out[i,:], dw[i,:] = sum_b dlogits[b,i] * y[b,i,:]. */
 int lamp_diag_logits_bwd(const float* y, const float* w_out, const float* dlogits, int32_t B, int32_t L,
@@ -495,9 +541,17 @@ int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src
                                       layout as without the flag.  Same definition, other kernel: results agree within rounding,
                                       not bit for bit, with the padded route; a sample's bits do not depend on T or B either way. */
 
+#define LAMP_FWD_DEC_SIGMOID 2     /* lamp_fwd_options.flags: BOTH attention blocks of every decoder layer (lamp/Layers.py:35,40) run
+                                      sigmoid attention -- P = sigmoid(Q K^T / temperature), blocked entries exactly 0, no row
+                                      normalisation (lamp/SubLayers.py:17-25,39); a label without one allowed neighbour receives 0,
+                                      not NaN.  The reference accepts attn_type and never hands it to its layers (lamp/Layers.py:
+                                      23-30): this is the opt-in that does what the flag says.  The encoder, dead or live, stays
+                                      softmax (the reference never gives it an attn_type); aux maps of the decoder are the sigmoid
+                                      maps.  Micro-batching and the bit-for-bit independence from B, T and the split hold. */
+
 typedef struct lamp_fwd_options {
     int32_t enc_self_attn;
-    int32_t flags;               /* LAMP_FWD_PACKED_ENCODER or 0 */
+    int32_t flags;               /* LAMP_FWD_PACKED_ENCODER | LAMP_FWD_DEC_SIGMOID, or 0 */
     const lamp_mask* enc_mask;
     const lamp_chain_pack* enc_chain_packs;
 } lamp_fwd_options;

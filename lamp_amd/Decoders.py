@@ -37,8 +37,9 @@ class GraphDecoder(nn.Module):
     def __init__(self, n_tgt_vocab, n_max_seq, n_layers=6, n_head=8, n_head2=8, d_k=64, d_v=64,
                  d_word_vec=512, d_model=512, d_inner_hid=1024, dropout=0.1, dropout2=0.1,
                  no_dec_self_att=False, label_adj_matrix=None, label_mask=None, enc_vec=True,
-                 graph_conv=False, attn_type='softmax'):
+                 graph_conv=False, attn_type='softmax', dec_attn_type=None):
         super().__init__()
+        self.dec_attn_type = dec_attn_type   # None: softmax, whatever attn_type says (as the reference); 'sigmoid': see DecoderLayer
         self.enc_vec = enc_vec   # the encoder hands over ONE vector per sample (mlp / enc_transform): no key-padding mask
         self.dropout = nn.Dropout(dropout)
         self.constant_input = torch.from_numpy(np.arange(n_tgt_vocab)).view(-1, 1)
@@ -72,7 +73,7 @@ class GraphDecoder(nn.Module):
                                       self.label_allowed_pairs <= self.SPARSE_ROWS_MAX_DENSITY * blocked.numel())
         self.layer_stack = nn.ModuleList(
             DecoderLayer(d_model, d_inner_hid, n_head, n_head2, d_k, d_v, dropout=dropout, dropout2=dropout2,
-                         no_dec_self_att=no_dec_self_att, attn_type=attn_type) for _ in range(n_layers))
+                         no_dec_self_att=no_dec_self_att, attn_type=attn_type, dec_attn_type=dec_attn_type) for _ in range(n_layers))
 
     def label_mask_struct(self):
         m = self.label_mask_u8

@@ -34,15 +34,17 @@ class EncoderLayer(nn.Module):
 class DecoderLayer(nn.Module):
     """Label-state update: input->label attention, FFN, label->label attention over the label graph,
     FFN (reference: lamp/Layers.py:22-48).  ``attn_type`` / ``ffn`` are accepted and unused, as in
-    the reference."""
+    the reference.  ``dec_attn_type`` is this project's opt-in that does what the flag says: 'sigmoid' makes
+    BOTH attention blocks sigmoid attention (SubLayers.ScaledDotProductAttention); None = the reference's softmax."""
 
     def __init__(self, d_model, d_inner_hid, n_head, n_head2, d_k, d_v, dropout=0.1, dropout2=False,
-                 no_dec_self_att=False, ffn=True, attn_type='softmax'):
+                 no_dec_self_att=False, ffn=True, attn_type='softmax', dec_attn_type=None):
         super().__init__()
-        self.enc_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
+        act = 'softmax' if dec_attn_type is None else dec_attn_type
+        self.enc_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout, attn_type=act)
         self.pos_ffn1 = PositionwiseFeedForward(d_model, d_inner_hid, dropout=dropout)
         if not no_dec_self_att:
-            self.slf_attn = MultiHeadAttention(n_head2, d_model, d_k, d_v, dropout=dropout, dropout2=dropout2)
+            self.slf_attn = MultiHeadAttention(n_head2, d_model, d_k, d_v, dropout=dropout, dropout2=dropout2, attn_type=act)
         self.pos_ffn2 = PositionwiseFeedForward(d_model, d_inner_hid, dropout=dropout)
 
     def forward(self, dec_input, enc_output, slf_attn_mask=None, dec_enc_attn_mask=None, need_attn=True):

@@ -10,6 +10,12 @@ model, which the reference's code computes and then overwrites -- its ``w_qs / w
 there.  It is this project's own switch (last keyword, default off: every reference call constructs the reference's model),
 served by ``lamp_forward_opts`` in eval and by lamp_amd/training.py in training; parameters and ``state_dict`` are the same in
 both modes.
+
+``dec_attn_type='sigmoid'`` makes both attention blocks of every decoder layer sigmoid attention (lamp/SubLayers.py:17-25):
+the reference accepts ``attn_type`` and never hands it to its layers (lamp/Layers.py:23-30), so ``attn_type`` stays accepted
+and ignored here too, and this second project-own keyword (keyword-only in practice: it sits behind the reference's last argument, in front of
+``enc_self_attn``) is the opt-in that does what the flag says (``lamp_forward_opts``
+with LAMP_FWD_DEC_SIGMOID in eval, lamp_amd/training.py in training).  The encoder stays softmax; ``state_dict`` is unchanged.
 """
 import ctypes as C
 
@@ -43,8 +49,13 @@ class LAMP(nn.Module):
                  embs_share_weight=True, encoder='selfatt', decoder='sa_m', enc_transform='', onehot=False,
                  no_enc_pos_embedding=False, no_dec_self_att=False, loss='ce', label_adj_matrix=None,
                  label_mask=None, matching_mlp=False, graph_conv=False, attn_type='softmax', int_preds=False,
-                 enc_self_attn=False):
+                 dec_attn_type=None, enc_self_attn=False):
         super().__init__()
+        if dec_attn_type is not None and decoder != 'graph':
+            raise NotImplementedError('dec_attn_type belongs to the graph decoder, not to decoder=%r' % (decoder,))
+        if dec_attn_type is not None and dec_attn_type not in N.ATTN_TYPES:
+            raise NotImplementedError("dec_attn_type=%r: None, 'softmax' or 'sigmoid'" % (dec_attn_type,))
+        self.dec_attn_type = dec_attn_type
         if enc_self_attn and encoder != 'graph':
             raise NotImplementedError('enc_self_attn=True belongs to the graph encoder, not to encoder=%r' % (encoder,))
         self.enc_self_attn = bool(enc_self_attn)
@@ -77,7 +88,7 @@ class LAMP(nn.Module):
                 d_word_vec=d_word_vec, d_model=d_model, d_k=d_k, d_v=d_v, d_inner_hid=d_inner_hid,
                 dropout=dec_dropout, dropout2=dec_dropout2, no_dec_self_att=no_dec_self_att,
                 label_adj_matrix=label_adj_matrix, label_mask=label_mask, enc_vec=self.enc_vec,
-                graph_conv=graph_conv, attn_type=attn_type)
+                graph_conv=graph_conv, attn_type=attn_type, dec_attn_type=dec_attn_type)
         elif decoder == 'mlp':
             self.decoder = MLPDecoder(
                 n_tgt_vocab, n_max_seq_e, n_max_seq_d, n_layers=n_layers_dec, n_head=n_head, d_word_vec=d_word_vec,
@@ -429,6 +440,10 @@ class LAMP(nn.Module):
                 mstruct = N.Mask(N.LAMP_MASK_U8, 0, m8.data_ptr(), T * T, T, None, 0, 0)
                 keep += [m8, mstruct]
                 opts.enc_mask = C.pointer(mstruct)
+        if self.dec_attn_type == 'sigmoid':   # both decoder attention blocks: sigmoid attention (LAMP_FWD_DEC_SIGMOID)
+            if opts is None:
+                opts = N.FwdOptions(0, 0, None, None)
+            opts.flags |= N.LAMP_FWD_DEC_SIGMOID
         if opts is not None and fe is not None:
             def ws_bytes(mb):
                 return lib.lamp_onehot_forward_opts_workspace_bytes(C.byref(model), C.byref(fe), C.byref(opts), mb, T_in,

@@ -32,27 +32,29 @@ class XavierLinear(nn.Module):
 
 
 class ScaledDotProductAttention(nn.Module):
-    """softmax(mask(q k^T / temperature)) v on head-major batches (reference: lamp/SubLayers.py:16-43).
+    """act(mask(q k^T / temperature)) v on head-major batches (reference: lamp/SubLayers.py:16-43).
 
-    ``attn_type`` is accepted like in the reference; anything but 'softmax' is never reached by the
-    reference's own call sites and is rejected here.  ``need_attn=False`` skips the
-    write-out of the (N, lq, lk) probability tensor and returns ``None`` in its place.
+    ``attn_type`` is 'softmax' or 'sigmoid' as in the reference (lamp/SubLayers.py:17-25): sigmoid gates every key on its
+    own -- blocked entries are sigmoid(-inf) = 0, there is no row normalisation, and a row without one allowed key is 0, not
+    NaN (csrc/attention_sigmoid.hip).  Any other string raises.  ``need_attn=False`` skips the write-out of the (N, lq, lk)
+    probability tensor and returns ``None`` in its place.
     """
 
     def __init__(self, temperature, dropout=0.1, attn_type='softmax'):
         super().__init__()
         self.temperature = temperature
         self.dropout = nn.Dropout(dropout)  # identity in eval mode; kept for module-tree parity
-        if attn_type != 'softmax':
-            raise NotImplementedError("attn_type=%r: only 'softmax' is on the path" % (attn_type,))
-        self.attn_type = nn.Softmax(dim=2)
+        if attn_type not in N.ATTN_TYPES:
+            raise NotImplementedError("attn_type=%r: 'softmax' and 'sigmoid' are on the path" % (attn_type,))
+        self.attn_type = nn.Softmax(dim=2) if attn_type == 'softmax' else nn.Sigmoid()   # module-tree parity (no parameters)
+        self.act = N.ATTN_TYPES[attn_type]
         self.need_attn = True
 
     def forward(self, q, k, v, attn_mask=None, stop_sig=False):
         if self.training:
             from . import training
             return training.sdpa_train(self, q, k, v, attn_mask)
-        return N.sdpa(q, k, v, attn_mask, 1.0 / float(self.temperature), need_attn=self.need_attn)
+        return N.sdpa(q, k, v, attn_mask, 1.0 / float(self.temperature), need_attn=self.need_attn, act=self.act)
 
 
 class MultiHeadAttention(nn.Module):
@@ -96,7 +98,7 @@ class MultiHeadAttention(nn.Module):
             N.require_device(q, k, v)
             return training.mha_train(self, q, k, mstruct, keep, training._Seeds(), xv=None if same_kv else v)
         if same_kv:
-            out, attn = N.mha(q, k, N.mha_weights(self), self.d_k, self.d_v, mstruct, self.need_attn)
+            out, attn = N.mha(q, k, N.mha_weights(self), self.d_k, self.d_v, mstruct, self.need_attn, act=self.attention.act)
             del keep
             return out, attn
         # Distinct key and value sources (lamp/SubLayers.py:77-93 projects them independently; no layer of the reference
@@ -105,7 +107,7 @@ class MultiHeadAttention(nn.Module):
         N.require_device(q, k, v)
         H = self.n_head
         a, attn = N.sdpa_fused(N.linear(q, self.w_qs.weight), N.linear(k, self.w_ks.weight), N.linear(v, self.w_vs.weight),
-                               H, mstruct, 1.0 / float(self.d_k) ** 0.5, need_attn=self.need_attn)
+                               H, mstruct, 1.0 / float(self.d_k) ** 0.5, need_attn=self.need_attn, act=self.attention.act)
         del keep
         if H > 1:
             o = N.linear(a, self.fc.weight, residual=q)

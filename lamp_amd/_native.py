@@ -18,7 +18,9 @@ TUNING_LIB_PATH = os.path.join(_HERE, 'liblamp_hip_tuning.so')
 ABI_VERSION = 5
 LAMP_MASK_NONE, LAMP_MASK_U8, LAMP_MASK_KEY_TOKENS_I64, LAMP_MASK_BITS_U32 = 0, 1, 2, 3
 LAMP_MASK_SPARSE_ROWS, LAMP_MASK_SELF_RAGGED = 1, 2   # lamp_mask.flags (include/lamp_hip.h)
-LAMP_FWD_PACKED_ENCODER = 1                            # lamp_fwd_options.flags
+LAMP_FWD_PACKED_ENCODER, LAMP_FWD_DEC_SIGMOID = 1, 2   # lamp_fwd_options.flags
+LAMP_ATTN_SOFTMAX, LAMP_ATTN_SIGMOID = 0, 1            # the activation of an attention block (attn_type)
+ATTN_TYPES = {'softmax': LAMP_ATTN_SOFTMAX, 'sigmoid': LAMP_ATTN_SIGMOID}
 K_EMBED, K_GEMM, K_ATTN, K_LAYERNORM, K_DIAG, K_COUNT = 0, 1, 2, 3, 4, 5
 KERNEL_CLASS_NAMES = ('embed', 'gemm', 'attention', 'layernorm', 'diag_readout')
 
@@ -193,6 +195,15 @@ PROTOTYPES = {
     'lamp_embed_bwd_ordered': (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i64, _vp, _vp]),
     'lamp_bce_logits_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
     'lamp_optim_step': (C.c_int, [C.POINTER(OptimEntry), _i32, _i32, _i64] + [C.c_double] * 4 + [_vp]),
+    'lamp_sdpa_act_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _i32,
+                                    C.POINTER(Mask), C.POINTER(AttnLayout), _vp]),
+    'lamp_mha_act_fwd': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(MhaWeights), _i32,
+                                   C.POINTER(Mask), _vp, _vp, _vp, _sz, _vp]),
+    'lamp_mha_train_act_fwd': (C.c_int, [C.POINTER(MhaTrainDesc), C.POINTER(MhaWeights), _i32, _vp, _vp, _vp, C.POINTER(Mask)] +
+                               [_vp] * 9 + [_vp]),
+    'lamp_mha_act_bwd': (C.c_int, [C.POINTER(MhaTrainDesc), C.POINTER(MhaWeights), _i32] + [_vp] * 11 + [_vp] * 15 +
+                         [_vp, _sz, _vp, _sz, C.POINTER(ReduceJob), _vp]),
+    'lamp_sigmoid_attn_bwd': (C.c_int, [_vp, _vp, _i64, _i32, _f, _f, C.c_uint32, _vp, _vp]),
     'lamp_prof_enable': (C.c_int, [_i32]),
     'lamp_prof_reset': (C.c_int, []),
     'lamp_prof_read': (C.c_int, [_i32, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -383,8 +394,9 @@ def layernorm(x, gamma, beta, eps=1e-5):
     return out.view(x.shape)
 
 
-def sdpa(q, k, v, mask, inv_temperature, need_attn=True, _lib=None):
-    """q (N, lq, dk), k (N, lk, dk), v (N, lk, dv) head-major batches as in the reference."""
+def sdpa(q, k, v, mask, inv_temperature, need_attn=True, _lib=None, act=LAMP_ATTN_SOFTMAX):
+    """q (N, lq, dk), k (N, lk, dk), v (N, lk, dv) head-major batches as in the reference.  act: LAMP_ATTN_SIGMOID for
+    P = sigmoid(scores) with blocked entries exactly 0 (lamp_sdpa_act_fwd)."""
     require_device(q, k, v)
     q, k, v = f32c(q), f32c(k), f32c(v)
     N, lq, dk = q.shape
@@ -394,6 +406,13 @@ def sdpa(q, k, v, mask, inv_temperature, need_attn=True, _lib=None):
     attn = torch.empty((N, lq, lk), dtype=torch.float32, device=q.device) if (need_attn or wide) else None
     mstruct, keep = make_mask(mask, N, lq, lk)
     lay = AttnLayout(lq * dk, 0, dk, lk * dk, 0, dk, lk * dv, 0, dv, lq * dv, 0, dv)
+    if act != LAMP_ATTN_SOFTMAX:
+        check((_lib or lib()).lamp_sdpa_act_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), N, 1, lq, lk, dk, dv,
+                                                float(inv_temperature), int(act),
+                                                C.byref(mstruct) if mstruct is not None else None, C.byref(lay), stream()),
+              'lamp_sdpa_act_fwd')
+        del keep
+        return out, (attn if need_attn else None)
     check((_lib or lib()).lamp_sdpa_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), N, 1, lq, lk, dk, dv,
                               float(inv_temperature), C.byref(mstruct) if mstruct is not None else None,
                               C.byref(lay), stream()), 'lamp_sdpa_fwd')
@@ -401,7 +420,7 @@ def sdpa(q, k, v, mask, inv_temperature, need_attn=True, _lib=None):
     return out, (attn if need_attn else None)
 
 
-def sdpa_fused(q, k, v, n_head, mask_struct, inv_temperature, need_attn=True, fast_maps=False):
+def sdpa_fused(q, k, v, n_head, mask_struct, inv_temperature, need_attn=True, fast_maps=False, act=LAMP_ATTN_SOFTMAX):
     """Attention on head-fused projections: q (B, lq, H*dk), k (B, lk, H*dk), v (B, lk, H*dv) ->
     out (B, lq, H*dv), attn (H*B, lq, lk) [index head*B + b] or None.  No head split/merge copies: the
     kernel walks the heads through lamp_attn_layout strides.  fast_maps: single-pass map write-out
@@ -416,6 +435,10 @@ def sdpa_fused(q, k, v, n_head, mask_struct, inv_temperature, need_attn=True, fa
     attn = torch.empty((H * B, lq, lk), dtype=torch.float32, device=q.device) if (need_attn or wide) else None
     lay = AttnLayout(lq * H * dk, dk, H * dk, lk * H * dk, dk, H * dk, lk * H * dv, dv, H * dv, lq * H * dv, dv, H * dv)
     m = C.byref(mask_struct) if mask_struct is not None else None
+    if act != LAMP_ATTN_SOFTMAX:   # the sigmoid kernel writes its maps in the same single pass: no lse, no fast / exact split
+        check(lib().lamp_sdpa_act_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), B, H, lq, lk, dk, dv,
+                                      float(inv_temperature), int(act), m, C.byref(lay), stream()), 'lamp_sdpa_act_fwd')
+        return out, (attn if need_attn else None)
     if fast_maps and need_attn:
         lse = torch.empty((H * B * lq,), dtype=torch.float32, device=q.device)
         check(lib().lamp_sdpa_fwd_fast_maps(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), ptr(lse), B, H, lq, lk, dk, dv,
@@ -439,7 +462,7 @@ def ffn_weights(mod):
                       ptr(mod.layer_norm.weight), ptr(mod.layer_norm.bias))
 
 
-def mha(xq, xkv, weights, d_k, d_v, mask_struct, need_attn):
+def mha(xq, xkv, weights, d_k, d_v, mask_struct, need_attn, act=LAMP_ATTN_SOFTMAX):
     require_device(xq, xkv)
     xq, xkv = f32c(xq), f32c(xkv)
     B, lq, d = xq.shape
@@ -449,8 +472,12 @@ def mha(xq, xkv, weights, d_k, d_v, mask_struct, need_attn):
     attn = torch.empty((h * B, lq, lk), dtype=torch.float32, device=xq.device) if need_attn else None
     nbytes = lib().lamp_mha_workspace_bytes(B, lq, lk, d, h, d_k, d_v)
     ws = workspace(nbytes, xq.device)
-    check(lib().lamp_mha_fwd(ptr(xq), ptr(xkv), B, lq, lk, d, d_k, d_v, C.byref(weights),
-                             C.byref(mask_struct) if mask_struct is not None else None, ptr(out), ptr(attn),
+    m = C.byref(mask_struct) if mask_struct is not None else None
+    if act != LAMP_ATTN_SOFTMAX:
+        check(lib().lamp_mha_act_fwd(ptr(xq), ptr(xkv), B, lq, lk, d, d_k, d_v, C.byref(weights), int(act), m, ptr(out),
+                                     ptr(attn), ptr(ws), ws.numel(), stream()), 'lamp_mha_act_fwd')
+        return out, attn
+    check(lib().lamp_mha_fwd(ptr(xq), ptr(xkv), B, lq, lk, d, d_k, d_v, C.byref(weights), m, ptr(out), ptr(attn),
                              ptr(ws), ws.numel(), stream()), 'lamp_mha_fwd')
     return out, attn
 
@@ -688,8 +715,8 @@ def ffn_bwd(x2, h, o, dy, w1, w2, ln_g, p, seed, want_dw1, want_dw2, defer_reduc
     return dx, (d_o if d_o is not None else dx), dh, dW1, dW2, db1, db2, dg, db, pending
 
 
-def mha_train_fwd(desc, xq, xk, xv, wq, wk, wv, fc, ln_g, ln_b, mask_struct):
-    """lamp_mha_train_fwd -> (q, k, v, a, P, Pd | None, o | None, y)."""
+def mha_train_fwd(desc, xq, xk, xv, wq, wk, wv, fc, ln_g, ln_b, mask_struct, act=LAMP_ATTN_SOFTMAX):
+    """lamp_mha_train_fwd (lamp_mha_train_act_fwd for another activation) -> (q, k, v, a, P, Pd | None, o | None, y)."""
     B, lq, lk, d, H, dk, dv = desc.B, desc.lq, desc.lk, desc.d_model, desc.n_head, desc.d_k, desc.d_v
     dev = xq.device
     e = torch.empty
@@ -704,6 +731,11 @@ def mha_train_fwd(desc, xq, xk, xv, wq, wk, wv, fc, ln_g, ln_b, mask_struct):
     y = e((B, lq, d), dtype=torch.float32, device=dev)
     wts = MhaWeights(_dp(wq), _dp(wk), _dp(wv), _dp(fc), _dp(ln_g), _dp(ln_b), H, 1)
     m = C.byref(mask_struct) if mask_struct is not None else None
+    if act != LAMP_ATTN_SOFTMAX:
+        check(lib().lamp_mha_train_act_fwd(C.byref(desc), C.byref(wts), int(act), _dp(xq), _dp(xk), _dp(xv), m, q.data_ptr(),
+                                           k.data_ptr(), v.data_ptr(), a.data_ptr(), P.data_ptr(), _dp(Pd), lse.data_ptr(),
+                                           _dp(o), y.data_ptr(), stream()), 'lamp_mha_train_act_fwd')
+        return q, k, v, a, P, Pd, o, y
     check(lib().lamp_mha_train_fwd(C.byref(desc), C.byref(wts), _dp(xq), _dp(xk), _dp(xv), m, q.data_ptr(), k.data_ptr(),
                                    v.data_ptr(), a.data_ptr(), P.data_ptr(), _dp(Pd), lse.data_ptr(), _dp(o), y.data_ptr(),
                                    stream()), 'lamp_mha_train_fwd')
@@ -711,7 +743,7 @@ def mha_train_fwd(desc, xq, xk, xv, wq, wk, wv, fc, ln_g, ln_b, mask_struct):
 
 
 def mha_bwd(desc, xq, xk, xv, q, k, v, a, P, Pd, o, dy, wq, wk, wv, fc, ln_g, separate_value_source, want_dw, want_dfc,
-            defer_reduce=False, shared_qk=False):
+            defer_reduce=False, shared_qk=False, act=LAMP_ATTN_SOFTMAX):
     """lamp_mha_bwd -> dict of gradients and of the buffers deferred weight gradients are computed from; shared_qk: xq and xk
     are one tensor (self-attention) -- r['dxq'] is then its whole gradient and r['dxk'] None; with defer_reduce,
     r['pending'] = ([job], buffers to keep alive): dgamma / dbeta are finished by reduce_partials_grouped later."""
@@ -742,11 +774,15 @@ def mha_bwd(desc, xq, xk, xv, q, k, v, a, P, Pd, o, dy, wq, wk, wv, fc, ln_g, se
         npb = L.lamp_mha_bwd_partials_bytes(C.byref(desc))
         part = e((npb,), dtype=torch.uint8, device=dev)
         job = (ReduceJob * 1)()
-    check(L.lamp_mha_bwd(C.byref(desc), C.byref(wts), _dp(xq), _dp(xk), _dp(xv), _dp(q), _dp(k), _dp(v), _dp(a), _dp(P),
-                         _dp(Pd), _dp(o), _dp(dy), r['dxq'].data_ptr(), _dp(r['d_o']), _dp(da), dP.data_ptr(),
-                         r['dq'].data_ptr(), r['dk'].data_ptr(), r['dv'].data_ptr(), r['dxk'].data_ptr(), _dp(r['dxv']),
-                         r['dgamma'].data_ptr(), r['dbeta'].data_ptr(), _dp(r['dwq']), _dp(r['dwk']), _dp(r['dwv']),
-                         _dp(r['dfc']), ptr(ws), nb, ptr(part), npb, job, stream()), 'lamp_mha_bwd')
+    tail = (_dp(xq), _dp(xk), _dp(xv), _dp(q), _dp(k), _dp(v), _dp(a), _dp(P),
+            _dp(Pd), _dp(o), _dp(dy), r['dxq'].data_ptr(), _dp(r['d_o']), _dp(da), dP.data_ptr(),
+            r['dq'].data_ptr(), r['dk'].data_ptr(), r['dv'].data_ptr(), r['dxk'].data_ptr(), _dp(r['dxv']),
+            r['dgamma'].data_ptr(), r['dbeta'].data_ptr(), _dp(r['dwq']), _dp(r['dwk']), _dp(r['dwv']),
+            _dp(r['dfc']), ptr(ws), nb, ptr(part), npb, job, stream())
+    if act != LAMP_ATTN_SOFTMAX:
+        check(L.lamp_mha_act_bwd(C.byref(desc), C.byref(wts), int(act), *tail), 'lamp_mha_act_bwd')
+    else:
+        check(L.lamp_mha_bwd(C.byref(desc), C.byref(wts), *tail), 'lamp_mha_bwd')
     r['pending'] = ([job[0]], (part, vec)) if defer_reduce else None
     if shared_qk:   # r['dxq'] is the gradient of the one tensor behind xq and xk
         r['dxk'] = None
@@ -843,6 +879,17 @@ def softmax_bwd(P, dP, scale, out=None):
     lk = p.size(-1)
     o = torch.empty_like(p) if out is None else out
     check(lib().lamp_softmax_bwd(ptr(p), ptr(g), p.numel() // lk, lk, float(scale), ptr(o), stream()), 'lamp_softmax_bwd')
+    return o
+
+
+def sigmoid_attn_bwd(P, dP, scale, out=None, dropout_p=0.0, seed=0):
+    """dS = scale * P * (1 - P) * dP (lamp_sigmoid_attn_bwd); dropout_p > 0: the dropout mask of (seed, element) on load."""
+    require_device(P, dP)
+    p, g = f32c(P), f32c(dP)
+    lk = p.size(-1)
+    o = out if out is not None else torch.empty_like(p)
+    check(lib().lamp_sigmoid_attn_bwd(ptr(p), ptr(g), p.numel() // lk, lk, float(scale), float(dropout_p),
+                                      int(seed) & 0xffffffff, ptr(o), stream()), 'lamp_sigmoid_attn_bwd')
     return o
 
 

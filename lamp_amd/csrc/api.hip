@@ -242,6 +242,7 @@ struct MhaCall {
     const SeqPlan* keys = nullptr;     // per-sample key extents of a key-token mask (ragged batches)
     bool keys_packed = false;          // xkv holds the packed token rows (keys->rows[0] of them, counted on the device)
     const float* xkv_dense = nullptr;  // with keys_packed: the padded rows, read instead when nothing was skipped
+    int act = LAMP_ATTN_SOFTMAX;       // LAMP_ATTN_SIGMOID: sigmoid attention (attention_sigmoid.hip), maps in the same pass
 };
 
 
@@ -275,7 +276,8 @@ static int mha_attend(const MhaCall& c, const MhaScratch& sc, hipStream_t s) {
     a.Q = c.q_ready ? c.q_ready : sc.Q; a.K = sc.K; a.V = need_v ? sc.V : nullptr; a.O = need_v ? sc.A : nullptr; a.P = c.attn;
     a.scratch = sc.S;
     // maps + output: single-pass kernel (same O bits as without maps), scores normalised in place afterwards
-    if (c.attn && need_v && sc.lse) a.lse = sc.lse;
+    if (c.attn && need_v && sc.lse && c.act == LAMP_ATTN_SOFTMAX) a.lse = sc.lse;
+    a.act = c.act;
     a.B = B; a.H = h; a.lq = lq; a.lk = lk; a.dk = dk; a.dv = dv;
     a.P_batch = c.P_batch > 0 ? c.P_batch : B; a.P_b0 = c.P_b0;
     a.lay.q_b = c.xq_shared ? 0 : int64_t(lq) * hdk; a.lay.q_h = dk; a.lay.q_r = hdk;
@@ -355,11 +357,12 @@ using namespace lamp;
 namespace {
 int sdpa_impl(const float* q, const float* k, const float* v, float* out, float* attn, float* lse, int32_t B, int32_t H,
               int32_t lq, int32_t lk, int32_t d_k, int32_t d_v, float inv_temperature, const lamp_mask* mask,
-                  const lamp_attn_layout* layout, lamp_stream_t stream) {
+                  const lamp_attn_layout* layout, lamp_stream_t stream, int act = LAMP_ATTN_SOFTMAX) {
     if (!layout) return LAMP_E_NULL;
     LAMP_CK(check_mask(mask));
     AttnParams a{};
-    a.Q = q; a.K = k; a.V = v; a.O = out; a.P = attn; a.lse = lse;
+    a.Q = q; a.K = k; a.V = v; a.O = out; a.P = attn; a.lse = act == LAMP_ATTN_SOFTMAX ? lse : nullptr;
+    a.act = act;
     a.B = B; a.H = H; a.lq = lq; a.lk = lk; a.dk = d_k; a.dv = d_v;
     a.P_batch = B; a.P_b0 = 0;
     a.lay = *layout;
@@ -410,6 +413,12 @@ int lamp_sdpa_fwd(const float* q, const float* k, const float* v, float* out, fl
     return sdpa_impl(q, k, v, out, attn, nullptr, B, H, lq, lk, d_k, d_v, inv_temperature, mask, layout, stream);
 }
 
+int lamp_sdpa_act_fwd(const float* q, const float* k, const float* v, float* out, float* attn, int32_t B, int32_t H,
+                      int32_t lq, int32_t lk, int32_t d_k, int32_t d_v, float inv_temperature, int32_t act,
+                      const lamp_mask* mask, const lamp_attn_layout* layout, lamp_stream_t stream) {
+    return sdpa_impl(q, k, v, out, attn, nullptr, B, H, lq, lk, d_k, d_v, inv_temperature, mask, layout, stream, act);
+}
+
 int lamp_sdpa_fwd_fast_maps(const float* q, const float* k, const float* v, float* out, float* attn, float* lse,
                             int32_t B, int32_t H, int32_t lq, int32_t lk, int32_t d_k, int32_t d_v,
                             float inv_temperature, const lamp_mask* mask, const lamp_attn_layout* layout,
@@ -431,6 +440,14 @@ size_t lamp_mha_workspace_bytes(int32_t B, int32_t lq, int32_t lk, int32_t d_mod
 int lamp_mha_fwd(const float* xq, const float* xkv, int32_t B, int32_t lq, int32_t lk, int32_t d_model,
                  int32_t d_k, int32_t d_v, const lamp_mha_weights* w, const lamp_mask* mask, float* out,
                  float* attn, void* workspace, size_t workspace_bytes, lamp_stream_t stream) {
+    return lamp_mha_act_fwd(xq, xkv, B, lq, lk, d_model, d_k, d_v, w, LAMP_ATTN_SOFTMAX, mask, out, attn, workspace,
+                            workspace_bytes, stream);
+}
+
+int lamp_mha_act_fwd(const float* xq, const float* xkv, int32_t B, int32_t lq, int32_t lk, int32_t d_model,
+                     int32_t d_k, int32_t d_v, const lamp_mha_weights* w, int32_t act, const lamp_mask* mask, float* out,
+                     float* attn, void* workspace, size_t workspace_bytes, lamp_stream_t stream) {
+    if (act != LAMP_ATTN_SOFTMAX && act != LAMP_ATTN_SIGMOID) return LAMP_E_UNSUPPORTED;
     if (!xq || !xkv || !w || !out || !workspace) return LAMP_E_NULL;
     if (B <= 0 || lq <= 0 || lk <= 0 || d_model <= 0 || d_k <= 0 || d_v <= 0 || w->n_head <= 0) return LAMP_E_DIMS;
     if (d_model & 3) return LAMP_E_UNSUPPORTED;
@@ -439,7 +456,8 @@ int lamp_mha_fwd(const float* xq, const float* xkv, int32_t B, int32_t lq, int32
     MhaScratch sc;
     mha_layout(c, sc, lq, lk, w->n_head, d_k, d_v, true);
     if (c.off > workspace_bytes) return LAMP_E_WORKSPACE;
-    const MhaCall a{xq, xkv, B, lq, lk, d_model, d_k, d_v, w, mask, out, attn};
+    MhaCall a{xq, xkv, B, lq, lk, d_model, d_k, d_v, w, mask, out, attn};
+    a.act = act;
     LAMP_CK(mha_attend(a, sc, hipStream_t(stream)));
     return mha_tail(a, sc, nullptr, nullptr, nullptr, hipStream_t(stream));
 }
@@ -529,6 +547,13 @@ int lamp_dropout(const float* x, int64_t n, float p, uint32_t seed, float* y, la
 int lamp_softmax_bwd(const float* P, const float* dP, int64_t rows, int32_t lk, float scale, float* dS,
                      lamp_stream_t stream) {
     return launch_softmax_bwd(P, dP, rows, lk, scale, dS, hipStream_t(stream));
+}
+
+int lamp_sigmoid_attn_bwd(const float* P, const float* dP, int64_t rows, int32_t lk, float scale, float dropout_p,
+                          uint32_t seed, float* dS, lamp_stream_t stream) {
+    if (!(dropout_p >= 0.f) || !(dropout_p < 1.f)) return LAMP_E_UNSUPPORTED;
+    const DropoutSpec ds = make_dropout(dropout_p, seed);
+    return launch_sigmoid_bwd(P, dP, rows, lk, scale, dS, hipStream_t(stream), dropout_p > 0.f ? &ds : nullptr);
 }
 
 int lamp_diag_logits_bwd(const float* y, const float* w_out, const float* dlogits, int32_t B, int32_t L, int32_t d_model,
@@ -656,7 +681,14 @@ int lamp_ffn_bwd(const float* x, const float* h, const float* o, const float* dy
 int lamp_mha_train_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, const float* xq, const float* xk,
                        const float* xv, const lamp_mask* mask, float* q, float* k, float* v, float* a, float* P, float* Pd,
                        float* lse, float* o, float* y, lamp_stream_t stream) {
-    if (!c || !w || !xq || !xk || !xv || !q || !k || !v || !a || !P || !lse || !y) return LAMP_E_NULL;
+    return lamp_mha_train_act_fwd(c, w, LAMP_ATTN_SOFTMAX, xq, xk, xv, mask, q, k, v, a, P, Pd, lse, o, y, stream);
+}
+
+int lamp_mha_train_act_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, int32_t act, const float* xq,
+                           const float* xk, const float* xv, const lamp_mask* mask, float* q, float* k, float* v, float* a,
+                           float* P, float* Pd, float* lse, float* o, float* y, lamp_stream_t stream) {
+    if (act != LAMP_ATTN_SOFTMAX && act != LAMP_ATTN_SIGMOID) return LAMP_E_UNSUPPORTED;
+    if (!c || !w || !xq || !xk || !xv || !q || !k || !v || !a || !P || (!lse && act == LAMP_ATTN_SOFTMAX) || !y) return LAMP_E_NULL;
     if (!w->w_qs || !w->w_ks || !w->w_vs || !w->ln_g || !w->ln_b) return LAMP_E_NULL;
     const int B = c->B, lq = c->lq, lk = c->lk, d = c->d_model, H = c->n_head, dk = c->d_k, dv = c->d_v;
     if (B <= 0 || lq <= 0 || lk <= 0 || d <= 0 || H <= 0 || dk <= 0 || dv <= 0) return LAMP_E_DIMS;
@@ -672,7 +704,7 @@ int lamp_mha_train_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, 
     LAMP_CK(project_qkv(*w, d, dk, dv, xq, Mq, q, xk, xv, Mk, k, v, s, nullptr, nullptr));
     const lamp_attn_layout lay{int64_t(lq) * hdk, dk, hdk, int64_t(lk) * hdk, dk, hdk, int64_t(lk) * hdv, dv, hdv,
                                int64_t(lq) * hdv, dv, hdv};
-    LAMP_CK(sdpa_impl(q, k, v, a, P, lse, B, H, lq, lk, dk, dv, c->inv_temperature, mask, &lay, stream));
+    LAMP_CK(sdpa_impl(q, k, v, a, P, lse, B, H, lq, lk, dk, dv, c->inv_temperature, mask, &lay, stream, act));
     if (c->p_attn > 0.f) {   // the reference drops probabilities AFTER the softmax (lamp/SubLayers.py:40-41): a = dropout(P) V
         LAMP_CK(launch_dropout(P, int64_t(H) * B * lq * lk, c->p_attn, c->seed_attn, Pd, s));
         LAMP_CK(gg(Opd{Pd, lk, 1, int64_t(B) * lq * lk, int64_t(lq) * lk}, Opd{v, 1, hdv, dv, int64_t(lk) * hdv}, a, hdv, dv,
@@ -711,6 +743,18 @@ int lamp_mha_bwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, const 
                  float* dv_, float* dxk, float* dxv, float* dgamma, float* dbeta, float* dwq, float* dwk, float* dwv, float* dfc,
                  void* workspace, size_t workspace_bytes, void* partials, size_t partials_bytes, lamp_reduce_job* job,
                  lamp_stream_t stream) {
+    return lamp_mha_act_bwd(c, w, LAMP_ATTN_SOFTMAX, xq, xk, xv, q, k, v, a, P, Pd, o, dy, dxq, d_o, da, dP, dq, dk_, dv_, dxk,
+                            dxv, dgamma, dbeta, dwq, dwk, dwv, dfc, workspace, workspace_bytes, partials, partials_bytes, job,
+                            stream);
+}
+
+int lamp_mha_act_bwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, int32_t act, const float* xq, const float* xk,
+                     const float* xv, const float* q, const float* k, const float* v, const float* a, const float* P,
+                     const float* Pd, const float* o, const float* dy, float* dxq, float* d_o, float* da, float* dP, float* dq,
+                     float* dk_, float* dv_, float* dxk, float* dxv, float* dgamma, float* dbeta, float* dwq, float* dwk,
+                     float* dwv, float* dfc, void* workspace, size_t workspace_bytes, void* partials, size_t partials_bytes,
+                     lamp_reduce_job* job, lamp_stream_t stream) {
+    if (act != LAMP_ATTN_SOFTMAX && act != LAMP_ATTN_SIGMOID) return LAMP_E_UNSUPPORTED;
     if (partials && (!job || partials_bytes < lamp_mha_bwd_partials_bytes(c))) return LAMP_E_WORKSPACE;
     if (!c || !w || !xq || !xk || !xv || !q || !k || !v || !a || !P || !dy) return LAMP_E_NULL;
     if (!dxq || !dP || !dq || !dk_ || !dv_ || !dxk || !dgamma || !dbeta) return LAMP_E_NULL;
@@ -756,7 +800,10 @@ int lamp_mha_bwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, const 
     LAMP_CK(gg(Opd{g_a, hdv, 1, dv, int64_t(lq) * hdv}, Opd{v, hdv, 1, dv, int64_t(lk) * hdv}, dP, lk, PB0, PB1, lq, lk, dv, H,
                B, false, nullptr, nullptr, 0, s));
     // dS = softmax backward of dropout-backward(dPd), in place (the mask is applied on load)
-    LAMP_CK(launch_softmax_bwd(P, dP, int64_t(H) * B * lq, lk, c->inv_temperature, dP, s, drop_a ? &da_spec : nullptr));
+    if (act == LAMP_ATTN_SIGMOID)
+        LAMP_CK(launch_sigmoid_bwd(P, dP, int64_t(H) * B * lq, lk, c->inv_temperature, dP, s, drop_a ? &da_spec : nullptr));
+    else
+        LAMP_CK(launch_softmax_bwd(P, dP, int64_t(H) * B * lq, lk, c->inv_temperature, dP, s, drop_a ? &da_spec : nullptr));
     // dQ = dS K, dK = dS^T Q
     LAMP_CK(gg(Opd{dP, lk, 1, PB0, PB1}, Opd{k, 1, hdk, dk, int64_t(lk) * hdk}, dq, hdk, dk, int64_t(lq) * hdk, lq, dk, lk, H, B,
                false, nullptr, nullptr, 0, s));
@@ -884,6 +931,7 @@ struct Pass {
     const lamp_mask* enc_mask = nullptr;             // the encoder self-attention's mask: &pad_mask, or this micro-batch's
                                                      // slice of lamp_fwd_options::enc_mask
     const lamp_chain_pack* enc_packs = nullptr;      // lamp_fwd_options::enc_chain_packs
+    int dec_act = LAMP_ATTN_SOFTMAX;                 // LAMP_FWD_DEC_SIGMOID: both attention blocks of every decoder layer
 };
 
 // GraphEncoder.forward (lamp/Encoders.py:64-110) on the packed non-PAD token rows (+ ONE shared PAD row: all PAD positions
@@ -1075,6 +1123,7 @@ static int decoder_layer(Pass& p, int i) {
                 p.aux && p.aux->dec_enc_attn ? p.aux->dec_enc_attn[i] : nullptr, p.B, int(p.b0)};
     enc.xq_shared = i == 0; enc.q_ready = i == 0 ? m->dec0_query : nullptr; enc.kv_ready = g.n_ahead > 0;
     enc.keys = &p.sp; enc.keys_packed = p.packed; enc.xkv_dense = p.x;
+    enc.act = p.dec_act;
     LAMP_CK(mha_attend(enc, sc, p.s));
     LAMP_CK(mha_tail(enc, sc, &f1, pk, &ffn_ran, p.s));
     if (!ffn_ran) LAMP_CK(ffn_core(f1, p.s));   // lamp/Layers.py:36
@@ -1085,6 +1134,7 @@ static int decoder_layer(Pass& p, int i) {
         // label->label messages over the label graph (lamp/Layers.py:40)
         MhaCall slf{Y, Y, p.nb, L, L, d, g.dk, g.dv, &l.slf_attn, &p.label_mask, Y,
                     p.aux && p.aux->dec_self_attn ? p.aux->dec_self_attn[i] : nullptr, p.B, int(p.b0)};
+        slf.act = p.dec_act;
         LAMP_CK(mha_attend(slf, w.mha, p.s));
         LAMP_CK(mha_tail(slf, w.mha, &f2, pk ? pk + 1 : nullptr, &ffn_ran, p.s));
     }
@@ -1186,6 +1236,7 @@ static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const Fw
         if (g.live) enc_mask.flags |= LAMP_MASK_SELF_RAGGED;   // a sample's kernel and key split: its own length, never T
         p.enc_mask = &enc_mask;
         p.enc_packs = o ? o->enc_chain_packs : nullptr;
+        p.dec_act = (o && (o->flags & LAMP_FWD_DEC_SIGMOID)) ? LAMP_ATTN_SIGMOID : LAMP_ATTN_SOFTMAX;
         LAMP_CK(!packed ? encode_padded(p) : g.live ? encode_packed_live(p) : encode_packed(p));
         if (g.n_ahead)
             LAMP_CK(project_kv_layers(p.xk, int64_t(nb) * g.T, g.d, g.dk, g.dv, m->dec_layers, g.n_ahead, w.K_ahead,

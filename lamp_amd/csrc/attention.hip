@@ -510,6 +510,7 @@ constexpr int g_force_attn = 0;
 int launch_attn(const AttnParams& p, hipStream_t s) {
     if (p.B <= 0 || p.H <= 0 || p.lq <= 0 || p.lk <= 0 || p.dk <= 0 || p.dv <= 0) return LAMP_E_DIMS;
     if ((p.dk & 3) || (p.dv & 3)) return LAMP_E_UNSUPPORTED;
+    if (p.act != LAMP_ATTN_SOFTMAX && p.act != LAMP_ATTN_SIGMOID) return LAMP_E_UNSUPPORTED;
     if (!p.Q || !p.K) return LAMP_E_NULL;
     if ((!p.V || !p.O) && !(p.P && !p.V && !p.O)) return LAMP_E_NULL;  // V, O optional only with P
     if (p.lse && (!p.P || !p.V || !p.O)) return LAMP_E_NULL;             // single-pass map write-out needs everything
@@ -530,6 +531,9 @@ int launch_attn(const AttnParams& p, hipStream_t s) {
     if (int64_t(p.lq) * L.q_r * 4 >= 0x7fffffffLL || int64_t(p.lk) * L.k_r * 4 >= 0x7fffffffLL ||
         int64_t(p.lk) * L.v_r * 4 >= 0x7fffffffLL || (int64_t(p.lq) * p.m_sq + p.lk) * (p.mask_kind == LAMP_MASK_BITS_U32 ? 4 : 1) >= 0x7fffffffLL)
         return LAMP_E_UNSUPPORTED;  // 32-bit offsets inside one (sample, head) slice
+    // sigmoid attention: its own kernel, before any softmax route is considered (one kernel for every shape: the choice cannot
+    // depend on the batch, nor -- LAMP_MASK_SELF_RAGGED -- on lq / lk)
+    if (p.act == LAMP_ATTN_SIGMOID) return launch_attn_sigmoid(p, s);
     // Key split: must NOT depend on the batch size (a split sums in a different order than the
     // sequential online softmax, and samples must come out bit-identical for every batch / shard), so it
     // is chosen from the per-sample shape only.  At most 128 queries and >= 3 key tiles -> 2-way split

@@ -64,6 +64,38 @@ __global__ __launch_bounds__(256) void masked_softmax_kernel(SoftmaxParams p) {
     for (int k = lane; k < p.lk; k += 64) row[k] *= inv;
 }
 
+// The sigmoid sibling (AttnParams::act == LAMP_ATTN_SIGMOID; lamp/SubLayers.py:17-25,39): P = 1 / (1 + exp(-s)) in place, blocked
+// entries exactly 0 -- a fully blocked row is a row of zeros, not NaN.  Elementwise: no row statistics.
+template <int MK>
+__global__ __launch_bounds__(256) void masked_sigmoid_kernel(SoftmaxParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t rr = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    const int64_t rows = int64_t(p.H) * p.B * p.lq;
+    if (rr >= rows) return;
+    const int q = int(rr % p.lq);
+    const int64_t hb = rr / p.lq;
+    const int b = int(hb % p.B), h = int(hb / p.B);
+    float* row = p.P + ((int64_t(h) * p.P_batch + p.P_b0 + b) * p.lq + q) * int64_t(p.lk);
+    for (int k = lane; k < p.lk; k += 64) {
+        bool blocked = false;
+        if constexpr (MK == LAMP_MASK_U8)
+            blocked = static_cast<const unsigned char*>(p.mask)[int64_t(b) * p.m_sb + int64_t(q) * p.m_sq + k] != 0;
+        else if constexpr (MK == LAMP_MASK_KEY_TOKENS_I64)
+            blocked = static_cast<const long long*>(p.mask)[int64_t(b) * p.m_sb + k] == 0;
+        else if constexpr (MK == LAMP_MASK_BITS_U32)
+            blocked = (static_cast<const unsigned*>(p.mask)[int64_t(b) * p.m_sb + int64_t(q) * p.m_sq + (k >> 5)] >> (k & 31)) & 1u;
+        row[k] = blocked ? 0.f : 1.0f / (1.0f + expf(-row[k]));
+    }
+}
+
+template <int MK>
+void launch_rows(const SoftmaxParams& sp, int act, unsigned grid, hipStream_t s) {
+    if (act == LAMP_ATTN_SIGMOID)
+        hipLaunchKernelGGL(masked_sigmoid_kernel<MK>, dim3(grid), dim3(256), 0, s, sp);
+    else
+        hipLaunchKernelGGL(masked_softmax_kernel<MK>, dim3(grid), dim3(256), 0, s, sp);
+}
+
 }  // namespace
 
 int launch_attn_general(const AttnParams& p, hipStream_t s) {
@@ -88,18 +120,10 @@ int launch_attn_general(const AttnParams& p, hipStream_t s) {
     const int64_t grid = (rows + 3) / 4;
     if (grid > 0x7fffffffLL) return LAMP_E_DIMS;
     switch (p.mask_kind) {
-        case LAMP_MASK_U8:
-            hipLaunchKernelGGL(masked_softmax_kernel<LAMP_MASK_U8>, dim3(unsigned(grid)), dim3(256), 0, s, sp);
-            break;
-        case LAMP_MASK_KEY_TOKENS_I64:
-            hipLaunchKernelGGL(masked_softmax_kernel<LAMP_MASK_KEY_TOKENS_I64>, dim3(unsigned(grid)), dim3(256), 0, s, sp);
-            break;
-        case LAMP_MASK_BITS_U32:
-            hipLaunchKernelGGL(masked_softmax_kernel<LAMP_MASK_BITS_U32>, dim3(unsigned(grid)), dim3(256), 0, s, sp);
-            break;
-        default:
-            hipLaunchKernelGGL(masked_softmax_kernel<LAMP_MASK_NONE>, dim3(unsigned(grid)), dim3(256), 0, s, sp);
-            break;
+        case LAMP_MASK_U8: launch_rows<LAMP_MASK_U8>(sp, p.act, unsigned(grid), s); break;
+        case LAMP_MASK_KEY_TOKENS_I64: launch_rows<LAMP_MASK_KEY_TOKENS_I64>(sp, p.act, unsigned(grid), s); break;
+        case LAMP_MASK_BITS_U32: launch_rows<LAMP_MASK_BITS_U32>(sp, p.act, unsigned(grid), s); break;
+        default: launch_rows<LAMP_MASK_NONE>(sp, p.act, unsigned(grid), s); break;
     }
     if (int e = int(hipGetLastError())) return e;
     if (!p.V || !p.O) return 0;  // maps only (the reference's dead encoder self-attention)

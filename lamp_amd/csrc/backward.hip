@@ -225,6 +225,17 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
     for (int c = lane; c < lk; c += 64) o[c] = scale * p[c] * (grad(c) - s);
 }
 
+// dS = scale * P * (1 - P) * dP (sigmoid attention backward, elementwise; P = 0 on blocked entries keeps them at 0).  DROP as above.
+template <bool DROP>
+__global__ __launch_bounds__(256) void sigmoid_bwd_kernel(const float* P, const float* dP, int64_t n, float scale, float* dS,
+                                                          DropoutSpec ds) {
+    for (int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x; e < n; e += int64_t(gridDim.x) * 256) {
+        const float p = P[e];
+        const float g = DROP ? drop1(dP[e], e, ds) : dP[e];
+        dS[e] = scale * (p * (1.0f - p)) * g;
+    }
+}
+
 // Read-out backward (lamp/Models.py:124-126): dy[b,i,:] = dl[b,i] * w[i,:];  dw[i,:] = sum_b dl[b,i] * y[b,i,:]
 __global__ __launch_bounds__(256) void diag_bwd_kernel(const float* __restrict__ y, const float* __restrict__ w,
                                                        const float* __restrict__ dl, int B, int L, int d,
@@ -398,6 +409,19 @@ int launch_softmax_bwd(const float* P, const float* dP, int64_t rows, int lk, fl
     else
         hipLaunchKernelGGL(softmax_bwd_kernel<false>, dim3((unsigned)g), dim3(256), 0, s, P, dP, rows, lk, scale, dS,
                            DropoutSpec{0u, 1.f, 0u});
+    return int(hipGetLastError());
+}
+
+int launch_sigmoid_bwd(const float* P, const float* dP, int64_t rows, int lk, float scale, float* dS, hipStream_t s,
+                       const DropoutSpec* drop) {
+    if (rows <= 0 || lk <= 0) return LAMP_E_DIMS;
+    if (!P || !dP || !dS) return LAMP_E_NULL;
+    const int64_t n = rows * lk, g = (n + 255) / 256;
+    const unsigned grid = unsigned(g < 16384 ? g : 16384);
+    if (drop && drop->threshold > 0)
+        hipLaunchKernelGGL(sigmoid_bwd_kernel<true>, dim3(grid), dim3(256), 0, s, P, dP, n, scale, dS, *drop);
+    else
+        hipLaunchKernelGGL(sigmoid_bwd_kernel<false>, dim3(grid), dim3(256), 0, s, P, dP, n, scale, dS, DropoutSpec{0u, 1.f, 0u});
     return int(hipGetLastError());
 }
 

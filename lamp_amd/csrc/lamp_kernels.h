@@ -78,6 +78,8 @@ struct AttnParams {
     const int* kv_len;
     const int* kv_off;
     unsigned long long* trace;  // tuning build only: per-workgroup timeline of attention_small.hip; NULL in production
+    int act;  // LAMP_ATTN_SOFTMAX (0) or LAMP_ATTN_SIGMOID: P = sigmoid(scores), blocked entries exactly 0, no row normalisation, lse
+              // unused (attention_sigmoid.hip; wide heads: masked_sigmoid_kernel of attention_general.hip)
 };
 
 int launch_gemm(const GemmParams& p, hipStream_t s);
@@ -98,6 +100,8 @@ int launch_attn_tile(const AttnParams& p, hipStream_t s);
 // attention_sparse.hip: only the allowed (query, key) pairs of a sparse, unstructured shared mask (exact; not the dense kernels' bits)
 bool attn_sparse_applies(const AttnParams& p);
 int launch_attn_sparse(const AttnParams& p, hipStream_t s);
+// attention_sigmoid.hip: every AttnParams::act == LAMP_ATTN_SIGMOID call with d_k, d_v <= 128 (launch_attn checks the arguments)
+int launch_attn_sigmoid(const AttnParams& p, hipStream_t s);
 size_t gemm_gen_workspace_bytes(int M, int N, int K, int batch);
 int launch_gemm_gen(const lamp_gemm_desc& d, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_gemm_group(const lamp_gemm_desc* descs, int n, hipStream_t s);
@@ -214,6 +218,9 @@ int launch_reduce_group(const lamp_reduce_job* jobs, int n, hipStream_t s);
 int launch_dropout(const float* x, int64_t n, float p, uint32_t seed, float* y, hipStream_t s);
 int launch_softmax_bwd(const float* P, const float* dP, int64_t rows, int lk, float scale, float* dS, hipStream_t s,
                        const DropoutSpec* drop = nullptr);   // drop: dP is the gradient of dropout(P), mask applied on load
+// dS = scale * P * (1 - P) * dP, elementwise (sigmoid attention; P = 0 on blocked entries keeps them at 0); dS == dP allowed
+int launch_sigmoid_bwd(const float* P, const float* dP, int64_t rows, int lk, float scale, float* dS, hipStream_t s,
+                       const DropoutSpec* drop = nullptr);
 int launch_diag_bwd(const float* y, const float* w, const float* dl, int B, int L, int d, float* dy, float* dw,
                     hipStream_t s);
 int launch_embed_bwd(const int64_t* seq, int64_t n_tok, const float* dout, int d, int n_vocab, int64_t pad_idx,

@@ -57,6 +57,9 @@ def parse(argv=None):
     ap.add_argument('-enc_self_att', action='store_true',
                     help="the encoder's self-attention is live (LAMP(enc_self_attn=True)); a run_train checkpoint brings the flag "
                          "in its settings, this is for bare state dicts")
+    ap.add_argument('-attn_type', type=str, choices=['softmax', 'sigmoid'], default='softmax',
+                    help="the decoder's attention (LAMP(dec_attn_type=...)); a run_train checkpoint brings the setting, this is for "
+                         "bare state dicts")
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4],
                     help='batches in flight (HIP streams); 4 measured best: 36.6 k / 43.3 k / 46.2 k samples/s with 1 / 2 / 4 on a '
                          'reuters-sized split (tools/bench_eval_epoch.py)')
@@ -121,10 +124,19 @@ def load_checkpoint_state(path):
 def load_checkpoint(path):
     """(state_dict, enc_self_att) of a checkpoint: the flag is run_train's `-enc_self_att` as stored in the checkpoint's
     'settings'; a checkpoint without the setting (the reference's, a bare state_dict) has it off."""
+    return load_checkpoint_settings(path)[:2]
+
+
+def load_checkpoint_settings(path):
+    """(state_dict, enc_self_att, attn_type) of a checkpoint: run_train's `-enc_self_att` and `-attn_type` as stored in the
+    checkpoint's 'settings'; a checkpoint without a field (an earlier run_train's, the reference's, a bare state_dict) has the
+    encoder's self-attention off and a softmax decoder."""
     ckpt = torch.load(path, map_location='cpu', weights_only=False)
     if isinstance(ckpt, dict) and 'model' in ckpt:
-        return ckpt['model'], bool(getattr(ckpt.get('settings'), 'enc_self_att', False))
-    return ckpt, False
+        settings = ckpt.get('settings')
+        return (ckpt['model'], bool(getattr(settings, 'enc_self_att', False)),
+                getattr(settings, 'attn_type', None) or 'softmax')
+    return ckpt, False, 'softmax'
 
 
 def spawn_ranks(n, argv):
@@ -179,13 +191,16 @@ def main(argv=None):
            if opt.label_mask == 'prior' else None)
     d, h = opt.d_model, opt.n_head
     torch.manual_seed(opt.seed)
-    state, live = load_checkpoint(opt.checkpoint) if opt.checkpoint else (None, False)
+    state, live, attn_type = load_checkpoint_settings(opt.checkpoint) if opt.checkpoint else (None, False, 'softmax')
     live = live or opt.enc_self_att
+    if opt.attn_type != 'softmax':
+        attn_type = opt.attn_type
     model = LAMP(n_src, n_labels, data['settings'].max_seq_len, n_labels, n_layers_enc=opt.n_layers_enc,
                  n_layers_dec=opt.n_layers_dec, n_head=h, n_head2=opt.n_head2, d_word_vec=d, d_model=d,
                  d_inner_hid=opt.d_inner_hid, d_k=d // h, d_v=d // h, encoder='graph', decoder='graph',
                  no_enc_pos_embedding=opt.no_enc_pos_embedding, no_dec_self_att=opt.no_dec_self_att,
-                 label_adj_matrix=adj, label_mask=opt.label_mask, dec_dropout2=False, onehot=opt.onehot, enc_self_attn=live)
+                 label_adj_matrix=adj, label_mask=opt.label_mask, dec_dropout2=False, onehot=opt.onehot, enc_self_attn=live,
+                 dec_attn_type=None if attn_type == 'softmax' else attn_type)
     if state is not None:
         model.load_state_dict(state)
     model = model.to(device).eval()

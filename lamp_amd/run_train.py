@@ -3,7 +3,7 @@ decoder=graph, on the MI355X path.
 
     python -m lamp_amd.run_train -data data/reuters/train_valid_test.pt -dataset reuters -batch_size 32 \
            -d_model 512 -n_layers_enc 2 -n_head 4 -label_mask prior -epoch 50 -dropout 0.1 -lr 0.0002 [-int_preds] \
-           [-enc_self_att] [-lr_decay 0.9 -lr_step_size 10] [-save_mode best] [-load_pretrained] [-name run1] [-results_dir results/]
+           [-enc_self_att] [-attn_type sigmoid] [-lr_decay 0.9 -lr_step_size 10] [-save_mode best] [-load_pretrained] [-name run1] [-results_dir results/]
 
 Flag names and derived defaults are config_args.py's for everything on this path (n_layers_dec = n_layers_enc :87-88,
 test_batch_size = batch_size :93-94, d_k = d_v = d_model / n_head :96-99, dec_dropout = dropout :101-102, no position
@@ -74,6 +74,10 @@ def parse(argv=None):
     ap.add_argument('-enc_self_att', action='store_true',
                     help="the encoder's self-attention is live: the paper's feature->feature step, which the reference computes "
                          "and then discards (LAMP(enc_self_attn=True)); stored in the checkpoint's settings for run_eval")
+    ap.add_argument('-attn_type', type=str, choices=['softmax', 'sigmoid'], default='softmax',
+                    help="the decoder's attention: sigmoid gates every key on its own, no row normalisation (LAMP(dec_attn_type="
+                         "'sigmoid')); the reference parses the flag and drops it (config_args.py:49, lamp/Layers.py:23-30), "
+                         "here it does what it says; stored in the checkpoint's settings for run_eval")
     ap.add_argument('-optim_impl', choices=['lamp', 'torch'], default=DEFAULT_OPTIM_IMPL,
                     help='lamp = lamp_amd.optim (one lamp_optim_step launch per step); torch = torch.optim (fused=True for adam)')
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4], help='batches in flight in the valid / test epochs')
@@ -144,6 +148,9 @@ def derive(opt):
     opt.enc_self_att = bool(getattr(opt, 'enc_self_att', False))
     if opt.enc_self_att:
         name += '.enc_self_att'
+    opt.attn_type = getattr(opt, 'attn_type', None) or 'softmax'
+    if opt.attn_type != 'softmax':
+        name += '.attn_' + opt.attn_type
     if opt.name:
         name += '.' + str(opt.name)
     opt.model_name = os.path.join(opt.results_dir, opt.dataset, name)
@@ -178,7 +185,8 @@ def build_model(opt, data, device):
                 n_head2=opt.n_head2, dropout=opt.dropout, dec_dropout=opt.dec_dropout, dec_dropout2=opt.dec_dropout2,
                 encoder=opt.encoder, decoder=opt.decoder, onehot=opt.onehot, no_enc_pos_embedding=opt.no_enc_pos_embedding,
                 no_dec_self_att=opt.no_dec_self_att, loss=opt.loss, label_adj_matrix=adj, label_mask=opt.label_mask,
-                int_preds=opt.int_preds, enc_self_attn=opt.enc_self_att)
+                int_preds=opt.int_preds, enc_self_attn=opt.enc_self_att,
+                dec_attn_type=None if opt.attn_type == 'softmax' else opt.attn_type)
 
 
 def build_optimizer(model, opt):

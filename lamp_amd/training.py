@@ -364,8 +364,8 @@ class _MHAFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xq, xkv, wq, wk, wv, fc, ln_g, ln_b, n_head, mask, keep, p_attn, p_out, seed_attn, seed_out,
-                xv=None, defer=None):
-        """xkv: the key source and, unless ``xv`` is given, the value source too (every layer of the reference passes one
+                xv=None, defer=None, act=0):
+        """act: N.LAMP_ATTN_SIGMOID for sigmoid attention (no row normalisation; blocked entries 0).  xkv: the key source and, unless ``xv`` is given, the value source too (every layer of the reference passes one
         tensor for both, lamp/Layers.py:16,35,40; the module itself accepts two, lamp/SubLayers.py:77-93)."""
         ctx.defer = defer   # (wq, wk, wv, fc, ln_g, ln_b) as the leaf Parameters, or None
         # self-attention: one tensor is query, key and value source -- its three gradient branches are summed in place by the
@@ -376,6 +376,7 @@ class _MHAFn(torch.autograd.Function):
         H = n_head
         dk, dv = wq.size(0) // H, wv.size(0) // H
         inv_t = 1.0 / float(dk) ** 0.5
+        ctx.act = act
         ctx.composite = (COMPOSITE_CALLS and dk <= 128 and dv <= 128 and
                          _plain(xq, xkv, xv, wq, wk, wv, fc, ln_g, ln_b) and (fc is not None or H * dv == d))
         if ctx.composite:
@@ -383,7 +384,7 @@ class _MHAFn(torch.autograd.Function):
             desc = N.MhaTrainDesc(B, lq, lk, d, H, dk, dv, inv_t, p_attn, p_out, seed_attn & 0xffffffff,
                                   seed_out & 0xffffffff)
             q, k, v, a, P, Pd, o, y = N.mha_train_fwd(desc, xq, xkv, xkv if xv is None else xv, wq, wk, wv, fc, ln_g, ln_b,
-                                                     mask)
+                                                     mask, act=act)
             attn = Pd if p_attn > 0 else P.clone()
             # the dropped map is what the value product used: kept for the backward instead of recomputed -- and it is the map
             # the caller gets, so it is SAVED (version-checked: an in-place edit by the caller raises in backward instead of
@@ -397,7 +398,7 @@ class _MHAFn(torch.autograd.Function):
         q = N.linear(xq, wq)
         k = N.linear(xkv, wk)
         v = N.linear(xkv if xv is None else xv, wv)
-        a, P = N.sdpa_fused(q, k, v, H, mask, inv_t, need_attn=True, fast_maps=True)
+        a, P = N.sdpa_fused(q, k, v, H, mask, inv_t, need_attn=True, fast_maps=True, act=act)
         Pd = P
         if p_attn > 0:  # the reference drops probabilities AFTER the softmax; the value product uses the dropped map
             Pd = N.dropout(P, p_attn, seed_attn)
@@ -424,7 +425,7 @@ class _MHAFn(torch.autograd.Function):
                                   seed_out & 0xffffffff)
             r = N.mha_bwd(desc, xq, xkv, xv if has_xv else xkv, q, k, v, a, P, Pd_saved if p_attn > 0 else None, o if has_fc else None,
                           dy.reshape(B * lq, d).contiguous(), wq, wk, wv, fc if has_fc else None, ln_g, has_xv, not wait,
-                          not wait_fc, defer_reduce=wait, shared_qk=ctx.shared_qk)
+                          not wait_fc, defer_reduce=wait, shared_qk=ctx.shared_qk, act=ctx.act)
             if r['pending'] is not None:
                 _weight_grads.add_reductions(r['pending'], [(defer[4], r['dgamma']), (defer[5], r['dbeta'])])
                 r['dgamma'] = r['dbeta'] = None
@@ -436,7 +437,7 @@ class _MHAFn(torch.autograd.Function):
             if wait_fc and has_fc:
                 _weight_grads.add(defer[3], r['d_o'], a.view(-1, H * dv))
             return (r['dxq'].view(xq.shape), None if ctx.shared_qk else r['dxk'].view(xkv.shape), r['dwq'], r['dwk'], r['dwv'], r['dfc'], r['dgamma'],
-                    r['dbeta']) + (None,) * 7 + (r['dxv'].view(xv.shape) if has_xv else None, None)
+                    r['dbeta']) + (None,) * 7 + (r['dxv'].view(xv.shape) if has_xv else None, None, None)
         xq2, xkv2 = xq.reshape(-1, d), xkv.reshape(-1, d)
         xv2 = xv.reshape(-1, d) if has_xv else xkv2
         dz, do, dg, db, _ = N.layernorm_bwd(o.view(xq2.shape), xq2, ln_g, dy.reshape(xq2.shape), dropout_p=p_out,
@@ -460,7 +461,10 @@ class _MHAFn(torch.autograd.Function):
         dP = N.matmul_nt(dah, vh)                                                                 # dPd = dA V^T
         if p_attn > 0:
             N.dropout(dP, p_attn, seed_attn, out=dP)
-        N.softmax_bwd(P4, dP, inv_t, out=dP)                                                      # dS (in place)
+        if ctx.act == N.LAMP_ATTN_SIGMOID:
+            N.sigmoid_attn_bwd(P4, dP, inv_t, out=dP)                                             # dS = P (1 - P) dP / t (in place)
+        else:
+            N.softmax_bwd(P4, dP, inv_t, out=dP)                                                  # dS (in place)
         dq_buf, dk_buf = torch.empty_like(q), torch.empty_like(k)
         N.matmul_nt(dP, kh.transpose(-1, -2), out=heads(dq_buf, lq, dk))                          # dQ = dS K
         N.matmul_nt(dP.transpose(-1, -2), qh.transpose(-1, -2), out=heads(dk_buf, lk, dk))        # dK = dS^T Q
@@ -478,14 +482,14 @@ class _MHAFn(torch.autograd.Function):
         if ctx.shared_qk:   # one tensor behind query, key and value: the three branches summed in place (as lamp_mha_bwd does)
             N.matmul_nt(dk2, wk.t(), out=dxq, accumulate=True)
             N.matmul_nt(dv2, wv.t(), out=dxq, accumulate=True)
-            return (dxq.view(xq.shape), None, dwq, dwk, dwv, dfc, dg, db) + (None,) * 7 + (None, None)
+            return (dxq.view(xq.shape), None, dwq, dwk, dwv, dfc, dg, db) + (None,) * 7 + (None, None, None)
         dxkv = N.matmul_nt(dk2, wk.t())
         dxv = None
         if has_xv:
             dxv = N.matmul_nt(dv2, wv.t()).view(xv.shape)
         else:
             N.matmul_nt(dv2, wv.t(), out=dxkv, accumulate=True)
-        return (dxq.view(xq.shape), dxkv.view(xkv.shape), dwq, dwk, dwv, dfc, dg, db) + (None,) * 7 + (dxv, None)
+        return (dxq.view(xq.shape), dxkv.view(xkv.shape), dwq, dwk, dwv, dfc, dg, db) + (None,) * 7 + (dxv, None, None)
 
 
 class _ReadoutFn(torch.autograd.Function):
@@ -515,7 +519,7 @@ def mha_train(mod, xq, xkv, mask, keep, seeds, xv=None):
                         mod.layer_norm.bias, mod.n_head, mask, keep, float(mod.attention.dropout.p),
                         float(mod.dropout.p), seeds.next(), seeds.next(), xv,
                         _deferrable(mod.w_qs.weight, mod.w_ks.weight, mod.w_vs.weight, fc, mod.layer_norm.weight,
-                                    mod.layer_norm.bias))
+                                    mod.layer_norm.bias), getattr(mod.attention, 'act', 0))
 
 
 class _LinearFn(torch.autograd.Function):
@@ -547,14 +551,14 @@ class _SDPAFn(torch.autograd.Function):
     v (n, lk, dv): out = dropout(softmax(mask(q k^T / t))) v; returns (out, the dropped map) like the reference."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, inv_t, p, seed):
-        out, P = N.sdpa(q, k, v, mask, inv_t, need_attn=True)
+    def forward(ctx, q, k, v, mask, inv_t, p, seed, act=0):
+        out, P = N.sdpa(q, k, v, mask, inv_t, need_attn=True, act=act)
         Pd = P
         if p > 0:
             Pd = N.dropout(P, p, seed)
             out = N.matmul_nt(Pd, v.transpose(-1, -2))
         ctx.save_for_backward(q, k, v, P)
-        ctx.cfg = (inv_t, p, seed)
+        ctx.cfg = (inv_t, p, seed, act)
         attn = Pd if p > 0 else P.clone()
         ctx.mark_non_differentiable(attn)
         return out, attn
@@ -562,23 +566,26 @@ class _SDPAFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do, _dattn_unused):
         q, k, v, P = ctx.saved_tensors
-        inv_t, p, seed = ctx.cfg
+        inv_t, p, seed, act = ctx.cfg
         do = do.contiguous()
         Pd = N.dropout(P, p, seed) if p > 0 else P
         dv = N.matmul_nt(Pd.transpose(-1, -2), do.transpose(-1, -2))    # dV = Pd^T dO
         dP = N.matmul_nt(do, v)                                         # dPd = dO V^T
-        if p > 0:
-            N.dropout(dP, p, seed, out=dP)
-        N.softmax_bwd(P, dP, inv_t, out=dP)                             # dS (in place)
+        if act == N.LAMP_ATTN_SIGMOID:
+            N.sigmoid_attn_bwd(P, dP, inv_t, out=dP, dropout_p=p, seed=seed)   # dS = P (1 - P) dropout'(dP) / t (in place)
+        else:
+            if p > 0:
+                N.dropout(dP, p, seed, out=dP)
+            N.softmax_bwd(P, dP, inv_t, out=dP)                         # dS (in place)
         dq = N.matmul_nt(dP, k.transpose(-1, -2))                       # dQ = dS K
         dk = N.matmul_nt(dP.transpose(-1, -2), q.transpose(-1, -2))     # dK = dS^T Q
-        return dq, dk, dv, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None
 
 
 def sdpa_train(mod, q, k, v, attn_mask):
     N.require_device(q, k, v)
     seed = _Seeds().next()
-    return _SDPAFn.apply(q, k, v, attn_mask, 1.0 / float(mod.temperature), float(mod.dropout.p), seed)
+    return _SDPAFn.apply(q, k, v, attn_mask, 1.0 / float(mod.temperature), float(mod.dropout.p), seed, getattr(mod, 'act', 0))
 
 
 def forward_train(model, src_seq, src_pos, return_attns=False, int_preds=False, adj=None):
