@@ -221,6 +221,25 @@ int lamp_linear_fwd(const float* A, int64_t M, int32_t K, int64_t lda,
                     const float* residual, int64_t ldr, int32_t relu,
                     float* C, int64_t ldc, lamp_stream_t stream);
 
+/* lamp_linear_fwd at a chosen matmul precision.  gfx950 has no TF32 and its fp32 matrix pipe runs at 1/16 of the bf16 one, so the
+ * "treat each float32 as the sum of three bfloat16 numbers" of torch.set_float32_matmul_precision('high') is the one reduced
+ * precision this chip offers an fp32 GEMM (csrc/gemm_split.hip).  Operands and result stay fp32 in memory; each operand tile is
+ * split on the fly into h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), and per 32-wide k-chunk the products are summed in fp32,
+ * smallest first, in a fixed order:
+ *   LAMP_PREC_FP32    lamp_linear_fwd, bit for bit
+ *   LAMP_PREC_BF16X3  a_m w_h + a_h w_m + a_h w_h                                   (|error| <= 2^-14 sum_k |a_k w_k| at K <= 512)
+ *   LAMP_PREC_BF16X6  a_l w_h + a_h w_l + a_m w_m + a_m w_h + a_h w_m + a_h w_h     (fp32-class error)
+ * Any other value: LAMP_E_UNSUPPORTED.  Same shapes as lamp_linear_fwd (no shape falls back to the fp32 kernel).  An output
+ * element's bits depend on (K, precision) only -- never on M, N, the tile or the grid -- and rows are independent.  The one
+ * semantic deviation: an inf operand gives NaN (inf - inf in the split) where fp32 arithmetic gives inf. */
+#define LAMP_PREC_FP32 0
+#define LAMP_PREC_BF16X3 1
+#define LAMP_PREC_BF16X6 2
+int lamp_linear_prec_fwd(const float* A, int64_t M, int32_t K, int64_t lda,
+                         const float* W, int32_t N, int64_t ldw, const float* bias,
+                         const float* residual, int64_t ldr, int32_t relu,
+                         float* C, int64_t ldc, int32_t precision, lamp_stream_t stream);
+
 /* nn.LayerNorm over the last dim, biased variance, eps inside the sqrt (lamp/SubLayers.py:68,130).
  * y may alias x.  d must be a multiple of 4. */
 int lamp_layernorm_fwd(const float* x, int64_t M, int32_t d, const float* gamma, const float* beta,
@@ -549,9 +568,21 @@ int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src
                                       softmax (the reference never gives it an attn_type); aux maps of the decoder are the sigmoid
                                       maps.  Micro-batching and the bit-for-bit independence from B, T and the split hold. */
 
+#define LAMP_FWD_MATMUL_BF16X3 4   /* lamp_fwd_options.flags: every nn.Linear-class GEMM launch of the forward runs at LAMP_PREC_BF16X3 */
+#define LAMP_FWD_MATMUL_BF16X6 8   /* ... at LAMP_PREC_BF16X6.  Both flags together: LAMP_E_UNSUPPORTED.
+                                      Covered (lamp_forward_opts and lamp_onehot_forward_opts): the encoder's feed-forward GEMMs
+                                      including the one with the gathered residual, the K/V, Q and Q/K/V projections of every
+                                      attention block, the live encoder's projections, and the separate-launch tails (fc, W1, W2)
+                                      where the chain launch does not apply.
+                                      These STAY fp32: the chain launch (csrc/chain.hip); every attention kernel; conv2 of the
+                                      one-hot front end; the read-out; the weights-only precomputations a caller builds once per
+                                      weight version (hoisted layer-0 query, embedding fold tables); all of training, lamp_gemm /
+                                      lamp_gemm_grouped and the backward.  The workspace functions return what they return
+                                      without the flags.  A sample's bits stay independent of B, T and the micro-batch split. */
+
 typedef struct lamp_fwd_options {
     int32_t enc_self_attn;
-    int32_t flags;               /* LAMP_FWD_PACKED_ENCODER | LAMP_FWD_DEC_SIGMOID, or 0 */
+    int32_t flags;               /* LAMP_FWD_PACKED_ENCODER | LAMP_FWD_DEC_SIGMOID | LAMP_FWD_MATMUL_BF16X3 / _BF16X6, or 0 */
     const lamp_mask* enc_mask;
     const lamp_chain_pack* enc_chain_packs;
 } lamp_fwd_options;

@@ -16,6 +16,13 @@ the reference accepts ``attn_type`` and never hands it to its layers (lamp/Layer
 and ignored here too, and this second project-own keyword (keyword-only in practice: it sits behind the reference's last argument, in front of
 ``enc_self_attn``) is the opt-in that does what the flag says (``lamp_forward_opts``
 with LAMP_FWD_DEC_SIGMOID in eval, lamp_amd/training.py in training).  The encoder stays softmax; ``state_dict`` is unchanged.
+
+``LAMP.matmul_precision`` ('highest' | 'high' | 'bf16x6', default 'highest') is this chip's reading of
+``torch.set_float32_matmul_precision``: 'high' runs the nn.Linear-class GEMM launches of the FUSED EVAL forward as three bf16
+products per fp32 product on the bf16 matrix pipe (csrc/gemm_split.hip; gfx950 has no TF32), 'bf16x6' as six.  Only that route
+takes it: the module-by-module route (baseline encoders / decoders, per-sample input graphs with maps), ``nn.DataParallel``
+replicas and ``model.train()`` stay fp32, and so do the chain launch, attention, conv2, the read-out and the weights-only
+precomputations inside the fused forward (include/lamp_hip.h: LAMP_FWD_MATMUL_BF16X3).
 """
 import ctypes as C
 
@@ -40,6 +47,21 @@ def _chain_pack(fc, w1, w2, keep):
         keep.append(trio)
         ptrs += [N.ptr(t) for t in trio]
     return N.ChainPack(*ptrs)
+
+
+class _MatmulPrecision:
+    """LAMP.matmul_precision: reads 'highest' on the class and on a model that never set it; setting it on a model validates the
+    name (ValueError) and touches no other attribute's assignment."""
+
+    def __get__(self, obj, owner=None):
+        return 'highest' if obj is None else obj.__dict__.get('_matmul_precision', 'highest')
+
+    def __set__(self, obj, value):
+        N.matmul_precision(value)   # ValueError for anything but 'highest' / 'high' / 'bf16x6'
+        obj.__dict__['_matmul_precision'] = value
+
+    def __delete__(self, obj):
+        obj.__dict__.pop('_matmul_precision', None)
 
 
 class LAMP(nn.Module):
@@ -444,6 +466,11 @@ class LAMP(nn.Module):
             if opts is None:
                 opts = N.FwdOptions(0, 0, None, None)
             opts.flags |= N.LAMP_FWD_DEC_SIGMOID
+        prec_flag = N.matmul_precision(self.matmul_precision)[1]
+        if prec_flag and not getattr(self, '_is_replica', False):   # the nn.Linear-class GEMMs as bf16 split products (LAMP_FWD_MATMUL_*)
+            if opts is None:
+                opts = N.FwdOptions(0, 0, None, None)
+            opts.flags |= prec_flag
         if opts is not None and fe is not None:
             def ws_bytes(mb):
                 return lib.lamp_onehot_forward_opts_workspace_bytes(C.byref(model), C.byref(fe), C.byref(opts), mb, T_in,
@@ -497,6 +524,11 @@ class LAMP(nn.Module):
     # Fold encoder layer 0's first FFN matrix into the embedding tables (weights-only: Emb . W1^T and Pos . W1^T + b1, one
     # GEMM fewer per forward; results move in the last bits, a re-association).  False = the unfolded route.
     fold_embedding = True
+    # Matmul precision of the fused eval forward's nn.Linear-class GEMMs: 'highest' (fp32 matrix pipe), 'high' (bf16x3: each fp32
+    # product as three bf16 products of split operands -- torch.set_float32_matmul_precision('high') on a chip without TF32) or
+    # 'bf16x6' (six products, fp32-class error).  The module-by-module route, nn.DataParallel replicas and model.train() stay
+    # fp32.  Anything else raises ValueError when set on a model or used.
+    matmul_precision = _MatmulPrecision()
     # Live encoder (enc_self_attn=True) on the packed token rows (csrc/attention_ragged.hip) instead of the padded layout.  Off:
     # it measured slower than the padded route on the ragged reuters batch, so it ships behind this switch.
     use_packed_live_encoder = False

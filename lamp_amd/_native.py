@@ -19,6 +19,11 @@ ABI_VERSION = 5
 LAMP_MASK_NONE, LAMP_MASK_U8, LAMP_MASK_KEY_TOKENS_I64, LAMP_MASK_BITS_U32 = 0, 1, 2, 3
 LAMP_MASK_SPARSE_ROWS, LAMP_MASK_SELF_RAGGED = 1, 2   # lamp_mask.flags (include/lamp_hip.h)
 LAMP_FWD_PACKED_ENCODER, LAMP_FWD_DEC_SIGMOID = 1, 2   # lamp_fwd_options.flags
+LAMP_FWD_MATMUL_BF16X3, LAMP_FWD_MATMUL_BF16X6 = 4, 8  # ... the forward's nn.Linear-class GEMMs as bf16x3 / bf16x6 split products
+LAMP_PREC_FP32, LAMP_PREC_BF16X3, LAMP_PREC_BF16X6 = 0, 1, 2   # lamp_linear_prec_fwd
+# LAMP.matmul_precision -> (LAMP_PREC_*, lamp_fwd_options flag); the names of torch.set_float32_matmul_precision where they apply
+MATMUL_PRECISIONS = {'highest': (LAMP_PREC_FP32, 0), 'high': (LAMP_PREC_BF16X3, LAMP_FWD_MATMUL_BF16X3),
+                     'bf16x6': (LAMP_PREC_BF16X6, LAMP_FWD_MATMUL_BF16X6)}
 LAMP_ATTN_SOFTMAX, LAMP_ATTN_SIGMOID = 0, 1            # the activation of an attention block (attn_type)
 ATTN_TYPES = {'softmax': LAMP_ATTN_SOFTMAX, 'sigmoid': LAMP_ATTN_SIGMOID}
 K_EMBED, K_GEMM, K_ATTN, K_LAYERNORM, K_DIAG, K_COUNT = 0, 1, 2, 3, 4, 5
@@ -129,6 +134,7 @@ PROTOTYPES = {
     'lamp_version': (C.c_int, []),
     'lamp_strerror': (C.c_char_p, [C.c_int]),
     'lamp_linear_fwd': (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _vp]),
+    'lamp_linear_prec_fwd': (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp]),
     'lamp_layernorm_fwd': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _f, _vp, _vp]),
     'lamp_sdpa_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f,
                                 C.POINTER(Mask), C.POINTER(AttnLayout), _vp]),
@@ -371,7 +377,17 @@ def key_token_mask(src_seq, T):
 
 
 # ------------------------------------------------------------------ thin wrappers
-def linear(x, weight, bias=None, residual=None, relu=False, _lib=None):
+def matmul_precision(name):
+    """(LAMP_PREC_*, lamp_fwd_options flag) of a LAMP.matmul_precision name; ValueError for anything else."""
+    try:
+        return MATMUL_PRECISIONS[name]
+    except (KeyError, TypeError):
+        raise ValueError("matmul_precision=%r: 'highest', 'high' (bf16x3) or 'bf16x6'" % (name,)) from None
+
+
+def linear(x, weight, bias=None, residual=None, relu=False, _lib=None, precision='highest'):
+    """precision: 'highest' (fp32 matrix pipe), 'high' (bf16x3) or 'bf16x6' -- lamp_linear_prec_fwd."""
+    prec = matmul_precision(precision)[0]
     require_device(x, weight, bias, residual)
     x2 = f32c(x).reshape(-1, x.size(-1))
     w = f32c(weight).reshape(weight.size(0), -1)
@@ -380,6 +396,10 @@ def linear(x, weight, bias=None, residual=None, relu=False, _lib=None):
     out = torch.empty((M, N), dtype=torch.float32, device=x.device)
     r = f32c(residual).reshape(M, N) if residual is not None else None
     b = f32c(bias) if bias is not None else None
+    if prec:
+        check((_lib or lib()).lamp_linear_prec_fwd(ptr(x2), M, K, K, ptr(w), N, K, ptr(b), ptr(r), N, int(relu), ptr(out), N, prec,
+                                                   stream()), 'lamp_linear_prec_fwd')
+        return out.view(*x.shape[:-1], N)
     check((_lib or lib()).lamp_linear_fwd(ptr(x2), M, K, K, ptr(w), N, K, ptr(b), ptr(r), N, int(relu), ptr(out), N,
                                 stream()), 'lamp_linear_fwd')
     return out.view(*x.shape[:-1], N)

@@ -28,7 +28,7 @@ CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'build')
 LIB = os.path.join(HERE, 'liblamp_hip.so')
 LIB_TUNING = os.path.join(HERE, 'liblamp_hip_tuning.so')
-SOURCES = ['gemm.hip', 'gemm_gen.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_general.hip', 'attention_sparse.hip',
+SOURCES = ['gemm.hip', 'gemm_split.hip', 'gemm_gen.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_general.hip', 'attention_sparse.hip',
            'attention_ragged.hip', 'attention_sigmoid.hip', 'pointwise.hip',
            'backward.hip', 'chain.hip', 'conv.hip', 'metrics.hip', 'train_step.hip', 'api.hip']
 TUNING_SOURCES = {'gemm.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_sparse.hip', 'chain.hip'}

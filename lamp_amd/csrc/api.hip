@@ -89,9 +89,16 @@ struct ResGather {
     const float* pos_table;
 };
 
+// lamp_fwd_options.flags -> LAMP_PREC_*, or -1 when both matmul flags are set
+static inline int fwd_matmul_prec(const lamp_fwd_options* o) {
+    const int f = o ? o->flags & (LAMP_FWD_MATMUL_BF16X3 | LAMP_FWD_MATMUL_BF16X6) : 0;
+    return f == 0 ? LAMP_PREC_FP32 : f == LAMP_FWD_MATMUL_BF16X3 ? LAMP_PREC_BF16X3 : f == LAMP_FWD_MATMUL_BF16X6 ? LAMP_PREC_BF16X6 : -1;
+}
+
+// prec: LAMP_PREC_* -- which kernel family multiplies (gemm.hip, or gemm_split.hip's bf16x3 / bf16x6 split products)
 static int linear(const float* A, int64_t M, int K, int64_t lda, const float* const* W, int nseg, int N,
                   int64_t ldw, const float* const* bias, const float* R, int64_t ldr, int relu,
-                  float* const* C, int64_t ldc, hipStream_t s, const int* m_dev = nullptr,
+                  float* const* C, int64_t ldc, int prec, hipStream_t s, const int* m_dev = nullptr,
                   const float* A_dense = nullptr, const ResGather* rg = nullptr) {
     GemmParams p{};
     p.A = A; p.lda = lda; p.M = M; p.K = K; p.N = N; p.nseg = nseg; p.ldw = ldw; p.ldc = ldc;
@@ -105,6 +112,8 @@ static int linear(const float* A, int64_t M, int K, int64_t lda, const float* co
         p.bias[i] = bias ? bias[i] : nullptr;
         p.C[i] = C[i];
     }
+    if (prec == LAMP_PREC_BF16X3) return launch_gemm_split(p, 3, s);
+    if (prec == LAMP_PREC_BF16X6) return launch_gemm_split(p, 6, s);
     return launch_gemm(p, s);
 }
 
@@ -134,18 +143,18 @@ static void attn_mask(AttnParams& a, const lamp_mask* mask) {
 // go out as segments of ONE launch (same bits as one launch each): K with V when both read the same rows at the same
 // width, Q with both when it reads those rows too.  m_dev / A_dense (GemmParams): the key / value rows are packed.
 static int project_qkv(const lamp_mha_weights& w, int d, int dk, int dv, const float* xq, int64_t Mq, float* Q,
-                       const float* xk, const float* xv, int64_t Mk, float* K, float* V, hipStream_t s, const int* m_dev,
-                       const float* A_dense) {
+                       const float* xk, const float* xv, int64_t Mk, float* K, float* V, int prec, hipStream_t s,
+                       const int* m_dev, const float* A_dense) {
     const int hdk = w.n_head * dk, hdv = w.n_head * dv;
     const bool one_kv = K && V && xk == xv && hdk == hdv;
     const bool one_qkv = one_kv && Q && xq == xk && Mq == Mk && !m_dev;
     const float* W[3] = {w.w_qs, w.w_ks, w.w_vs};
     float* C[3] = {Q, K, V};
-    if (Q) LAMP_CK(linear(xq, Mq, d, d, W, one_qkv ? 3 : 1, hdk, d, nullptr, nullptr, 0, 0, C, hdk, s));
+    if (Q) LAMP_CK(linear(xq, Mq, d, d, W, one_qkv ? 3 : 1, hdk, d, nullptr, nullptr, 0, 0, C, hdk, prec, s));
     if (one_qkv) return 0;
-    if (one_kv) return linear(xk, Mk, d, d, W + 1, 2, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, s, m_dev, A_dense);
-    if (K) LAMP_CK(linear(xk, Mk, d, d, W + 1, 1, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, s, m_dev, A_dense));
-    if (V) LAMP_CK(linear(xv, Mk, d, d, W + 2, 1, hdv, d, nullptr, nullptr, 0, 0, C + 2, hdv, s, m_dev, A_dense));
+    if (one_kv) return linear(xk, Mk, d, d, W + 1, 2, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, prec, s, m_dev, A_dense);
+    if (K) LAMP_CK(linear(xk, Mk, d, d, W + 1, 1, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, prec, s, m_dev, A_dense));
+    if (V) LAMP_CK(linear(xv, Mk, d, d, W + 2, 1, hdv, d, nullptr, nullptr, 0, 0, C + 2, hdv, prec, s, m_dev, A_dense));
     return 0;
 }
 
@@ -170,6 +179,7 @@ struct FfnParams {
     // pointwise.hip: gather_row): the first GEMM is not launched, and with `rg` the residual is gathered (x does not exist)
     bool hidden_ready = false;
     const ResGather* rg = nullptr;
+    int prec = LAMP_PREC_FP32;   // matmul precision of the two GEMMs (the forward's LAMP_FWD_MATMUL_* flags)
 };
 
 static int ffn_core(const FfnParams& f, hipStream_t s) {
@@ -181,13 +191,13 @@ static int ffn_core(const FfnParams& f, hipStream_t s) {
         const float* W[1] = {w.w1};
         const float* b[1] = {w.b1};
         float* C[1] = {f.hidden};
-        LAMP_CK(linear(f.x, f.M, d, d, W, 1, dff, d, b, nullptr, 0, 1, C, dff, s, f.rows_dev));
+        LAMP_CK(linear(f.x, f.M, d, d, W, 1, dff, d, b, nullptr, 0, 1, C, dff, f.prec, s, f.rows_dev));
     }
     {
         const float* W[1] = {w.w2};
         const float* b[1] = {w.b2};
         float* C[1] = {f.out};
-        LAMP_CK(linear(f.hidden, f.M, dff, dff, W, 1, d, dff, b, f.x, d, 0, C, d, s, f.rows_dev, nullptr, f.rg));
+        LAMP_CK(linear(f.hidden, f.M, dff, dff, W, 1, d, dff, b, f.x, d, 0, C, d, f.prec, s, f.rows_dev, nullptr, f.rg));
     }
     LayerNormParams ln{f.out, f.M, d, w.ln_g, w.ln_b, f.out};
     if (f.scatter) {
@@ -243,6 +253,7 @@ struct MhaCall {
     bool keys_packed = false;          // xkv holds the packed token rows (keys->rows[0] of them, counted on the device)
     const float* xkv_dense = nullptr;  // with keys_packed: the padded rows, read instead when nothing was skipped
     int act = LAMP_ATTN_SOFTMAX;       // LAMP_ATTN_SIGMOID: sigmoid attention (attention_sigmoid.hip), maps in the same pass
+    int prec = LAMP_PREC_FP32;         // matmul precision of the projections and of a separate-launch fc (never of the chain launch)
 };
 
 
@@ -258,7 +269,7 @@ static int mha_attend(const MhaCall& c, const MhaScratch& sc, hipStream_t s) {
     const bool need_v = c.out != nullptr;
     const bool kv = !c.kv_ready;
     LAMP_CK(project_qkv(w, d, dk, dv, c.xq, c.xq_shared ? lq : int64_t(B) * lq, c.q_ready ? nullptr : sc.Q, c.xkv, c.xkv,
-                        int64_t(B) * lk, kv ? sc.K : nullptr, kv && need_v ? sc.V : nullptr, s,
+                        int64_t(B) * lk, kv ? sc.K : nullptr, kv && need_v ? sc.V : nullptr, c.prec, s,
                         c.keys_packed ? c.keys->rows : nullptr, c.keys_packed ? c.xkv_dense : nullptr));
 
     // A key-token mask without a plan (lamp_mha_fwd on its own): count each sample's keys here, padded layout, so that
@@ -345,7 +356,7 @@ static int mha_tail(const MhaCall& c, const MhaScratch& sc, const FfnParams* f, 
     if (h > 1) {
         const float* W[1] = {w.fc};
         float* C[1] = {out};
-        LAMP_CK(linear(sc.A, M, hdv, hdv, W, 1, d, hdv, nullptr, ln.residual ? nullptr : xq, ln.residual ? 0 : d, 0, C, d, s));
+        LAMP_CK(linear(sc.A, M, hdv, hdv, W, 1, d, hdv, nullptr, ln.residual ? nullptr : xq, ln.residual ? 0 : d, 0, C, d, c.prec, s));
     }
     return launch_layernorm(ln, s);
 }
@@ -394,11 +405,18 @@ const char* lamp_strerror(int status) {
 int lamp_linear_fwd(const float* A, int64_t M, int32_t K, int64_t lda, const float* W, int32_t N, int64_t ldw,
                     const float* bias, const float* residual, int64_t ldr, int32_t relu, float* C, int64_t ldc,
                     lamp_stream_t stream) {
+    return lamp_linear_prec_fwd(A, M, K, lda, W, N, ldw, bias, residual, ldr, relu, C, ldc, LAMP_PREC_FP32, stream);
+}
+
+int lamp_linear_prec_fwd(const float* A, int64_t M, int32_t K, int64_t lda, const float* W, int32_t N, int64_t ldw,
+                         const float* bias, const float* residual, int64_t ldr, int32_t relu, float* C, int64_t ldc,
+                         int32_t precision, lamp_stream_t stream) {
+    if (precision != LAMP_PREC_FP32 && precision != LAMP_PREC_BF16X3 && precision != LAMP_PREC_BF16X6) return LAMP_E_UNSUPPORTED;
     const float* Ws[1] = {W};
     const float* bs[1] = {bias};
     float* Cs[1] = {C};
     if (lda < K || ldw < K || ldc < N || (residual && ldr < N)) return LAMP_E_DIMS;
-    return linear(A, M, K, lda, Ws, 1, N, ldw, bs, residual, ldr, relu, Cs, ldc, hipStream_t(stream));
+    return linear(A, M, K, lda, Ws, 1, N, ldw, bs, residual, ldr, relu, Cs, ldc, precision, hipStream_t(stream));
 }
 
 int lamp_layernorm_fwd(const float* x, int64_t M, int32_t d, const float* gamma, const float* beta, float eps,
@@ -604,13 +622,13 @@ int lamp_ffn_train_fwd(const float* x, int64_t M, int32_t d_model, int32_t d_inn
         const float* W[1] = {w->w1};
         const float* b[1] = {w->b1};
         float* C[1] = {h};
-        LAMP_CK(linear(x, M, d_model, d_model, W, 1, d_inner, d_model, b, nullptr, 0, 1, C, d_inner, s));
+        LAMP_CK(linear(x, M, d_model, d_model, W, 1, d_inner, d_model, b, nullptr, 0, 1, C, d_inner, LAMP_PREC_FP32, s));
     }
     {
         const float* W[1] = {w->w2};
         const float* b[1] = {w->b2};
         float* C[1] = {o};
-        LAMP_CK(linear(h, M, d_inner, d_inner, W, 1, d_model, d_inner, b, nullptr, 0, 0, C, d_model, s));
+        LAMP_CK(linear(h, M, d_inner, d_inner, W, 1, d_model, d_inner, b, nullptr, 0, 0, C, d_model, LAMP_PREC_FP32, s));
     }
     const DropoutSpec ds = make_dropout(dropout_p, seed);
     LayerNormParams p{o, M, d_model, w->ln_g, w->ln_b, y};
@@ -701,7 +719,7 @@ int lamp_mha_train_act_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights*
     hipStream_t s = hipStream_t(stream);
     const int hdk = H * dk, hdv = H * dv;
     const int64_t Mq = int64_t(B) * lq, Mk = int64_t(B) * lk;
-    LAMP_CK(project_qkv(*w, d, dk, dv, xq, Mq, q, xk, xv, Mk, k, v, s, nullptr, nullptr));
+    LAMP_CK(project_qkv(*w, d, dk, dv, xq, Mq, q, xk, xv, Mk, k, v, LAMP_PREC_FP32, s, nullptr, nullptr));
     const lamp_attn_layout lay{int64_t(lq) * hdk, dk, hdk, int64_t(lk) * hdk, dk, hdk, int64_t(lk) * hdv, dv, hdv,
                                int64_t(lq) * hdv, dv, hdv};
     LAMP_CK(sdpa_impl(q, k, v, a, P, lse, B, H, lq, lk, dk, dv, c->inv_temperature, mask, &lay, stream, act));
@@ -715,7 +733,7 @@ int lamp_mha_train_act_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights*
     if (has_fc) {
         const float* W[1] = {w->fc};
         float* C[1] = {o};
-        LAMP_CK(linear(a, Mq, hdv, hdv, W, 1, d, hdv, nullptr, nullptr, 0, 0, C, d, s));
+        LAMP_CK(linear(a, Mq, hdv, hdv, W, 1, d, hdv, nullptr, nullptr, 0, 0, C, d, LAMP_PREC_FP32, s));
         pre = o;
     }
     LayerNormParams ln{pre, Mq, d, w->ln_g, w->ln_b, y};
@@ -932,6 +950,7 @@ struct Pass {
                                                      // slice of lamp_fwd_options::enc_mask
     const lamp_chain_pack* enc_packs = nullptr;      // lamp_fwd_options::enc_chain_packs
     int dec_act = LAMP_ATTN_SOFTMAX;                 // LAMP_FWD_DEC_SIGMOID: both attention blocks of every decoder layer
+    int prec = LAMP_PREC_FP32;                       // LAMP_FWD_MATMUL_*: every linear() of the pass (FfnParams / MhaCall::prec)
 };
 
 // GraphEncoder.forward (lamp/Encoders.py:64-110) on the packed non-PAD token rows (+ ONE shared PAD row: all PAD positions
@@ -959,6 +978,7 @@ static int encode_packed(Pass& p) {
                               m->position_enc, m->n_position, d, p.sp, w.granules, w.Xp, p.s, &fold));
     for (int i = 0; i < m->n_layers_enc; ++i) {   // lamp/Layers.py:18
         FfnParams f{w.Xp, int64_t(p.nb) * T + 1, d, dff, &m->enc_layers[i].pos_ffn, w.Xp, w.H};
+        f.prec = p.prec;
         f.rows_dev = p.sp.rows + 1; f.hidden_ready = folded && i == 0; f.rg = gather_res && i == 0 ? &rg : nullptr;
         if (i + 1 == m->n_layers_enc) { f.scatter = &p.sp; f.nb = p.nb; f.T = T; f.y_flat = p.x; }
         LAMP_CK(ffn_core(f, p.s));
@@ -986,16 +1006,16 @@ static int encode_packed_live(Pass& p) {
         const int hdk = a.n_head * dk, hdv = a.n_head * dv;
         const float* W[3] = {a.w_qs, a.w_ks, a.w_vs};
         float* C[3] = {w.mha.Q, w.mha.K, w.mha.V};
-        LAMP_CK(linear(w.Xp, Mub, d, d, W, 3, hdk, d, nullptr, nullptr, 0, 0, C, hdk, p.s, w.live_rows));
+        LAMP_CK(linear(w.Xp, Mub, d, d, W, 3, hdk, d, nullptr, nullptr, 0, 0, C, hdk, p.prec, p.s, w.live_rows));
         LAMP_CK(launch_attn_ragged_self(w.mha.Q, w.mha.K, w.mha.V, w.mha.A, p.nb, a.n_head, T, dk, dv, p.sp, p.s));
         const float* Wfc[1] = {a.fc};
         float* Cx[1] = {w.Xp};
-        LAMP_CK(linear(w.mha.A, Mub, hdv, hdv, Wfc, 1, d, hdv, nullptr, w.Xp, d, 0, Cx, d, p.s, w.live_rows));
+        LAMP_CK(linear(w.mha.A, Mub, hdv, hdv, Wfc, 1, d, hdv, nullptr, w.Xp, d, 0, Cx, d, p.prec, p.s, w.live_rows));
         LayerNormParams ln{w.Xp, Mub, d, a.ln_g, a.ln_b, w.Xp};
         ln.m_dev = w.live_rows;
         LAMP_CK(launch_layernorm(ln, p.s));
         FfnParams f{w.Xp, Mub, d, dff, &m->enc_layers[i].pos_ffn, w.Xp, w.H};
-        f.rows_dev = w.live_rows;
+        f.rows_dev = w.live_rows; f.prec = p.prec;
         LAMP_CK(ffn_core(f, p.s));
     }
     LAMP_CK(launch_scatter_rows(w.Xp, d, p.nb, T, p.sp, p.x, p.s));
@@ -1037,11 +1057,12 @@ static int encode_padded(Pass& p) {
         const lamp_enc_layer& l = m->enc_layers[i];
         float* map = p.aux && p.aux->enc_self_attn ? p.aux->enc_self_attn[i] : nullptr;
         FfnParams f{p.x, Me, d, dff, &l.pos_ffn, p.x, w.H};   // lamp/Layers.py:18
+        f.prec = p.prec;
         if (p.g.live) {
             // lamp/Layers.py:16 with its output kept: x <- slf_attn(x, x, x), then pos_ffn(x).  The row-local tail
             // (fc + residual -> LayerNorm -> W1 -> W2 + residual -> LayerNorm) is the decoder's sub-chain.
             MhaCall a{p.x, p.x, p.nb, T, T, d, p.g.dk, p.g.dv, &l.slf_attn, p.enc_mask, p.x, map, p.B, int(p.b0)};
-            a.keys = &p.sp;
+            a.keys = &p.sp; a.prec = p.prec;
             bool ffn_ran = false;
             LAMP_CK(mha_attend(a, w.mha, p.s));
             LAMP_CK(mha_tail(a, w.mha, &f, p.enc_packs ? p.enc_packs + i : nullptr, &ffn_ran, p.s));
@@ -1052,7 +1073,7 @@ static int encode_padded(Pass& p) {
             // lamp/Layers.py:16 -- only the attention map of this block is ever observable.  Maps are
             // (h*B, T, T) over the WHOLE batch: this micro-batch fills rows h*B + b0 + b.
             MhaCall a{p.x, p.x, p.nb, T, T, d, p.g.dk, p.g.dv, &l.slf_attn, p.enc_mask, nullptr, map, p.B, int(p.b0)};
-            a.keys = &p.sp;
+            a.keys = &p.sp; a.prec = p.prec;
             LAMP_CK(mha_attend(a, w.mha, p.s));
         }
         f.hidden_ready = folded && i == 0;
@@ -1065,7 +1086,7 @@ static int encode_padded(Pass& p) {
 // K and V projections of the first n decoder layers' enc-attention from the same encoder output: ONE launch when the
 // 2n weight matrices fit the GEMM's segment list (n <= 2) -- 4 x more tiles per launch than layer by layer.
 static int project_kv_layers(const float* x, int64_t Me, int d, int dk, int dv, const lamp_dec_layer* layers, int n,
-                             float* const* K, float* const* V, hipStream_t s, const int* m_dev, const float* A_dense) {
+                             float* const* K, float* const* V, int prec, hipStream_t s, const int* m_dev, const float* A_dense) {
     const int h = layers[0].enc_attn.n_head;
     bool uniform = 2 * n <= GEMM_MAX_SEG && h * dk == h * dv;
     for (int i = 1; i < n && uniform; ++i) uniform = layers[i].enc_attn.n_head == h;
@@ -1079,10 +1100,10 @@ static int project_kv_layers(const float* x, int64_t Me, int d, int dk, int dv, 
             C[2 * i] = K[i];
             C[2 * i + 1] = V[i];
         }
-        return linear(x, Me, d, d, W, 2 * n, h * dk, d, nullptr, nullptr, 0, 0, C, h * dk, s, m_dev, A_dense);
+        return linear(x, Me, d, d, W, 2 * n, h * dk, d, nullptr, nullptr, 0, 0, C, h * dk, prec, s, m_dev, A_dense);
     }
     for (int i = 0; i < n; ++i)
-        LAMP_CK(project_qkv(layers[i].enc_attn, d, dk, dv, nullptr, 0, nullptr, x, x, Me, K[i], V[i], s, m_dev, A_dense));
+        LAMP_CK(project_qkv(layers[i].enc_attn, d, dk, dv, nullptr, 0, nullptr, x, x, Me, K[i], V[i], prec, s, m_dev, A_dense));
     return 0;
 }
 
@@ -1110,6 +1131,7 @@ static int decoder_layer(Pass& p, int i) {
     bool ffn_ran = false;
     FfnParams f1{Y, Md, d, dff, &l.pos_ffn1, Y, w.H}, f2{Y, Md, d, dff, &l.pos_ffn2, Y, w.H};
     f2.n_labels = L;
+    f1.prec = f2.prec = p.prec;
     // the read-out (lamp/Models.py:124-126) rides in the last LayerNorm.  Not with the live encoder: there it is the read-out
     // launch the module-by-module route ends with, so that the two routes agree bit for bit (the fused one sums in another order)
     const bool fused_readout = last && !g.live;
@@ -1123,7 +1145,7 @@ static int decoder_layer(Pass& p, int i) {
                 p.aux && p.aux->dec_enc_attn ? p.aux->dec_enc_attn[i] : nullptr, p.B, int(p.b0)};
     enc.xq_shared = i == 0; enc.q_ready = i == 0 ? m->dec0_query : nullptr; enc.kv_ready = g.n_ahead > 0;
     enc.keys = &p.sp; enc.keys_packed = p.packed; enc.xkv_dense = p.x;
-    enc.act = p.dec_act;
+    enc.act = p.dec_act; enc.prec = p.prec;
     LAMP_CK(mha_attend(enc, sc, p.s));
     LAMP_CK(mha_tail(enc, sc, &f1, pk, &ffn_ran, p.s));
     if (!ffn_ran) LAMP_CK(ffn_core(f1, p.s));   // lamp/Layers.py:36
@@ -1134,7 +1156,7 @@ static int decoder_layer(Pass& p, int i) {
         // label->label messages over the label graph (lamp/Layers.py:40)
         MhaCall slf{Y, Y, p.nb, L, L, d, g.dk, g.dv, &l.slf_attn, &p.label_mask, Y,
                     p.aux && p.aux->dec_self_attn ? p.aux->dec_self_attn[i] : nullptr, p.B, int(p.b0)};
-        slf.act = p.dec_act;
+        slf.act = p.dec_act; slf.prec = p.prec;
         LAMP_CK(mha_attend(slf, w.mha, p.s));
         LAMP_CK(mha_tail(slf, w.mha, &f2, pk ? pk + 1 : nullptr, &ffn_ran, p.s));
     }
@@ -1157,6 +1179,7 @@ static int onehot_check(const lamp_model* m, const lamp_onehot_frontend* fe, int
 static int check_forward(const lamp_model* m, const lamp_onehot_frontend* fe, const int64_t* src_seq, const int64_t* src_pos,
                          int32_t B, int32_t T_in, const float* logits, const float* enc_output, const lamp_aux* aux,
                          const void* workspace, FwdDims* g, const lamp_fwd_options* o = nullptr) {
+    if (fwd_matmul_prec(o) < 0) return LAMP_E_UNSUPPORTED;   // LAMP_FWD_MATMUL_BF16X3 and _BF16X6 together
     if (fe) LAMP_CK(onehot_check(m, fe, T_in));
     if (!m || !src_seq || (fe && !src_pos) || !logits || !enc_output || !workspace) return LAMP_E_NULL;
     if (B <= 0 || T_in <= 0) return LAMP_E_DIMS;
@@ -1237,10 +1260,13 @@ static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const Fw
         p.enc_mask = &enc_mask;
         p.enc_packs = o ? o->enc_chain_packs : nullptr;
         p.dec_act = (o && (o->flags & LAMP_FWD_DEC_SIGMOID)) ? LAMP_ATTN_SIGMOID : LAMP_ATTN_SOFTMAX;
+        // LAMP_FWD_MATMUL_*: every linear() of the pass -- encoder FFN, K/V, Q and Q/K/V projections, the separate-launch tails --
+        // takes the split kernel (gemm_split.hip); the chain launch, attention, conv2 and the read-out are not linear() calls
+        p.prec = fwd_matmul_prec(o);
         LAMP_CK(!packed ? encode_padded(p) : g.live ? encode_packed_live(p) : encode_packed(p));
         if (g.n_ahead)
             LAMP_CK(project_kv_layers(p.xk, int64_t(nb) * g.T, g.d, g.dk, g.dv, m->dec_layers, g.n_ahead, w.K_ahead,
-                                      w.V_ahead, s, packed ? p.sp.rows : nullptr, packed ? p.x : nullptr));
+                                      w.V_ahead, p.prec, s, packed ? p.sp.rows : nullptr, packed ? p.x : nullptr));
         for (int i = 0; i < m->n_layers_dec; ++i) LAMP_CK(decoder_layer(p, i));
     }
     return 0;

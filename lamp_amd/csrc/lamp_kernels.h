@@ -85,6 +85,9 @@ struct AttnParams {
 int launch_gemm(const GemmParams& p, hipStream_t s);
 // whether launch_gemm takes a gathered residual (GemmParams::rg_tok) for this product: the 16-byte epilogue of whole k-tiles of
 // every tile of the menu (shape / alignment rule only: the caller decides BEFORE it leaves the embedded rows unwritten)
+// gemm_split.hip: the same product with every fp32 product replaced by nprod (3 or 6) bf16 products of split operands, fp32
+// accumulation (the LAMP_PREC_BF16X3 / LAMP_PREC_BF16X6 matmul precisions).  Same contract as launch_gemm, any K % 4 == 0.
+int launch_gemm_split(const GemmParams& p, int nprod, hipStream_t s);
 bool gemm_gathered_residual_ok(int N, int K, int64_t ldc, const float* bias, const float* C, const float* emb, const float* pos_table);
 // slab.hip (tuning build only: measured slower than the tile kernel, profiles/r05_rejected_experiments.txt): the same product
 // from format-1 weight packs, one slab of rows per CU, bit-identical to launch_gemm

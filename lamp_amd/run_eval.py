@@ -60,6 +60,10 @@ def parse(argv=None):
     ap.add_argument('-attn_type', type=str, choices=['softmax', 'sigmoid'], default='softmax',
                     help="the decoder's attention (LAMP(dec_attn_type=...)); a run_train checkpoint brings the setting, this is for "
                          "bare state dicts")
+    ap.add_argument('-matmul_precision', type=str, choices=['highest', 'high', 'bf16x6'], default='highest',
+                    help="LAMP.matmul_precision: the forward's nn.Linear-class GEMMs on the fp32 matrix pipe ('highest'), as three "
+                         "bf16 products per fp32 product ('high') or as six ('bf16x6'); attention, the chain launch and the "
+                         "read-out stay fp32")
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4],
                     help='batches in flight (HIP streams); 4 measured best: 36.6 k / 43.3 k / 46.2 k samples/s with 1 / 2 / 4 on a '
                          'reuters-sized split (tools/bench_eval_epoch.py)')
@@ -204,6 +208,7 @@ def main(argv=None):
     if state is not None:
         model.load_state_dict(state)
     model = model.to(device).eval()
+    model.matmul_precision = opt.matmul_precision
     split = data[opt.split]
     batches = D.EvalBatcher(split['src'], split['tgt'], opt.batch_size)
     torch.cuda.synchronize()
@@ -217,7 +222,7 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     out = {'split': opt.split, 'n_samples': batches.n_insts, 'n_labels': n_labels, 'n_batches': len(batches),
            'bce_total': bce_total, 'seconds': dt, 'samples_per_s': batches.n_insts / dt,
-           'checkpoint': opt.checkpoint, 'onehot': opt.onehot, 'n_gpus': world, 'backend': plane.backend, 'backend_note': plane.note}
+           'checkpoint': opt.checkpoint, 'onehot': opt.onehot, 'matmul_precision': model.matmul_precision, 'n_gpus': world, 'backend': plane.backend, 'backend_note': plane.note}
     out.update(multilabel_metrics(preds, targets, opt.br_threshold))
     if opt.all_metrics and rank == 0:
         from .metrics import RANKING_KEYS, compute_metrics
