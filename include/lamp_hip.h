@@ -260,7 +260,11 @@ int lamp_sdpa_fwd(const float* q, const float* k, const float* v, float* out, fl
  * the scaled scores into `attn` and every row's log2-sum-exp into `lse` [(H*B) * lq] (caller-provided, also an
  * output), then `attn` is normalised in place by a second launch.  The maps agree with lamp_sdpa_fwd's exact
  * two-pass softmax to rounding; a fully blocked row is NaN in both.  The training forward uses this (the maps are
- * the backward pass's input); a mask's tile list is ignored (every tile is visited). */
+ * the backward pass's input); a mask's tile list is ignored (every tile is visited).
+ * `lse`, index (head*B + b) * lq + q: log2 of the row's sum of exp(scaled, masked score), i.e. logsumexp / ln 2, so that
+ * attn = exp2(score * log2(e) - lse).  A fully blocked row (every key masked, or a sample whose keys are all padding) has an
+ * empty sum: its lse is -inf (log2f(0), no NaN), and exp2(-inf - -inf) is what makes its map row NaN.  Both kernels the call
+ * can reach write it so (tests/test_attention_train_routes_gpu.py pins the value). */
 int lamp_sdpa_fwd_fast_maps(const float* q, const float* k, const float* v, float* out, float* attn, float* lse,
                             int32_t B, int32_t H, int32_t lq, int32_t lk, int32_t d_k, int32_t d_v,
                             float inv_temperature, const lamp_mask* mask, const lamp_attn_layout* layout,

@@ -440,11 +440,17 @@ def sdpa(q, k, v, mask, inv_temperature, need_attn=True, _lib=None, act=LAMP_ATT
     return out, (attn if need_attn else None)
 
 
-def sdpa_fused(q, k, v, n_head, mask_struct, inv_temperature, need_attn=True, fast_maps=False, act=LAMP_ATTN_SOFTMAX):
+def sdpa_fused(q, k, v, n_head, mask_struct, inv_temperature, need_attn=True, fast_maps=False, act=LAMP_ATTN_SOFTMAX,
+               return_lse=False, _lib=None):
     """Attention on head-fused projections: q (B, lq, H*dk), k (B, lk, H*dk), v (B, lk, H*dv) ->
     out (B, lq, H*dv), attn (H*B, lq, lk) [index head*B + b] or None.  No head split/merge copies: the
     kernel walks the heads through lamp_attn_layout strides.  fast_maps: single-pass map write-out
-    (lamp_sdpa_fwd_fast_maps) instead of the exact two-pass variant."""
+    (lamp_sdpa_fwd_fast_maps) instead of the exact two-pass variant.  return_lse (with fast_maps and need_attn): a third
+    result, that call's row log2-sum-exp (H*B, lq) [index head*B + b; -inf for a fully blocked row] -- the tests' view of
+    what the training forward hands the normalising launch.  _lib: another build of the library (the tuning build)."""
+    if return_lse and not (fast_maps and need_attn and act == LAMP_ATTN_SOFTMAX):
+        raise ValueError('return_lse: only the single-pass softmax map write-out (fast_maps, need_attn) has an lse')
+    L = _lib or lib()
     require_device(q, k, v)
     q, k, v = f32c(q), f32c(k), f32c(v)
     B, lq, hq = q.shape
@@ -456,16 +462,16 @@ def sdpa_fused(q, k, v, n_head, mask_struct, inv_temperature, need_attn=True, fa
     lay = AttnLayout(lq * H * dk, dk, H * dk, lk * H * dk, dk, H * dk, lk * H * dv, dv, H * dv, lq * H * dv, dv, H * dv)
     m = C.byref(mask_struct) if mask_struct is not None else None
     if act != LAMP_ATTN_SOFTMAX:   # the sigmoid kernel writes its maps in the same single pass: no lse, no fast / exact split
-        check(lib().lamp_sdpa_act_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), B, H, lq, lk, dk, dv,
-                                      float(inv_temperature), int(act), m, C.byref(lay), stream()), 'lamp_sdpa_act_fwd')
+        check(L.lamp_sdpa_act_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), B, H, lq, lk, dk, dv,
+                                  float(inv_temperature), int(act), m, C.byref(lay), stream()), 'lamp_sdpa_act_fwd')
         return out, (attn if need_attn else None)
     if fast_maps and need_attn:
         lse = torch.empty((H * B * lq,), dtype=torch.float32, device=q.device)
-        check(lib().lamp_sdpa_fwd_fast_maps(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), ptr(lse), B, H, lq, lk, dk, dv,
-                                            float(inv_temperature), m, C.byref(lay), stream()), 'lamp_sdpa_fwd_fast_maps')
-        return out, attn
-    check(lib().lamp_sdpa_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), B, H, lq, lk, dk, dv,
-                              float(inv_temperature), m, C.byref(lay), stream()), 'lamp_sdpa_fwd')
+        check(L.lamp_sdpa_fwd_fast_maps(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), ptr(lse), B, H, lq, lk, dk, dv,
+                                        float(inv_temperature), m, C.byref(lay), stream()), 'lamp_sdpa_fwd_fast_maps')
+        return (out, attn, lse.view(H * B, lq)) if return_lse else (out, attn)
+    check(L.lamp_sdpa_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(attn), B, H, lq, lk, dk, dv,
+                          float(inv_temperature), m, C.byref(lay), stream()), 'lamp_sdpa_fwd')
     return out, (attn if need_attn else None)
 
 

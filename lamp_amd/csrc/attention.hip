@@ -507,6 +507,24 @@ extern "C" __attribute__((visibility("default"))) void lamp_debug_force_attn(int
 constexpr int g_force_attn = 0;
 #endif
 
+// Where a call goes once d_k, d_v <= 128 and softmax are settled (the rule is spread over attn_sparse_applies,
+// attn_small_applies and attn_tile_applies; first match wins).  With P && lse -- the single-pass map write-out of the training
+// forward -- the pair kernel and the tile kernel refuse (both return false for any P), which leaves two rows:
+//
+//   call                      condition                                                       kernel
+//   P && lse (PM == 2)        lq <= 256, or lk <= 64 && !kv_len, or self_ragged,              attention_small.hip, 16-query blocks,
+//                             or bit 7 of the tuning hook                                     its own key split (1 / 2 / 4)
+//   P && lse (PM == 2)        everything else: lq > 256 && (lk > 64 || kv_len)                attn_kernel<DP, 1, 2, MK>, 32-query blocks
+//                                                                                             (<DP, 2, 2, MK> only when the hook forces
+//                                                                                             a 2-way split; a forced 4 becomes 2)
+//   P only (PM == 1)          always                                                          attn_kernel<DP, 1, 1, MK>, exact two-pass
+//   no P                      sparse_rows && ...                                              attention_sparse.hip (pair kernel)
+//   no P                      as the first row                                                attention_small.hip
+//   no P                      unsplit, 64 < max(d_k, d_v), lq > 256, lk >= 256, mask none / bits   attention_tile.hip
+//   no P                      everything else                                                 attn_kernel<DP, KSPLIT, 0, MK>
+//
+// Either PM == 2 kernel is followed by softmax_from_scores_kernel (below).  tests/test_attention_train_routes_gpu.py holds both
+// rows against fp64 beyond 256 queries.
 int launch_attn(const AttnParams& p, hipStream_t s) {
     if (p.B <= 0 || p.H <= 0 || p.lq <= 0 || p.lk <= 0 || p.dk <= 0 || p.dv <= 0) return LAMP_E_DIMS;
     if ((p.dk & 3) || (p.dv & 3)) return LAMP_E_UNSUPPORTED;

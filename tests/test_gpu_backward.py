@@ -295,7 +295,13 @@ def test_diag_logits_bwd_and_embed_bwd_vs_autograd(dev):
 def test_fast_maps_attention_equals_exact_two_pass(dev, B, H, lq, lk, dk, kind):
     """lamp_sdpa_fwd_fast_maps (single pass: scores + row log-sum-exp, normalised in place) against lamp_sdpa_fwd's exact
     two-pass maps and output, for every mask kind, with a key split (reuters' shape) and without, incl. a fully
-    blocked row (NaN in both)."""
+    blocked row (NaN in both).
+
+    Route: all five shapes have lq <= 200, so every single-pass call here runs the 16-query kernel
+    (attention_small.hip, PM == 2) -- and the comparison is kernel against kernel, not against fp64.  The 32-query
+    attn_kernel<DP, KS, 2> (lq > 256 and lk > 64: delicious' and the genomics encoder's label self-attention), the
+    16-query kernel beyond 256 queries (LAMP_MASK_SELF_RAGGED, lk <= 64), lse itself and the backward at those sizes
+    are held against fp64 in tests/test_attention_train_routes_gpu.py."""
     from lamp_amd import _native as N_
     g = torch.Generator().manual_seed(B * 100 + lq)
     q, k, v = (_rand(g, B, l, H * dk).to(dev) for l in (lq, lk, lk))
