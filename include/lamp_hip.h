@@ -62,9 +62,23 @@ enum lamp_mask_kind {
     LAMP_MASK_NONE = 0,
     LAMP_MASK_U8 = 1,            /* uint8, nonzero = blocked; element (b,q,k) at ptr[b*stride_b + q*stride_q + k] */
     LAMP_MASK_KEY_TOKENS_I64 = 2, /* int64 token ids [B, stride_b]; key k of sample b is blocked iff token == 0 (PAD) */
-    LAMP_MASK_BITS_U32 = 3        /* bit-packed rows: uint32 words, element (b,q,k) = bit (k & 31) of word
+    LAMP_MASK_BITS_U32 = 3,       /* bit-packed rows: uint32 words, element (b,q,k) = bit (k & 31) of word
                                      ptr[b*stride_b + q*stride_q + (k >> 5)] (strides in words), 1 = blocked; bits
                                      past lk are ignored.  One 4-byte load covers a whole 32-key tile of a row. */
+    LAMP_MASK_BIAS_F32 = 4        /* not a mask but an additive fp32 score bias (the weighted label graph): element (b,q,k) at
+                                     ptr[b*stride_b + q*stride_q + k] (strides in floats) is added to the scaled score before
+                                     the softmax, S = <q, k> / temperature + bias; -inf = blocked, exactly as a masked entry (a
+                                     row of -inf comes out NaN, only that row); +inf and NaN are the caller's error.  stride_b
+                                     == 0: shared over the batch; heads always share it.  softmax(s + log w) = w exp(s) / sum w
+                                     exp(s): a bias of log w re-weights the attention by w.  A constant: no gradient flows to it,
+                                     the backward entries take no bias (dS = softmax backward of the saved map).  ptr 16-byte
+                                     aligned, stride_q % 4 == 0 and stride_b % 4 == 0 (a lane fetches its four consecutive keys
+                                     with one 16-byte load; every row is readable up to the next multiple of 4 floats), else
+                                     LAMP_E_ALIGN.  Served by every entry that takes a lamp_mask (csrc/attention_bias.hip;
+                                     d_k or d_v > 128: the general kernel), in all three output modes.  LAMP_E_UNSUPPORTED,
+                                     before any launch: act == LAMP_ATTN_SIGMOID, a tile_list, LAMP_MASK_SPARSE_ROWS,
+                                     LAMP_MASK_SELF_RAGGED, or packed K / V with per-sample key counts (which only a key-token
+                                     mask brings today, so no entry can combine the two). */
 };
 
 /* lamp_mask.flags */
@@ -167,7 +181,8 @@ typedef struct lamp_model {
     const float* position_enc;  /* [n_position, d_model] or NULL (no_enc_pos_embedding) */
     const float* tgt_word_emb;  /* [n_labels, d_model]     decoder.tgt_word_emb.weight */
     const float* w_out;         /* [n_labels, d_model]     tgt_word_proj.linear.weight */
-    const uint8_t* label_mask;  /* [n_labels, n_labels] nonzero = blocked, or NULL ('none') */
+    const uint8_t* label_mask;  /* [n_labels, n_labels] nonzero = blocked, or NULL ('none').  Under LAMP_FWD_LABEL_BIAS
+                                   (lamp_fwd_options.flags): a const float* score bias instead, see there */
     const uint32_t* label_mask_bits; /* optional bit-packed copy of label_mask (LAMP_MASK_BITS_U32 rows of
                                         ceil(n_labels/32) words); used instead of the byte mask when given */
     const int32_t* label_tiles; /* optional active-tile list of label_mask (see lamp_mask.tile_list), row stride
@@ -584,9 +599,20 @@ int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src
                                       lamp_gemm_grouped and the backward.  The workspace functions return what they return
                                       without the flags.  A sample's bits stay independent of B, T and the micro-batch split. */
 
+#define LAMP_FWD_LABEL_BIAS 16     /* lamp_fwd_options.flags (lamp_forward_opts and lamp_onehot_forward_opts): lamp_model.label_mask
+                                      is read as a const float* [n_labels, ld] score bias, ld = (n_labels + 3) & ~3, 16-byte
+                                      aligned (else LAMP_E_ALIGN), instead of a byte mask: the label self-attention of every
+                                      decoder layer runs under LAMP_MASK_BIAS_F32 (NULL: no bias, no mask).  The enc-dec attention
+                                      and the encoder never take it.  label_mask_bits, label_tiles, label_mask_flags and
+                                      label_mask_allowed must be 0, and LAMP_FWD_DEC_SIGMOID must not be set: LAMP_E_UNSUPPORTED.
+                                      The workspace functions return what they return without the flag.  Micro-batching holds;
+                                      a sample's bits stay independent of B, T and the split (the kernel's key split is a
+                                      function of n_labels alone). */
+
 typedef struct lamp_fwd_options {
     int32_t enc_self_attn;
-    int32_t flags;               /* LAMP_FWD_PACKED_ENCODER | LAMP_FWD_DEC_SIGMOID | LAMP_FWD_MATMUL_BF16X3 / _BF16X6, or 0 */
+    int32_t flags;               /* LAMP_FWD_PACKED_ENCODER | LAMP_FWD_DEC_SIGMOID | LAMP_FWD_MATMUL_BF16X3 / _BF16X6 |
+                                    LAMP_FWD_LABEL_BIAS, or 0 */
     const lamp_mask* enc_mask;
     const lamp_chain_pack* enc_chain_packs;
 } lamp_fwd_options;

@@ -37,8 +37,19 @@ class GraphDecoder(nn.Module):
     def __init__(self, n_tgt_vocab, n_max_seq, n_layers=6, n_head=8, n_head2=8, d_k=64, d_v=64,
                  d_word_vec=512, d_model=512, d_inner_hid=1024, dropout=0.1, dropout2=0.1,
                  no_dec_self_att=False, label_adj_matrix=None, label_mask=None, enc_vec=True,
-                 graph_conv=False, attn_type='softmax', dec_attn_type=None):
+                 graph_conv=False, attn_type='softmax', dec_attn_type=None, label_bias=None):
         super().__init__()
+        if label_bias is not None:
+            # the weighted label graph: an additive (L, L) bias on the label -> label scores, shared by batch and heads
+            if no_dec_self_att:
+                raise ValueError('label_bias with no_dec_self_att=True: no label self-attention would read it')
+            if dec_attn_type == 'sigmoid':
+                raise NotImplementedError("label_bias with dec_attn_type='sigmoid': the score bias is a softmax matter")
+            if (not torch.is_tensor(label_bias) or not label_bias.is_floating_point() or
+                    tuple(label_bias.shape) != (n_tgt_vocab, n_tgt_vocab)):
+                raise ValueError('label_bias must be a float (%d, %d) tensor' % (n_tgt_vocab, n_tgt_vocab))
+            if torch.isnan(label_bias).any() or (label_bias == float('inf')).any():
+                raise ValueError('label_bias holds NaN or +inf (only -inf, = blocked, is allowed beside finite values)')
         self.dec_attn_type = dec_attn_type   # None: softmax, whatever attn_type says (as the reference); 'sigmoid': see DecoderLayer
         self.enc_vec = enc_vec   # the encoder hands over ONE vector per sample (mlp / enc_transform): no key-padding mask
         self.dropout = nn.Dropout(dropout)
@@ -71,11 +82,24 @@ class GraphDecoder(nn.Module):
         self.label_allowed_pairs = int((blocked == 0).sum()) if blocked is not None else 0
         self.label_rows_sparse = bool(blocked is not None and tiles is None and
                                       self.label_allowed_pairs <= self.SPARSE_ROWS_MAX_DENSITY * blocked.numel())
+        # the score bias with the mask folded in (blocked = -inf), rows padded to a multiple of 4 floats: with it, the kernels
+        # read THIS instead of the byte / bit mask (csrc/attention_bias.hip).  Like the mask: moved by .to(), not in state_dict
+        bias = None
+        if label_bias is not None:
+            bias = label_bias.detach().to(torch.float32).cpu().clone()
+            if blocked is not None:
+                bias = bias.masked_fill(blocked != 0, float('-inf'))
+            bias = N.pad_bias_rows(bias)
+        self.register_buffer('label_bias_f32', bias, persistent=False)
         self.layer_stack = nn.ModuleList(
             DecoderLayer(d_model, d_inner_hid, n_head, n_head2, d_k, d_v, dropout=dropout, dropout2=dropout2,
                          no_dec_self_att=no_dec_self_att, attn_type=attn_type, dec_attn_type=dec_attn_type) for _ in range(n_layers))
 
     def label_mask_struct(self):
+        bias = self.label_bias_f32
+        if bias is not None:   # LAMP_MASK_BIAS_F32: dense -- no tiles, no bits, no sparse flag, in eval and in training
+            N.require_device(bias)
+            return N.Mask(N.LAMP_MASK_BIAS_F32, 0, bias.data_ptr(), 0, bias.size(1), None, 0, 0)
         m = self.label_mask_u8
         if m is None:
             return None

@@ -71,8 +71,10 @@ class LAMP(nn.Module):
                  embs_share_weight=True, encoder='selfatt', decoder='sa_m', enc_transform='', onehot=False,
                  no_enc_pos_embedding=False, no_dec_self_att=False, loss='ce', label_adj_matrix=None,
                  label_mask=None, matching_mlp=False, graph_conv=False, attn_type='softmax', int_preds=False,
-                 dec_attn_type=None, enc_self_attn=False):
+                 dec_attn_type=None, label_bias=None, enc_self_attn=False):
         super().__init__()
+        if label_bias is not None and decoder != 'graph':
+            raise NotImplementedError('label_bias belongs to the graph decoder, not to decoder=%r' % (decoder,))
         if dec_attn_type is not None and decoder != 'graph':
             raise NotImplementedError('dec_attn_type belongs to the graph decoder, not to decoder=%r' % (decoder,))
         if dec_attn_type is not None and dec_attn_type not in N.ATTN_TYPES:
@@ -110,7 +112,7 @@ class LAMP(nn.Module):
                 d_word_vec=d_word_vec, d_model=d_model, d_k=d_k, d_v=d_v, d_inner_hid=d_inner_hid,
                 dropout=dec_dropout, dropout2=dec_dropout2, no_dec_self_att=no_dec_self_att,
                 label_adj_matrix=label_adj_matrix, label_mask=label_mask, enc_vec=self.enc_vec,
-                graph_conv=graph_conv, attn_type=attn_type, dec_attn_type=dec_attn_type)
+                graph_conv=graph_conv, attn_type=attn_type, dec_attn_type=dec_attn_type, label_bias=label_bias)
         elif decoder == 'mlp':
             self.decoder = MLPDecoder(
                 n_tgt_vocab, n_max_seq_e, n_max_seq_d, n_layers=n_layers_dec, n_head=n_head, d_word_vec=d_word_vec,
@@ -251,15 +253,18 @@ class LAMP(nn.Module):
         mask = self.decoder.label_mask_u8
         tiles = self.decoder.label_tiles
         bits = self.decoder.label_mask_bits
+        bias = getattr(self.decoder, 'label_bias_f32', None)
+        if bias is not None:   # LAMP_FWD_LABEL_BIAS: the bias rides in the label_mask slot, its companions stay empty
+            mask, tiles, bits = bias, None, None
         hoist = self.cache_layer0_query and not replica   # the hoisted projection needs a one-off stream sync
         packs = self.use_chain_packs and not replica      # weights-only repacks: same one-off cost, same staleness rule
         onehot = bool(getattr(self.encoder, 'onehot', False))
         live = self.enc_self_attn
         # weights-only tables, likewise; a live layer 0 starts with the attention, not with W1: nothing to fold into
         fold = self.fold_embedding and not replica and len(self.encoder.layer_stack) > 0 and not onehot and not live
-        sparse = bool(self.use_sparse_label_attention and self.use_mask_bits and self.decoder.label_rows_sparse)
+        sparse = bool(self.use_sparse_label_attention and self.use_mask_bits and self.decoder.label_rows_sparse and bias is None)
         key = tuple(p.data_ptr() for p in params) + (N.ptr(mask), N.ptr(bits), N.ptr(tiles), self.use_label_tiles,
-                                                      hoist, self.use_mask_bits, packs, fold, sparse, live)
+                                                      hoist, self.use_mask_bits, packs, fold, sparse, live, bias is not None)
         if hoist:  # the hoisted projection below is stale once either operand changes
             l0 = self.decoder.layer_stack[0].enc_attn
             key += (self.decoder.tgt_word_emb.weight._version, l0.w_qs.weight._version)
@@ -466,6 +471,10 @@ class LAMP(nn.Module):
             if opts is None:
                 opts = N.FwdOptions(0, 0, None, None)
             opts.flags |= N.LAMP_FWD_DEC_SIGMOID
+        if getattr(self.decoder, 'label_bias_f32', None) is not None:   # the label_mask slot holds the score bias
+            if opts is None:
+                opts = N.FwdOptions(0, 0, None, None)
+            opts.flags |= N.LAMP_FWD_LABEL_BIAS
         prec_flag = N.matmul_precision(self.matmul_precision)[1]
         if prec_flag and not getattr(self, '_is_replica', False):   # the nn.Linear-class GEMMs as bf16 split products (LAMP_FWD_MATMUL_*)
             if opts is None:

@@ -17,9 +17,11 @@ TUNING_LIB_PATH = os.path.join(_HERE, 'liblamp_hip_tuning.so')
 
 ABI_VERSION = 5
 LAMP_MASK_NONE, LAMP_MASK_U8, LAMP_MASK_KEY_TOKENS_I64, LAMP_MASK_BITS_U32 = 0, 1, 2, 3
+LAMP_MASK_BIAS_F32 = 4   # not a mask but an additive fp32 score bias (-inf = blocked): make_bias_mask
 LAMP_MASK_SPARSE_ROWS, LAMP_MASK_SELF_RAGGED = 1, 2   # lamp_mask.flags (include/lamp_hip.h)
 LAMP_FWD_PACKED_ENCODER, LAMP_FWD_DEC_SIGMOID = 1, 2   # lamp_fwd_options.flags
 LAMP_FWD_MATMUL_BF16X3, LAMP_FWD_MATMUL_BF16X6 = 4, 8  # ... the forward's nn.Linear-class GEMMs as bf16x3 / bf16x6 split products
+LAMP_FWD_LABEL_BIAS = 16   # ... lamp_model.label_mask holds an fp32 [L, (L + 3) & ~3] score bias instead of a byte mask
 LAMP_PREC_FP32, LAMP_PREC_BF16X3, LAMP_PREC_BF16X6 = 0, 1, 2   # lamp_linear_prec_fwd
 # LAMP.matmul_precision -> (LAMP_PREC_*, lamp_fwd_options flag); the names of torch.set_float32_matmul_precision where they apply
 MATMUL_PRECISIONS = {'highest': (LAMP_PREC_FP32, 0), 'high': (LAMP_PREC_BF16X3, LAMP_FWD_MATMUL_BF16X3),
@@ -333,6 +335,29 @@ def make_mask(mask, B, lq, lk):
     sb = 0 if m.size(0) == 1 else m.stride(0)
     sq = 0 if m.size(1) == 1 else m.stride(1)
     return Mask(LAMP_MASK_U8, 0, m.data_ptr(), sb, sq, None, 0), m
+
+
+def pad_bias_rows(bias):
+    """(.., lq, lk) float bias -> contiguous fp32 (.., lq, ld) copy with ld = (lk + 3) & ~3 (the padding holds zeros, which
+    the kernel never uses): rows a lane can read in 16-byte groups."""
+    lk = bias.size(-1)
+    ld = (lk + 3) & ~3
+    out = torch.zeros(tuple(bias.shape[:-1]) + (ld,), dtype=torch.float32, device=bias.device)
+    out[..., :lk] = bias
+    return out
+
+
+def make_bias_mask(bias, B, lq, lk):
+    """Float score bias of shape (lq, lk), (1, lq, lk) or (B, lq, lk) (-inf = blocked; added to the scaled scores before the
+    softmax, shared by all heads) -> (LAMP_MASK_BIAS_F32 Mask struct, keepalive tensor).  The row stride is padded to a
+    multiple of 4 floats.  (make_mask keeps reading a float tensor as the reference's mask format: nonzero = blocked.)"""
+    require_device(bias)
+    b = bias if bias.dim() == 3 else bias.unsqueeze(0)
+    if b.dim() != 3 or not b.is_floating_point() or b.size(-1) != lk or b.size(1) != lq or b.size(0) not in (1, B):
+        raise ValueError('attention bias of shape %s is not a float (%d, %d) or (%d, %d, %d) tensor' %
+                         (tuple(bias.shape), lq, lk, B, lq, lk))
+    m = pad_bias_rows(b)
+    return Mask(LAMP_MASK_BIAS_F32, 0, m.data_ptr(), 0 if m.size(0) == 1 else m.stride(0), m.stride(1), None, 0, 0), m
 
 
 def pack_mask_bits(blocked_u8):

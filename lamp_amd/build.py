@@ -29,7 +29,7 @@ OBJ = os.path.join(HERE, 'build')
 LIB = os.path.join(HERE, 'liblamp_hip.so')
 LIB_TUNING = os.path.join(HERE, 'liblamp_hip_tuning.so')
 SOURCES = ['gemm.hip', 'gemm_split.hip', 'gemm_gen.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_general.hip', 'attention_sparse.hip',
-           'attention_ragged.hip', 'attention_sigmoid.hip', 'pointwise.hip',
+           'attention_ragged.hip', 'attention_sigmoid.hip', 'attention_bias.hip', 'pointwise.hip',
            'backward.hip', 'chain.hip', 'conv.hip', 'metrics.hip', 'train_step.hip', 'api.hip']
 TUNING_SOURCES = {'gemm.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_sparse.hip', 'chain.hip'}
 TUNING_ONLY = ['experiments/slab.hip']   # experiments kept bit-identical and benchmarkable, never part of the product library

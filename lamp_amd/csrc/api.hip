@@ -117,12 +117,19 @@ static int linear(const float* A, int64_t M, int K, int64_t lda, const float* co
     return launch_gemm(p, s);
 }
 
-static int check_mask(const lamp_mask* m) {
+// act: the activation of the attention the mask goes to (a score bias is a softmax matter)
+static int check_mask(const lamp_mask* m, int act = LAMP_ATTN_SOFTMAX) {
     if (!m) return 0;
     if (m->kind != LAMP_MASK_NONE && m->kind != LAMP_MASK_U8 && m->kind != LAMP_MASK_KEY_TOKENS_I64 &&
-        m->kind != LAMP_MASK_BITS_U32)
+        m->kind != LAMP_MASK_BITS_U32 && m->kind != LAMP_MASK_BIAS_F32)
         return LAMP_E_UNSUPPORTED;
     if (m->kind != LAMP_MASK_NONE && !m->ptr) return LAMP_E_NULL;
+    if (m->kind == LAMP_MASK_BIAS_F32) {
+        // dense and softmax only: no tile list (not even one the map write-out would ignore), no sparse / ragged route
+        if (act == LAMP_ATTN_SIGMOID || m->tile_list || (m->flags & (LAMP_MASK_SPARSE_ROWS | LAMP_MASK_SELF_RAGGED)))
+            return LAMP_E_UNSUPPORTED;
+        if (!aligned16(m->ptr) || (m->stride_q & 3) || (m->stride_b & 3)) return LAMP_E_ALIGN;
+    }
     return 0;
 }
 
@@ -370,7 +377,7 @@ int sdpa_impl(const float* q, const float* k, const float* v, float* out, float*
               int32_t lq, int32_t lk, int32_t d_k, int32_t d_v, float inv_temperature, const lamp_mask* mask,
                   const lamp_attn_layout* layout, lamp_stream_t stream, int act = LAMP_ATTN_SOFTMAX) {
     if (!layout) return LAMP_E_NULL;
-    LAMP_CK(check_mask(mask));
+    LAMP_CK(check_mask(mask, act));
     AttnParams a{};
     a.Q = q; a.K = k; a.V = v; a.O = out; a.P = attn; a.lse = act == LAMP_ATTN_SOFTMAX ? lse : nullptr;
     a.act = act;
@@ -469,7 +476,7 @@ int lamp_mha_act_fwd(const float* xq, const float* xkv, int32_t B, int32_t lq, i
     if (!xq || !xkv || !w || !out || !workspace) return LAMP_E_NULL;
     if (B <= 0 || lq <= 0 || lk <= 0 || d_model <= 0 || d_k <= 0 || d_v <= 0 || w->n_head <= 0) return LAMP_E_DIMS;
     if (d_model & 3) return LAMP_E_UNSUPPORTED;
-    LAMP_CK(check_mask(mask));
+    LAMP_CK(check_mask(mask, act));
     Carver c{static_cast<char*>(workspace), size_t(B)};
     MhaScratch sc;
     mha_layout(c, sc, lq, lk, w->n_head, d_k, d_v, true);
@@ -716,6 +723,7 @@ int lamp_mha_train_act_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights*
     const bool has_fc = w->fc != nullptr;
     if (has_fc ? !o : (H * dv != d)) return has_fc ? LAMP_E_NULL : LAMP_E_DIMS;
     if (c->p_attn > 0.f && !Pd) return LAMP_E_NULL;
+    LAMP_CK(check_mask(mask, act));   // before the projections go out
     hipStream_t s = hipStream_t(stream);
     const int hdk = H * dk, hdv = H * dv;
     const int64_t Mq = int64_t(B) * lq, Mk = int64_t(B) * lk;
@@ -1203,6 +1211,13 @@ static int check_forward(const lamp_model* m, const lamp_onehot_frontend* fe, co
         if (o->enc_mask->kind != LAMP_MASK_U8 || o->enc_mask->stride_b == 0 || o->enc_mask->tile_list) return LAMP_E_UNSUPPORTED;
         if (!g->live && !(aux && aux->enc_self_attn)) return LAMP_E_UNSUPPORTED;   // nothing would read it
     }
+    if (o && (o->flags & LAMP_FWD_LABEL_BIAS)) {
+        // m->label_mask is an fp32 [L, ld] score bias: softmax only, and none of the byte mask's companions
+        if ((o->flags & LAMP_FWD_DEC_SIGMOID) || m->label_mask_bits || m->label_tiles || m->label_mask_flags ||
+            m->label_mask_allowed)
+            return LAMP_E_UNSUPPORTED;
+        if (m->label_mask && !aligned16(m->label_mask)) return LAMP_E_ALIGN;
+    }
     if ((m->d_model & 3) || (m->d_inner & 3) || (m->d_k & 3) || (m->d_v & 3)) return LAMP_E_UNSUPPORTED;
     if (fe && ((fe->conv2_pack && !aligned16(fe->conv2_pack)) || (!fe->conv2_pack && !aligned16(fe->conv2_w)) ||
                !aligned16(fe->t1) || !aligned16(fe->conv1_b) || !aligned16(workspace)))
@@ -1239,7 +1254,10 @@ static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const Fw
     // the label graph: bit-packed rows when the caller provides them (one dword per 32-key tile), else bytes
     const int L = g.L;
     lamp_mask label_mask{LAMP_MASK_NONE, 0, nullptr, 0, 0, nullptr, 0};
-    if (m->label_mask_bits)
+    if (o && (o->flags & LAMP_FWD_LABEL_BIAS)) {
+        if (m->label_mask)   // LAMP_FWD_LABEL_BIAS: the slot holds fp32 rows, (L + 3) & ~3 floats apart (check_forward)
+            label_mask = lamp_mask{LAMP_MASK_BIAS_F32, 0, m->label_mask, 0, (L + 3) & ~3, nullptr, 0};
+    } else if (m->label_mask_bits)
         label_mask = lamp_mask{LAMP_MASK_BITS_U32, m->label_mask_flags, m->label_mask_bits, 0, (L + 31) / 32, m->label_tiles,
                                (L + 31) / 32 + 1, m->label_mask_allowed};
     else if (m->label_mask)

@@ -497,6 +497,27 @@ __global__ __launch_bounds__(256) void softmax_from_scores_kernel(float* __restr
     for (int c = lane; c < lk; c += 64) p[c] = __builtin_amdgcn_exp2f(p[c] - l);
 }
 
+// The second half of the single-pass map write-out: P = exp2(scores - lse) in place, for the samples of this call.
+static int launch_softmax_from_scores(const AttnParams& p, hipStream_t s) {
+    // NB: only the rows of THIS call's (P_b0 .. P_b0 + B) samples are normalised, head by head
+    const int64_t rows_per_head = int64_t(p.B) * p.lq;
+    const int64_t g = (rows_per_head + 3) / 4;
+    if (g > 0x7fffffffLL) return LAMP_E_DIMS;
+    if (p.P_batch == p.B && p.P_b0 == 0) {  // the maps of all heads are one contiguous block of rows
+        const int64_t g_all = (rows_per_head * p.H + 3) / 4;
+        if (g_all > 0x7fffffffLL) return LAMP_E_DIMS;
+        hipLaunchKernelGGL(softmax_from_scores_kernel, dim3(unsigned(g_all)), dim3(256), 0, s, p.P, p.lse,
+                           rows_per_head * p.H, p.lk);
+        return int(hipGetLastError());
+    }
+    for (int h = 0; h < p.H; ++h) {
+        const int64_t off = (int64_t(h) * p.P_batch + p.P_b0) * p.lq;
+        hipLaunchKernelGGL(softmax_from_scores_kernel, dim3(unsigned(g)), dim3(256), 0, s, p.P + off * p.lk,
+                           p.lse + int64_t(h) * rows_per_head, rows_per_head, p.lk);
+    }
+    return int(hipGetLastError());
+}
+
 #ifdef LAMP_TUNING
 // Tuning build only (liblamp_hip_tuning.so): 0 = heuristic; bits 0-2: force that key split (1/2/4); bits 4-6: query
 // blocks per workgroup of the small-shape kernel (attention_small.hip); bit 7: that kernel for any query count; bit 8: no
@@ -537,6 +558,11 @@ int launch_attn(const AttnParams& p, hipStream_t s) {
     if (((L.q_b | L.q_h | L.q_r | L.k_b | L.k_h | L.k_r | L.v_b | L.v_h | L.v_r) & 3) ||
         !aligned16(p.Q) || !aligned16(p.K) || (p.V && !aligned16(p.V)))
         return LAMP_E_ALIGN;
+    if (p.mask_kind == LAMP_MASK_BIAS_F32) {
+        // an additive fp32 score bias (the weighted label graph): softmax only, dense, every key of every sample
+        if (p.act != LAMP_ATTN_SOFTMAX || p.tiles || p.sparse_rows || p.self_ragged || p.kv_len) return LAMP_E_UNSUPPORTED;
+        if (!aligned16(p.mask) || (p.m_sq & 3) || (p.m_sb & 3)) return LAMP_E_ALIGN;  // a lane's four keys are one 16-byte load
+    }
     if (p.dk > 128 || p.dv > 128) return launch_attn_general(p, s);  // beyond the fused kernel's register budget
     const bool sparse = !(g_force_attn & 0x200) && attn_sparse_applies(p);   // bit 9 of the tuning hook: never the pair kernel
     // the pair kernel executes the allowed pairs only: count what is executed (a roofline fraction must not exceed 1)
@@ -547,11 +573,18 @@ int launch_attn(const AttnParams& p, hipStream_t s) {
     ProfScope prof(LAMP_K_ATTN, flops, bytes, s);
     const int dmax = p.dk > p.dv ? p.dk : p.dv;
     if (int64_t(p.lq) * L.q_r * 4 >= 0x7fffffffLL || int64_t(p.lk) * L.k_r * 4 >= 0x7fffffffLL ||
-        int64_t(p.lk) * L.v_r * 4 >= 0x7fffffffLL || (int64_t(p.lq) * p.m_sq + p.lk) * (p.mask_kind == LAMP_MASK_BITS_U32 ? 4 : 1) >= 0x7fffffffLL)
+        int64_t(p.lk) * L.v_r * 4 >= 0x7fffffffLL || (int64_t(p.lq) * p.m_sq + p.lk) * (p.mask_kind == LAMP_MASK_BITS_U32 ? 4 : 1) >= 0x7fffffffLL ||
+        (p.mask_kind == LAMP_MASK_BIAS_F32 && (int64_t(p.lq) * p.m_sq + p.lk + 3) * 4 >= 0x7fffffffLL))
         return LAMP_E_UNSUPPORTED;  // 32-bit offsets inside one (sample, head) slice
     // sigmoid attention: its own kernel, before any softmax route is considered (one kernel for every shape: the choice cannot
     // depend on the batch, nor -- LAMP_MASK_SELF_RAGGED -- on lq / lk)
     if (p.act == LAMP_ATTN_SIGMOID) return launch_attn_sigmoid(p, s);
+    // a score bias: its own kernel too, for every shape and output mode (the key split is a function of lk alone); with lse it
+    // leaves biased scores in P like the other single-pass kernels, normalised by the launch at the end
+    if (p.mask_kind == LAMP_MASK_BIAS_F32) {
+        if (int rc = launch_attn_bias(p, s)) return rc;
+        return p.lse ? launch_softmax_from_scores(p, s) : 0;
+    }
     // Key split: must NOT depend on the batch size (a split sums in a different order than the
     // sequential online softmax, and samples must come out bit-identical for every batch / shard), so it
     // is chosen from the per-sample shape only.  At most 128 queries and >= 3 key tiles -> 2-way split
@@ -580,23 +613,7 @@ int launch_attn(const AttnParams& p, hipStream_t s) {
     else
         rc = launch_attn_dp<128>(p, ksplit, s);
     if (rc || !p.lse) return rc;
-    // NB: only the rows of THIS call's (P_b0 .. P_b0 + B) samples are normalised, head by head
-    const int64_t rows_per_head = int64_t(p.B) * p.lq;
-    const int64_t g = (rows_per_head + 3) / 4;
-    if (g > 0x7fffffffLL) return LAMP_E_DIMS;
-    if (p.P_batch == p.B && p.P_b0 == 0) {  // the maps of all heads are one contiguous block of rows
-        const int64_t g_all = (rows_per_head * p.H + 3) / 4;
-        if (g_all > 0x7fffffffLL) return LAMP_E_DIMS;
-        hipLaunchKernelGGL(softmax_from_scores_kernel, dim3(unsigned(g_all)), dim3(256), 0, s, p.P, p.lse,
-                           rows_per_head * p.H, p.lk);
-        return int(hipGetLastError());
-    }
-    for (int h = 0; h < p.H; ++h) {
-        const int64_t off = (int64_t(h) * p.P_batch + p.P_b0) * p.lq;
-        hipLaunchKernelGGL(softmax_from_scores_kernel, dim3(unsigned(g)), dim3(256), 0, s, p.P + off * p.lk,
-                           p.lse + int64_t(h) * rows_per_head, rows_per_head, p.lk);
-    }
-    return int(hipGetLastError());
+    return launch_softmax_from_scores(p, s);
 }
 
 }  // namespace lamp

@@ -46,9 +46,17 @@ __global__ __launch_bounds__(256) void masked_softmax_kernel(SoftmaxParams p) {
         else
             return false;
     };
+    // LAMP_MASK_BIAS_F32: the scores are already divided by the temperature and in the natural-log domain -- the bias is added
+    // as it is (-inf = blocked)
+    auto bias = [&](int k) -> float {
+        if constexpr (MK == LAMP_MASK_BIAS_F32)
+            return static_cast<const float*>(p.mask)[int64_t(b) * p.m_sb + int64_t(q) * p.m_sq + k];
+        else
+            return 0.f;
+    };
     float m = -INFINITY;
     for (int k = lane; k < p.lk; k += 64) {
-        const float s = blocked(k) ? -INFINITY : row[k];
+        const float s = blocked(k) ? -INFINITY : (MK == LAMP_MASK_BIAS_F32 ? row[k] + bias(k) : row[k]);
         row[k] = s;
         m = fmaxf(m, s);
     }
@@ -123,6 +131,9 @@ int launch_attn_general(const AttnParams& p, hipStream_t s) {
         case LAMP_MASK_U8: launch_rows<LAMP_MASK_U8>(sp, p.act, unsigned(grid), s); break;
         case LAMP_MASK_KEY_TOKENS_I64: launch_rows<LAMP_MASK_KEY_TOKENS_I64>(sp, p.act, unsigned(grid), s); break;
         case LAMP_MASK_BITS_U32: launch_rows<LAMP_MASK_BITS_U32>(sp, p.act, unsigned(grid), s); break;
+        case LAMP_MASK_BIAS_F32:   // softmax only (launch_attn refused the sigmoid)
+            hipLaunchKernelGGL(masked_softmax_kernel<LAMP_MASK_BIAS_F32>, dim3(unsigned(grid)), dim3(256), 0, s, sp);
+            break;
         default: launch_rows<LAMP_MASK_NONE>(sp, p.act, unsigned(grid), s); break;
     }
     if (int e = int(hipGetLastError())) return e;

@@ -65,7 +65,7 @@ struct AttnParams {
     float scale_log2e;  // inv_temperature * log2(e)
     int mask_kind;
     const void* mask;
-    int64_t m_sb, m_sq;
+    int64_t m_sb, m_sq;    // LAMP_MASK_BIAS_F32: fp32 bias, element (b,q,k) at mask[b*m_sb + q*m_sq + k], added to the scaled scores
     const int* tiles;      // optional per-32-query-block active key-tile lists (shared masks), or nullptr
     int64_t tiles_stride;
     int self_ragged;       // lamp_mask.flags & LAMP_MASK_SELF_RAGGED: the kernel choice must not look at lq / lk
@@ -105,6 +105,8 @@ bool attn_sparse_applies(const AttnParams& p);
 int launch_attn_sparse(const AttnParams& p, hipStream_t s);
 // attention_sigmoid.hip: every AttnParams::act == LAMP_ATTN_SIGMOID call with d_k, d_v <= 128 (launch_attn checks the arguments)
 int launch_attn_sigmoid(const AttnParams& p, hipStream_t s);
+// attention_bias.hip: every call whose mask is LAMP_MASK_BIAS_F32 with d_k, d_v <= 128 (launch_attn checks the arguments)
+int launch_attn_bias(const AttnParams& p, hipStream_t s);
 size_t gemm_gen_workspace_bytes(int M, int N, int K, int batch);
 int launch_gemm_gen(const lamp_gemm_desc& d, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_gemm_group(const lamp_gemm_desc* descs, int n, hipStream_t s);

@@ -46,6 +46,12 @@ def prior_adjacency_device(train_tgt, n_tgt_dict, device):
     not."""
     from . import _native as N
     L = n_tgt_dict - 4
+    ids, offsets = _label_csr(train_tgt)
+    return N.prior_graph(torch.from_numpy(ids).to(device), torch.from_numpy(offsets).to(device), L)
+
+
+def _label_csr(train_tgt):
+    """The label sets of a split flattened into CSR (ids without the four specials, offsets), as numpy int64."""
     lens = np.fromiter((max(len(s) - 2, 0) for s in train_tgt), dtype=np.int64, count=len(train_tgt))
     offsets = np.zeros(len(train_tgt) + 1, dtype=np.int64)
     np.cumsum(lens, out=offsets[1:])
@@ -54,7 +60,60 @@ def prior_adjacency_device(train_tgt, n_tgt_dict, device):
         n = len(s) - 2
         if n > 0:
             ids[lo:lo + n] = np.asarray(s[1:-1], dtype=np.int64) - 4
-    return N.prior_graph(torch.from_numpy(ids).to(device), torch.from_numpy(offsets).to(device), L)
+    return ids, offsets
+
+
+def label_cooccurrence(train_tgt, n_tgt_dict, device):
+    """(L, L) fp32 co-occurrence counts of the train split on `device`: C[i, j] = samples holding both labels, C[i, i] =
+    samples holding label i; a label repeated inside a sample counts once.  The statistics behind the weighted label graph
+    (LAMP(label_bias=...)): where prior_adjacency keeps one bit per pair, this keeps how often.  Built on the device from the
+    CSR prior_adjacency_device flattens: a multi-hot [L, n] matrix times its own transpose on the library's GEMM (lamp_gemm).
+    Sums of 0 / 1 products are exact in fp32 below 2^24 samples, in any order."""
+    from . import _native as N
+    hot = label_multihot_t(train_tgt, n_tgt_dict, device)
+    N.require_device(hot)
+    return N.matmul_nt(hot, hot)
+
+
+def label_multihot_t(train_tgt, n_tgt_dict, device=None):
+    """The transposed multi-hot matrix of a split's label sets: fp32 [L, n padded to a multiple of 4], 1 where the sample holds
+    the label (a label repeated inside a sample stores its 1 twice).  Host-side index bookkeeping; the product is the
+    library's."""
+    L = n_tgt_dict - 4
+    n = len(train_tgt)
+    assert n < 2 ** 24, 'co-occurrence counts are exact in fp32 below 2^24 samples only'
+    ids, offsets = _label_csr(train_tgt)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(offsets))
+    hot = torch.zeros((L, (max(n, 1) + 3) & ~3), dtype=torch.float32, device=device)
+    if ids.size:
+        hot[torch.from_numpy(ids).to(hot.device), torch.from_numpy(rows).to(hot.device)] = 1.0
+    return hot
+
+
+def label_bias_from_counts(C, kind, scale=1.0):
+    """The (L, L) score bias of LAMP(label_bias=...) from label_cooccurrence's counts.
+    'adj':  scale * A, A the prior adjacency with its diagonal (1 where C > 0 or i == j) -- with label_mask='none' the soft
+            prior the reference's unused -adj_matrix_lambda points at: a neighbour's score is raised, nobody is blocked.
+    'logp': scale * log((C[i, j] + 1) / (C[i, i] + 1)) off the diagonal, 0 on it -- a smoothed log P(j | i), finite
+            everywhere and asymmetric; softmax(s + log w) re-weights the attention by w."""
+    C = C.to(torch.float32)
+    L = C.size(0)
+    eye = torch.eye(L, dtype=torch.bool, device=C.device)
+    if kind == 'adj':
+        return float(scale) * ((C > 0) | eye).to(torch.float32)
+    if kind == 'logp':
+        logp = torch.log((C + 1.0) / (torch.diagonal(C).unsqueeze(1) + 1.0))
+        return float(scale) * logp.masked_fill(eye, 0.0)
+    raise ValueError("label bias kind %r: 'adj' or 'logp'" % (kind,))
+
+
+def build_label_bias(data, kind, scale, device):
+    """-label_bias / -label_bias_scale -> the (L, L) bias of LAMP(label_bias=...) from the TRAIN split's co-occurrence counts
+    (rebuilt the same way by run_eval, like the prior mask), or None."""
+    if kind in (None, 'none'):
+        return None
+    counts = label_cooccurrence(data['train']['tgt'], len(data['dict']['tgt']), device)
+    return label_bias_from_counts(counts, kind, scale).cpu()
 
 
 def pad_to_longest(insts):

@@ -60,6 +60,10 @@ def parse(argv=None):
     ap.add_argument('-attn_type', type=str, choices=['softmax', 'sigmoid'], default='softmax',
                     help="the decoder's attention (LAMP(dec_attn_type=...)); a run_train checkpoint brings the setting, this is for "
                          "bare state dicts")
+    ap.add_argument('-label_bias', type=str, choices=['none', 'adj', 'logp'], default='none',
+                    help="weighted label graph (LAMP(label_bias=...)), rebuilt from the train split as the prior mask is; a "
+                         "run_train checkpoint brings the setting, this is for bare state dicts")
+    ap.add_argument('-label_bias_scale', type=float, default=1.0)
     ap.add_argument('-matmul_precision', type=str, choices=['highest', 'high', 'bf16x6'], default='highest',
                     help="LAMP.matmul_precision: the forward's nn.Linear-class GEMMs on the fp32 matrix pipe ('highest'), as three "
                          "bf16 products per fp32 product ('high') or as six ('bf16x6'); attention, the chain launch and the "
@@ -135,12 +139,32 @@ def load_checkpoint_settings(path):
     """(state_dict, enc_self_att, attn_type) of a checkpoint: run_train's `-enc_self_att` and `-attn_type` as stored in the
     checkpoint's 'settings'; a checkpoint without a field (an earlier run_train's, the reference's, a bare state_dict) has the
     encoder's self-attention off and a softmax decoder."""
-    ckpt = torch.load(path, map_location='cpu', weights_only=False)
+    return checkpoint_settings(load_checkpoint_object(path))
+
+
+def load_checkpoint_object(path):
+    """The checkpoint file as saved: read once, then handed to checkpoint_settings and load_checkpoint_label_bias."""
+    return torch.load(path, map_location='cpu', weights_only=False)
+
+
+def checkpoint_settings(ckpt):
+    """load_checkpoint_settings of an already loaded checkpoint."""
     if isinstance(ckpt, dict) and 'model' in ckpt:
         settings = ckpt.get('settings')
         return (ckpt['model'], bool(getattr(settings, 'enc_self_att', False)),
                 getattr(settings, 'attn_type', None) or 'softmax')
     return ckpt, False, 'softmax'
+
+
+def load_checkpoint_label_bias(ckpt):
+    """(kind, scale) of run_train's `-label_bias` / `-label_bias_scale` as stored in the 'settings' of a LOADED checkpoint
+    (load_checkpoint_object), or None for one that says nothing about it (an earlier run_train's, the reference's, a bare
+    state_dict)."""
+    settings = ckpt.get('settings') if isinstance(ckpt, dict) and 'model' in ckpt else None
+    kind = getattr(settings, 'label_bias', None)
+    if kind is None:
+        return None
+    return kind, float(getattr(settings, 'label_bias_scale', 1.0))
 
 
 def spawn_ranks(n, argv):
@@ -195,16 +219,23 @@ def main(argv=None):
            if opt.label_mask == 'prior' else None)
     d, h = opt.d_model, opt.n_head
     torch.manual_seed(opt.seed)
-    state, live, attn_type = load_checkpoint_settings(opt.checkpoint) if opt.checkpoint else (None, False, 'softmax')
+    ckpt = load_checkpoint_object(opt.checkpoint) if opt.checkpoint else None
+    state, live, attn_type = checkpoint_settings(ckpt) if ckpt is not None else (None, False, 'softmax')
     live = live or opt.enc_self_att
     if opt.attn_type != 'softmax':
         attn_type = opt.attn_type
+    bias_kind, bias_scale = opt.label_bias, opt.label_bias_scale
+    stored = load_checkpoint_label_bias(ckpt)
+    del ckpt
+    if stored is not None:   # the checkpoint's settings override the flags
+        bias_kind, bias_scale = stored
+    bias = D.build_label_bias(data, bias_kind, bias_scale, device)
     model = LAMP(n_src, n_labels, data['settings'].max_seq_len, n_labels, n_layers_enc=opt.n_layers_enc,
                  n_layers_dec=opt.n_layers_dec, n_head=h, n_head2=opt.n_head2, d_word_vec=d, d_model=d,
                  d_inner_hid=opt.d_inner_hid, d_k=d // h, d_v=d // h, encoder='graph', decoder='graph',
                  no_enc_pos_embedding=opt.no_enc_pos_embedding, no_dec_self_att=opt.no_dec_self_att,
                  label_adj_matrix=adj, label_mask=opt.label_mask, dec_dropout2=False, onehot=opt.onehot, enc_self_attn=live,
-                 dec_attn_type=None if attn_type == 'softmax' else attn_type)
+                 dec_attn_type=None if attn_type == 'softmax' else attn_type, label_bias=bias)
     if state is not None:
         model.load_state_dict(state)
     model = model.to(device).eval()

@@ -78,6 +78,11 @@ def parse(argv=None):
                     help="the decoder's attention: sigmoid gates every key on its own, no row normalisation (LAMP(dec_attn_type="
                          "'sigmoid')); the reference parses the flag and drops it (config_args.py:49, lamp/Layers.py:23-30), "
                          "here it does what it says; stored in the checkpoint's settings for run_eval")
+    ap.add_argument('-label_bias', type=str, choices=['none', 'adj', 'logp'], default='none',
+                    help="weighted label graph: an additive bias on the label->label attention scores from the train split's "
+                         "co-occurrence counts (LAMP(label_bias=...)): adj = scale on every prior edge (with -label_mask none: "
+                         "the soft prior), logp = scale * smoothed log P(j | i); stored in the checkpoint's settings for run_eval")
+    ap.add_argument('-label_bias_scale', type=float, default=1.0)
     ap.add_argument('-optim_impl', choices=['lamp', 'torch'], default=DEFAULT_OPTIM_IMPL,
                     help='lamp = lamp_amd.optim (one lamp_optim_step launch per step); torch = torch.optim (fused=True for adam)')
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4], help='batches in flight in the valid / test epochs')
@@ -151,6 +156,10 @@ def derive(opt):
     opt.attn_type = getattr(opt, 'attn_type', None) or 'softmax'
     if opt.attn_type != 'softmax':
         name += '.attn_' + opt.attn_type
+    opt.label_bias = getattr(opt, 'label_bias', None) or 'none'
+    opt.label_bias_scale = float(getattr(opt, 'label_bias_scale', 1.0))
+    if opt.label_bias != 'none':
+        name += '.lbias_%s_%s' % (opt.label_bias, opt.label_bias_scale)
     if opt.name:
         name += '.' + str(opt.name)
     opt.model_name = os.path.join(opt.results_dir, opt.dataset, name)
@@ -179,6 +188,7 @@ def build_model(opt, data, device):
     opt.max_token_seq_len_e = data['settings'].max_seq_len
     adj = (D.prior_adjacency_device(data['train']['tgt'], len(data['dict']['tgt']), device).cpu()
            if opt.label_mask == 'prior' else None)
+    bias = D.build_label_bias(data, opt.label_bias, opt.label_bias_scale, device)
     return LAMP(n_src, n_labels, opt.max_token_seq_len_e, n_labels, proj_share_weight=opt.proj_share_weight,
                 embs_share_weight=True, d_k=opt.d_k, d_v=opt.d_v, d_model=opt.d_model, d_word_vec=opt.d_word_vec,
                 d_inner_hid=opt.d_inner_hid, n_layers_enc=opt.n_layers_enc, n_layers_dec=opt.n_layers_dec, n_head=opt.n_head,
@@ -186,7 +196,7 @@ def build_model(opt, data, device):
                 encoder=opt.encoder, decoder=opt.decoder, onehot=opt.onehot, no_enc_pos_embedding=opt.no_enc_pos_embedding,
                 no_dec_self_att=opt.no_dec_self_att, loss=opt.loss, label_adj_matrix=adj, label_mask=opt.label_mask,
                 int_preds=opt.int_preds, enc_self_attn=opt.enc_self_att,
-                dec_attn_type=None if opt.attn_type == 'softmax' else opt.attn_type)
+                dec_attn_type=None if opt.attn_type == 'softmax' else opt.attn_type, label_bias=bias)
 
 
 def build_optimizer(model, opt):
