@@ -431,7 +431,12 @@ int lamp_ffn_train_fwd(const float* x, int64_t M, int32_t d_model, int32_t d_inn
  * pre-ReLU hidden; dW1 [d_inner, d_model] = dh^T x and dW2 [d_model, d_inner] = d_o^T h nullable (deferred);
  * db1 [d_inner], db2, dgamma, dbeta [d_model].
  * partials (nullable, lamp_ffn_bwd_partials_bytes): when given, db1 / db2 / dgamma / dbeta are NOT final on return -- jobs[0..1]
- * describe the two reductions that finish them (see lamp_reduce_job). */
+ * describe the two reductions that finish them (see lamp_reduce_job).
+ * Workspace: lamp_ffn_bwd_workspace_bytes() is the maximum over the launches the call issues -- the LayerNorm backward, the
+ * column sum, and lamp_gemm_workspace_bytes() of each of its four products (dW2, dh, dW1, dx), taken from the one table the
+ * call issues them from -- so every product splits K exactly as lamp_gemm does for it with its own workspace (a smaller
+ * workspace is LAMP_E_WORKSPACE).  lamp_mha_bwd_workspace_bytes() likewise: the LayerNorm backward and the eight
+ * single-batch products (dfc, da, dwq, dwk, dwv and the three data gradients; the per-head products take no workspace). */
 size_t lamp_ffn_bwd_workspace_bytes(int64_t M, int32_t d_model, int32_t d_inner);
 size_t lamp_ffn_bwd_partials_bytes(int64_t M, int32_t d_model, int32_t d_inner);
 int lamp_ffn_bwd(const float* x, const float* h, const float* o, const float* dy, int64_t M, int32_t d_model,
@@ -539,7 +544,8 @@ int lamp_embed_bwd(const int64_t* src_seq, int64_t n_tokens, const float* dout, 
 /* ---- the whole hot path ------------------------------------------------------------------- */
 
 /* Bytes of workspace lamp_forward needs to process `micro_batch` samples of padded length T at a
- * time.  lamp_forward splits B into micro-batches of floor(workspace_bytes / bytes(1)) samples. */
+ * time.  lamp_forward splits B into micro-batches of floor(workspace_bytes / bytes(1)) samples.
+ * bytes(1) is also the least a call accepts: one byte less is LAMP_E_WORKSPACE before anything is launched or written. */
 size_t lamp_forward_workspace_bytes(const lamp_model* m, int32_t micro_batch, int32_t T,
                                     int32_t want_attn);
 

@@ -306,7 +306,13 @@ _ws = {}
 
 def workspace(nbytes, device):
     """Grow-only scratch buffer per (device, HIP stream): forwards issued on different streams may be in
-    flight at the same time and must not share scratch (the library itself never allocates)."""
+    flight at the same time and must not share scratch (the library itself never allocates).
+
+    The buffer is `nbytes + 256` bytes when it is (re)allocated and is never shrunk, so a call made through it almost
+    always has slack behind the bytes its `*_workspace_bytes()` asked for -- 256 bytes at least, usually whatever an
+    earlier, larger call left.  A size function that returns too little, or a kernel that writes past its share, is
+    therefore invisible through this route: tests/test_buffer_contracts_gpu.py bypasses it and hands the library
+    exactly-sized buffers between sentinel red zones (tests/redzone_common.py)."""
     key = (device.type, device.index if device.index is not None else torch.cuda.current_device(), stream())
     buf = _ws.get(key)
     if buf is None or buf.numel() < nbytes:

@@ -616,6 +616,33 @@ int gg(const Opd& A, const Opd& B, float* C, int64_t ldc, int64_t cb0, int64_t c
 inline Opd rows(const float* p, int64_t ld) { return Opd{p, ld, 1, 0, 0}; }        // [m, k], k contiguous
 inline Opd cols(const float* p, int64_t ld) { return Opd{p, 1, ld, 0, 0}; }        // stored [k, m]: the transposed read
 inline size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
+
+// The single-batch products of a backward composite, as (M, N, K) of C[M, N] = A[M, K] B[N, K]^T.  The composite issues its
+// products FROM this table and its *_workspace_bytes() takes the maximum OVER it: gemm_gen_workspace_bytes is not monotone in
+// the shape (an output of 512 tiles or more takes no K split), so no "largest" shape bounds the others.
+struct Prod {
+    int M, N, K;
+};
+enum { FFN_DW2, FFN_DH, FFN_DW1, FFN_DX, FFN_PRODS };
+struct FfnBwdProds {
+    Prod p[FFN_PRODS];
+    FfnBwdProds(int M, int d, int dff) : p{{d, dff, M}, {M, dff, d}, {dff, d, M}, {M, d, dff}} {}
+};
+enum { MHA_DFC, MHA_DA, MHA_DWQ, MHA_DWK, MHA_DWV, MHA_DXQ, MHA_DXK, MHA_DXV, MHA_PRODS };
+struct MhaBwdProds {
+    Prod p[MHA_PRODS];
+    MhaBwdProds(int Mq, int Mk, int d, int hdk, int hdv)
+        : p{{d, hdv, Mq}, {Mq, hdv, d}, {hdk, d, Mq}, {hdk, d, Mk}, {hdv, d, Mk}, {Mq, d, hdk}, {Mk, d, hdk}, {Mk, d, hdv}} {}
+};
+inline size_t prods_workspace_bytes(const Prod* p, int n) {
+    size_t need = 0;
+    for (int i = 0; i < n; ++i) need = std::max(need, gemm_gen_workspace_bytes(p[i].M, p[i].N, p[i].K, 1));
+    return need;
+}
+int gp(const Opd& A, const Opd& B, float* C, const Prod& q, bool accumulate, const float* relu_mask, void* ws, size_t ws_bytes,
+       hipStream_t s) {
+    return gg(A, B, C, q.N, 0, 0, q.M, q.N, q.K, 1, 1, accumulate, relu_mask, ws, ws_bytes, s);
+}
 }  // namespace
 
 int lamp_ffn_train_fwd(const float* x, int64_t M, int32_t d_model, int32_t d_inner, const lamp_ffn_weights* w,
@@ -645,9 +672,9 @@ int lamp_ffn_train_fwd(const float* x, int64_t M, int32_t d_model, int32_t d_inn
 
 size_t lamp_ffn_bwd_workspace_bytes(int64_t M, int32_t d_model, int32_t d_inner) {
     if (M <= 0 || M > 0x7fffffff || d_model <= 0 || d_inner <= 0) return 0;
+    const FfnBwdProds g(int(M), d_model, d_inner);
     return max3(layernorm_bwd_workspace_bytes(M, d_model), colsum_workspace_bytes(M, d_inner),
-                gemm_gen_workspace_bytes(d_model > d_inner ? d_model : d_inner, d_model > d_inner ? d_model : d_inner,
-                                         int(M), 1));
+                prods_workspace_bytes(g.p, FFN_PRODS));
 }
 
 size_t lamp_ffn_bwd_partials_bytes(int64_t M, int32_t d_model, int32_t d_inner) {
@@ -685,22 +712,19 @@ int lamp_ffn_bwd(const float* x, const float* h, const float* o, const float* dy
         LAMP_CK(launch_layernorm_bwd(o, x, 0, M, d_model, w->ln_g, 1e-5f, drop ? &ds : nullptr, dy, dx, drop ? d_o : nullptr,
                                      dgamma, dbeta, db2, workspace, workspace_bytes, s));
     const float* g_o = drop ? d_o : dx;
+    const FfnBwdProds g(Mi, d_model, d_inner);   // the products lamp_ffn_bwd_workspace_bytes sized the workspace for
     if (dW2)   // dW2 = d_o^T h
-        LAMP_CK(gg(cols(g_o, d_model), cols(h, d_inner), dW2, d_inner, 0, 0, d_model, d_inner, Mi, 1, 1, false, nullptr,
-                   workspace, workspace_bytes, s));
+        LAMP_CK(gp(cols(g_o, d_model), cols(h, d_inner), dW2, g.p[FFN_DW2], false, nullptr, workspace, workspace_bytes, s));
     // dh = relu'(h) * (d_o W2)
-    LAMP_CK(gg(rows(g_o, d_model), cols(w->w2, d_inner), dh, d_inner, 0, 0, Mi, d_inner, d_model, 1, 1, false, h, workspace,
-               workspace_bytes, s));
+    LAMP_CK(gp(rows(g_o, d_model), cols(w->w2, d_inner), dh, g.p[FFN_DH], false, h, workspace, workspace_bytes, s));
     if (keep)
         LAMP_CK(launch_colsum(dh, M, d_inner, d_inner, db1, keep + ln_bytes, partials_bytes - ln_bytes, s, &jobs[1]));
     else
         LAMP_CK(launch_colsum(dh, M, d_inner, d_inner, db1, workspace, workspace_bytes, s));
     if (dW1)   // dW1 = dh^T x
-        LAMP_CK(gg(cols(dh, d_inner), cols(x, d_model), dW1, d_model, 0, 0, d_inner, d_model, Mi, 1, 1, false, nullptr,
-                   workspace, workspace_bytes, s));
+        LAMP_CK(gp(cols(dh, d_inner), cols(x, d_model), dW1, g.p[FFN_DW1], false, nullptr, workspace, workspace_bytes, s));
     // dx = residual branch + dh W1
-    return gg(rows(dh, d_inner), cols(w->w1, d_model), dx, d_model, 0, 0, Mi, d_model, d_inner, 1, 1, true, nullptr, workspace,
-              workspace_bytes, s);
+    return gp(rows(dh, d_inner), cols(w->w1, d_model), dx, g.p[FFN_DX], true, nullptr, workspace, workspace_bytes, s);
 }
 
 int lamp_mha_train_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, const float* xq, const float* xk,
@@ -750,12 +774,12 @@ int lamp_mha_train_act_fwd(const lamp_mha_train_desc* c, const lamp_mha_weights*
 }
 
 size_t lamp_mha_bwd_workspace_bytes(const lamp_mha_train_desc* c) {
-    if (!c || c->B <= 0 || c->lq <= 0 || c->lk <= 0 || c->d_model <= 0) return 0;
+    if (!c || c->B <= 0 || c->lq <= 0 || c->lk <= 0 || c->d_model <= 0 || c->n_head <= 0 || c->d_k <= 0 || c->d_v <= 0) return 0;
     const int64_t Mq = int64_t(c->B) * c->lq, Mk = int64_t(c->B) * c->lk;
-    const int hd = c->n_head * (c->d_k > c->d_v ? c->d_k : c->d_v);
-    const int big = hd > c->d_model ? hd : c->d_model;
-    return max3(layernorm_bwd_workspace_bytes(Mq, c->d_model), gemm_gen_workspace_bytes(big, big, int(Mq), 1),
-                gemm_gen_workspace_bytes(big, big, int(Mk), 1));
+    if (Mq > 0x7fffffff || Mk > 0x7fffffff) return 0;
+    const MhaBwdProds g(int(Mq), int(Mk), c->d_model, c->n_head * c->d_k, c->n_head * c->d_v);
+    const size_t ln = layernorm_bwd_workspace_bytes(Mq, c->d_model), gemm = prods_workspace_bytes(g.p, MHA_PRODS);
+    return ln > gemm ? ln : gemm;
 }
 
 size_t lamp_mha_bwd_partials_bytes(const lamp_mha_train_desc* c) {
@@ -801,6 +825,7 @@ int lamp_mha_act_bwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, in
     const DropoutSpec ds = make_dropout(c->p_out, c->seed_out);
     void* ws = workspace;
     const size_t wsb = workspace_bytes;
+    const MhaBwdProds g(Mq, Mk, d, hdk, hdv);   // the single-batch products lamp_mha_bwd_workspace_bytes sized the workspace for
     // add & norm (+ output dropout): dxq <- the residual branch, d_o <- the gradient of the fc output
     if (partials)
         LAMP_CK(launch_layernorm_bwd(has_fc ? o : a, xq, 0, Mq64, d, w->ln_g, 1e-5f, drop_o ? &ds : nullptr, dy, dxq,
@@ -811,8 +836,8 @@ int lamp_mha_act_bwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, in
     const float* g_o = drop_o ? d_o : dxq;
     const float* g_a = g_o;   // gradient of the concatenated head outputs [Mq, H*dv]
     if (has_fc) {
-        if (dfc) LAMP_CK(gg(cols(g_o, d), cols(a, hdv), dfc, hdv, 0, 0, d, hdv, Mq, 1, 1, false, nullptr, ws, wsb, s));
-        LAMP_CK(gg(rows(g_o, d), cols(w->fc, hdv), da, hdv, 0, 0, Mq, hdv, d, 1, 1, false, nullptr, ws, wsb, s));
+        if (dfc) LAMP_CK(gp(cols(g_o, d), cols(a, hdv), dfc, g.p[MHA_DFC], false, nullptr, ws, wsb, s));
+        LAMP_CK(gp(rows(g_o, d), cols(w->fc, hdv), da, g.p[MHA_DA], false, nullptr, ws, wsb, s));
         g_a = da;
     }   // (single head without output dropout: g_a IS dxq; every product that reads it is issued before (*) accumulates into it)
     // head views: index (h, b) -> batch0 = head, batch1 = sample
@@ -835,15 +860,15 @@ int lamp_mha_act_bwd(const lamp_mha_train_desc* c, const lamp_mha_weights* w, in
                false, nullptr, nullptr, 0, s));
     LAMP_CK(gg(Opd{dP, 1, lk, PB0, PB1}, Opd{q, 1, hdk, dk, int64_t(lq) * hdk}, dk_, hdk, dk, int64_t(lk) * hdk, lk, dk, lq, H, B,
                false, nullptr, nullptr, 0, s));
-    if (dwq) LAMP_CK(gg(cols(dq, hdk), cols(xq, d), dwq, d, 0, 0, hdk, d, Mq, 1, 1, false, nullptr, ws, wsb, s));
-    if (dwk) LAMP_CK(gg(cols(dk_, hdk), cols(xk, d), dwk, d, 0, 0, hdk, d, Mk, 1, 1, false, nullptr, ws, wsb, s));
-    if (dwv) LAMP_CK(gg(cols(dv_, hdv), cols(xv, d), dwv, d, 0, 0, hdv, d, Mk, 1, 1, false, nullptr, ws, wsb, s));
+    if (dwq) LAMP_CK(gp(cols(dq, hdk), cols(xq, d), dwq, g.p[MHA_DWQ], false, nullptr, ws, wsb, s));
+    if (dwk) LAMP_CK(gp(cols(dk_, hdk), cols(xk, d), dwk, g.p[MHA_DWK], false, nullptr, ws, wsb, s));
+    if (dwv) LAMP_CK(gp(cols(dv_, hdv), cols(xv, d), dwv, g.p[MHA_DWV], false, nullptr, ws, wsb, s));
     // (*) data gradients of the three projections
-    LAMP_CK(gg(rows(dq, hdk), cols(w->w_qs, d), dxq, d, 0, 0, Mq, d, hdk, 1, 1, true, nullptr, ws, wsb, s));
+    LAMP_CK(gp(rows(dq, hdk), cols(w->w_qs, d), dxq, g.p[MHA_DXQ], true, nullptr, ws, wsb, s));
     // dxk == dxq (self-attention: query and key source are one tensor): its gradient is the sum, accumulated in place
-    LAMP_CK(gg(rows(dk_, hdk), cols(w->w_ks, d), dxk, d, 0, 0, Mk, d, hdk, 1, 1, dxk == dxq, nullptr, ws, wsb, s));
-    if (dxv) return gg(rows(dv_, hdv), cols(w->w_vs, d), dxv, d, 0, 0, Mk, d, hdv, 1, 1, false, nullptr, ws, wsb, s);
-    return gg(rows(dv_, hdv), cols(w->w_vs, d), dxk, d, 0, 0, Mk, d, hdv, 1, 1, true, nullptr, ws, wsb, s);
+    LAMP_CK(gp(rows(dk_, hdk), cols(w->w_ks, d), dxk, g.p[MHA_DXK], dxk == dxq, nullptr, ws, wsb, s));
+    if (dxv) return gp(rows(dv_, hdv), cols(w->w_vs, d), dxv, g.p[MHA_DXV], false, nullptr, ws, wsb, s);
+    return gp(rows(dv_, hdv), cols(w->w_vs, d), dxk, g.p[MHA_DXV], true, nullptr, ws, wsb, s);
 }
 
 int lamp_prior_graph_build(const int64_t* label_ids, const int64_t* offsets, int64_t n_samples, int32_t L, float* adj,
@@ -1301,6 +1326,9 @@ static int forward_tokens(const lamp_model* m, const lamp_fwd_options* o, const 
                           size_t workspace_bytes, lamp_stream_t stream) {
     FwdDims g;
     LAMP_CK(check_forward(m, nullptr, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, &g, o));
+    // lamp_forward_workspace_bytes(m, 1, T, want_attn) -- the K/V-ahead buffers counted -- is the least a call accepts, not the
+    // smaller layout it falls back to below: what the header documents and what the call checks are one number
+    if (workspace_bytes < fwd_size(g).bound(1)) return LAMP_E_WORKSPACE;
     // One launch for every decoder layer's enc-attention K/V projection (they all read the finished encoder output)
     // when the whole batch still fits the workspace with the extra K/V buffers and the weights fit one segment list.
     const bool kv_ahead =
