@@ -10,7 +10,8 @@ evaluates its contiguous share of the batches -- the forward path needs no colle
 
 Flag names and derived defaults follow the reference's config_args.py (single-dash flags; n_layers_dec =
 n_layers_enc :87-88, d_k = d_v = d_model / n_head :96-99, d_inner_hid = 2 d_model :110-111, no position
-embedding for bibtext / delicious / bookmarks / sider :104-105, n_head2 = n_head :135-136).  The model is
+embedding for bibtext / delicious / bookmarks / sider :104-105, n_head2 = n_head :135-136; -n_head2, -d_k and -d_v
+as run_train stored them in the checkpoint's settings take precedence over the flags and the defaults).  The model is
 built from the dataset exactly as main.py:53-88 does (vocabulary sizes, max sequence length, prior label
 adjacency from the train split).  Metrics are the thresholded multi-label basics the reference prints first
 (utils/evals.py:316-372: subset accuracy, Hamming accuracy, example-/micro-/macro-F1 at -br_threshold, with the
@@ -50,6 +51,10 @@ def parse(argv=None):
     ap.add_argument('-n_layers_dec', type=int, default=None)
     ap.add_argument('-n_head', type=int, default=4)
     ap.add_argument('-n_head2', type=int, default=0)
+    ap.add_argument('-d_k', type=int, default=-1,
+                    help="width of a query / key head (default d_model / n_head); a run_train checkpoint brings -d_k, -d_v and "
+                         "-n_head2 in its settings, the flags are for bare state dicts")
+    ap.add_argument('-d_v', type=int, default=-1, help='width of a value head (default d_model / n_head)')
     ap.add_argument('-label_mask', default='none', choices=['none', 'inveye', 'prior'])
     ap.add_argument('-no_dec_self_att', action='store_true')
     ap.add_argument('-no_enc_pos_embedding', action='store_true')
@@ -86,6 +91,10 @@ def parse(argv=None):
         opt.d_inner_hid = 2 * opt.d_model
     if opt.n_head2 == 0:
         opt.n_head2 = opt.n_head
+    if opt.d_k == -1:
+        opt.d_k = opt.d_model // opt.n_head
+    if opt.d_v == -1:
+        opt.d_v = opt.d_model // opt.n_head
     if opt.dataset in ('bibtext', 'delicious', 'bookmarks', 'sider'):
         opt.no_enc_pos_embedding = True
     # config_args.py:90-91: the genomics datasets read DNA through the one-hot / Conv1d encoder
@@ -167,6 +176,19 @@ def load_checkpoint_label_bias(ckpt):
     return kind, float(getattr(settings, 'label_bias_scale', 1.0))
 
 
+def load_checkpoint_head_geometry(ckpt):
+    """{'n_head2' / 'd_k' / 'd_v': value} for each of run_train's `-n_head2`, `-d_k` and `-d_v` that the 'settings' of a LOADED
+    checkpoint (load_checkpoint_object) carry as a positive integer; empty for one that says nothing about them (a bare
+    state_dict).  run_train and the reference store all three, derived defaults included."""
+    settings = ckpt.get('settings') if isinstance(ckpt, dict) and 'model' in ckpt else None
+    out = {}
+    for key in ('n_head2', 'd_k', 'd_v'):
+        value = getattr(settings, key, None)
+        if isinstance(value, int) and not isinstance(value, bool) and value > 0:
+            out[key] = value
+    return out
+
+
 def spawn_ranks(n, argv):
     """One process per GPU, each re-running this module with RANK / WORLD_SIZE set; rank 0 prints the result."""
     with socket.socket() as s:
@@ -226,13 +248,15 @@ def main(argv=None):
         attn_type = opt.attn_type
     bias_kind, bias_scale = opt.label_bias, opt.label_bias_scale
     stored = load_checkpoint_label_bias(ckpt)
+    geometry = dict(n_head2=opt.n_head2, d_k=opt.d_k, d_v=opt.d_v)
+    geometry.update(load_checkpoint_head_geometry(ckpt))   # the checkpoint's settings override the flags
     del ckpt
     if stored is not None:   # the checkpoint's settings override the flags
         bias_kind, bias_scale = stored
     bias = D.build_label_bias(data, bias_kind, bias_scale, device)
     model = LAMP(n_src, n_labels, data['settings'].max_seq_len, n_labels, n_layers_enc=opt.n_layers_enc,
-                 n_layers_dec=opt.n_layers_dec, n_head=h, n_head2=opt.n_head2, d_word_vec=d, d_model=d,
-                 d_inner_hid=opt.d_inner_hid, d_k=d // h, d_v=d // h, encoder='graph', decoder='graph',
+                 n_layers_dec=opt.n_layers_dec, n_head=h, n_head2=geometry['n_head2'], d_word_vec=d, d_model=d,
+                 d_inner_hid=opt.d_inner_hid, d_k=geometry['d_k'], d_v=geometry['d_v'], encoder='graph', decoder='graph',
                  no_enc_pos_embedding=opt.no_enc_pos_embedding, no_dec_self_att=opt.no_dec_self_att,
                  label_adj_matrix=adj, label_mask=opt.label_mask, dec_dropout2=False, onehot=opt.onehot, enc_self_attn=live,
                  dec_attn_type=None if attn_type == 'softmax' else attn_type, label_bias=bias)

@@ -64,10 +64,11 @@ def live_encoder_ref(sd, seq, pos, n_head, adj=None):
     return x, attns
 
 
-def live_forward_ref(sd, seq, pos, n_head, label_blocked, adj=None):
-    """-> (logits, enc_output, encoder maps, (decoder self maps, enc-dec maps), intermediate predictions)."""
+def live_forward_ref(sd, seq, pos, n_head, label_blocked, adj=None, n_head2=None):
+    """-> (logits, enc_output, encoder maps, (decoder self maps, enc-dec maps), intermediate predictions).  n_head2: heads of
+    the label self-attention (default n_head)."""
     enc, enc_attns = live_encoder_ref(sd, seq, pos, n_head, adj)
-    y, slf, encdec, int_outs = R.decoder_forward(sd, seq, enc, label_blocked, n_head)
+    y, slf, encdec, int_outs = R.decoder_forward(sd, seq, enc, label_blocked, n_head, n_head2)
     w = sd['tgt_word_proj.linear.weight']
     return R.readout(y, w), enc, enc_attns, (slf, encdec), [R.readout(o, w) for o in int_outs[:-1]]
 

@@ -6,7 +6,9 @@
 (Lives under tests/ because it uses the oracle, which only test code may import.)
 
 Eval: random model shapes (1-8 heads, d_k 4..256 incl. widths beyond the fused attention kernel, 1-3 + 1-3 layers,
-every mask kind, L and T from 1 to 300 / 150, ragged lengths, with / without decoder self-attention): logits and
+every mask kind, L and T from 1 to 300 / 150, ragged lengths, with / without decoder self-attention; beyond the slice
+tests/test_gpu_fuzz.py runs -- eval cases 60 on, training cases 6 on -- four cases in ten draw d_k, d_v and n_head2 independently
+of each other and of d_model / n_head, from a generator of their own, and are built by tests/head_geometry_common.py): logits and
 enc_output against the fp64 oracle (bar: max(1e-4, 4 x the oracle's own fp32-vs-fp64 gap)), every attention map against
 the fp32 oracle (1e-5), logits bit-identical with and without return_attns (= packed vs padded encoder), and one sample
 of the batch run alone at its own length bit-identical to its rows in the batch.
@@ -49,10 +51,30 @@ def case(i):
     no_slf = rng.random() < 0.2
     lengths = [rng.randint(1, T) for _ in range(B)]
     lengths[rng.randrange(B)] = T
-    return dict(h=h, d=d, dff=dff, L=L, T=T, B=B, mask=mask, pos=pos, n_enc=n_enc, n_dec=n_dec, no_slf=no_slf, lengths=lengths, V=rng.choice([5, 40, 1000]))
+    c = dict(h=h, d=d, dff=dff, L=L, T=T, B=B, mask=mask, pos=pos, n_enc=n_enc, n_dec=n_dec, no_slf=no_slf, lengths=lengths, V=rng.choice([5, 40, 1000]))
+    # A general head geometry: only beyond the cases tests/test_gpu_fuzz.py runs (eval 0..59, training 10000..10005 keep the
+    # shapes they always had), and from a second generator, so that the first one's stream does not move for any index.
+    rng2 = random.Random(77000 + i)
+    if (60 <= i < 10000 or i >= 10006) and rng2.random() < 0.4:
+        h2 = rng2.choice([1, 2, 3, 4, 8])
+        widths = [4, 8, 12, 16, 24, 32, 40, 64] + ([128, 160] if max(h, h2) < 4 else [])
+        dk2, dv2 = rng2.choice(widths), rng2.choice(widths)
+        if h == 1 or h2 == 1:
+            dv2 = d           # a block of one head has no fc: its value width IS d_model
+        c.update(h2=h2, dk=dk2, dv=dv2)
+    return c
 
 def build(c, i):
     h, d = c['h'], c['d']
+    if 'h2' in c:
+        import head_geometry_common as HG
+        g = dict(V=c['V'], L=c['L'], T=c['T'], d=d, dff=c['dff'], h=h, h2=c['h2'], dk=c['dk'], dv=c['dv'], n_enc=c['n_enc'],
+                 n_dec=c['n_dec'], mask=c['mask'], pos=c['pos'], no_dec_self_att=c['no_slf'])
+        sd = HG.make_state_dict(c['V'], c['L'], c['T'], d, c['dff'], h, c['h2'], c['dk'], c['dv'], c['n_enc'], c['n_dec'],
+                                pos_emb=c['pos'], seed=i, no_dec_self_att=c['no_slf'])
+        adj = R.make_adjacency(c['L'], 0.2, i) if c['mask'] == 'prior' else None
+        seq, spos = R.make_batch(c['B'], c['V'], c['T'], lengths=c['lengths'], seed=i)
+        return HG.build_model(g, sd, adj).to(dev), sd, R.label_block_mask(adj, c['mask'], c['L']), seq, spos
     sd = R.make_state_dict(c['V'], c['L'], c['T'], d, c['dff'], h, c['n_enc'], c['n_dec'], pos_emb=c['pos'], seed=i, no_dec_self_att=c['no_slf'])
     adj = R.make_adjacency(c['L'], 0.2, i) if c['mask'] == 'prior' else None
     seq, spos = R.make_batch(c['B'], c['V'], c['T'], lengths=c['lengths'], seed=i)
@@ -70,8 +92,8 @@ for i in range(n_eval):
         m, sd, blocked, seq, spos = build(c, i)
         m.eval()
         with torch.no_grad():
-            ref = R.forward(sd, seq, spos, c['h'], blocked, return_attns=True)
-            ref64, _, _ = R.forward(R.to_dtype(sd, torch.float64), seq, spos, c['h'], blocked)
+            ref = R.forward(sd, seq, spos, c['h'], blocked, n_head2=c.get('h2'), return_attns=True)
+            ref64, _, _ = R.forward(R.to_dtype(sd, torch.float64), seq, spos, c['h'], blocked, n_head2=c.get('h2'))
             lg, enc, _ = m((seq.to(dev), spos.to(dev)), None, None, None)
             got = m((seq.to(dev), spos.to(dev)), None, None, None, return_attns=True)
         gap = mad(ref[0], ref64)
@@ -100,7 +122,7 @@ for i in range(n_train):
         m, sd, blocked, seq, spos = build(c, i)
         tgt = (torch.rand(c['B'], c['L'], generator=torch.Generator().manual_seed(i)) < 0.3).float()
         sd64 = {k: v.double().requires_grad_(v.is_floating_point()) for k, v in sd.items()}
-        rl, _, _ = R.forward(sd64, seq, spos, c['h'], blocked)
+        rl, _, _ = R.forward(sd64, seq, spos, c['h'], blocked, n_head2=c.get('h2'))
         F.binary_cross_entropy_with_logits(rl, tgt.double()).backward()
         m.train()
         lg, _, _ = m((seq.to(dev), spos.to(dev)), None, None, tgt.to(dev))

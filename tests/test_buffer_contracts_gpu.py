@@ -499,9 +499,10 @@ def test_diag_logits_fwd_bwd_and_sigmoid_bce(dev, N):
 
 
 # ------------------------------------------------------------------ eval sub-layers: lamp_mha_fwd, lamp_mha_act_fwd, lamp_ffn_fwd
-def sublayer_weights(d, dff, H, dk, g):
+def sublayer_weights(d, dff, H, dk, g, dv=None):
+    dv = dk if dv is None else dv
     w = dict(wq=torch.randn(H * dk, d, generator=g) * 0.2, wk=torch.randn(H * dk, d, generator=g) * 0.2,
-             wv=torch.randn(H * dk, d, generator=g) * 0.2, fc=torch.randn(d, H * dk, generator=g) * 0.2 if H > 1 else None,
+             wv=torch.randn(H * dv, d, generator=g) * 0.2, fc=torch.randn(d, H * dv, generator=g) * 0.2 if H > 1 else None,
              ln_g=1 + 0.1 * torch.randn(d, generator=g), ln_b=0.1 * torch.randn(d, generator=g),
              w1=torch.randn(dff, d, generator=g) * 0.1, b1=torch.randn(dff, generator=g) * 0.1,
              w2=torch.randn(d, dff, generator=g) * 0.1, b2=torch.randn(d, generator=g) * 0.1)
@@ -530,14 +531,16 @@ def torch_mha_weights(N, w, H, dev):
 
 @pytest.mark.parametrize('act', [0, 1])
 @pytest.mark.parametrize('self_attn', [False, True])
-@pytest.mark.parametrize('H', [4, 1])
-def test_mha_fwd_exact_workspace(dev, N, H, self_attn, act):
+@pytest.mark.parametrize('H,d,dk,dv', [(4, 64, 16, 16), (1, 16, 16, 16), (3, 64, 24, 40), (1, 64, 48, 64), (2, 64, 160, 32)],
+                         ids=['4', '1', '3-d64-dk24-dv40', '1-d64-dk48-dv64', '2-d64-dk160-dv32'])
+def test_mha_fwd_exact_workspace(dev, N, H, d, dk, dv, self_attn, act):
     """lamp_mha_fwd / lamp_mha_act_fwd with a workspace of exactly lamp_mha_workspace_bytes(), maps requested, and xkv
-    aliasing xq (self-attention: one buffer is query, key and value source)."""
-    g = rnd(30 + H)
-    B, lq, lk, dk = 2, 37, 37 if self_attn else 23, 16
-    d = 64 if H > 1 else dk
-    w = sublayer_weights(d, 96, H, dk, g)
+    aliasing xq (self-attention: one buffer is query, key and value source).  Beside d_k = d_v = d_model / n_head: n_head * d_k
+    != n_head * d_v != d_model (K and V are two launches), one head without fc at d_v = d_model != d_k, and d_k > 128 (the
+    score scratch of the general route is part of the workspace)."""
+    g = rnd(30 + H if dk == dv else 300 + H + dk + dv)
+    B, lq, lk = 2, 37, 37 if self_attn else 23
+    w = sublayer_weights(d, 96, H, dk, g, dv)
     xq, xkv = torch.randn(B, lq, d, generator=g), torch.randn(B, lk, d, generator=g)
     blocked = torch.rand(lq, lk, generator=g) < 0.3
     blocked[:, 0] = False
@@ -550,13 +553,13 @@ def test_mha_fwd_exact_workspace(dev, N, H, self_attn, act):
         Mb = ar.inp(blocked.to(torch.uint8), 'mask')
         mask = N.Mask(N.LAMP_MASK_U8, 0, p(Mb), 0, lk, None, 0, 0)
         out, attn = ar.out((B, lq, d), 'out'), ar.out((H * B, lq, lk), 'attn')
-        nb = L.lamp_mha_workspace_bytes(B, lq, lk, d, H, dk, dk)
+        nb = L.lamp_mha_workspace_bytes(B, lq, lk, d, H, dk, dv)
         ws = ar.scratch(nb, 'workspace')
         if act:
-            ok(L.lamp_mha_act_fwd(p(XQ), p(XKV), B, lq, lk, d, dk, dk, C.byref(wts), act, C.byref(mask), p(out), p(attn), p(ws),
+            ok(L.lamp_mha_act_fwd(p(XQ), p(XKV), B, lq, lk, d, dk, dv, C.byref(wts), act, C.byref(mask), p(out), p(attn), p(ws),
                                   nb, N.stream()), 'lamp_mha_act_fwd')
         else:
-            ok(L.lamp_mha_fwd(p(XQ), p(XKV), B, lq, lk, d, dk, dk, C.byref(wts), C.byref(mask), p(out), p(attn), p(ws), nb,
+            ok(L.lamp_mha_fwd(p(XQ), p(XKV), B, lq, lk, d, dk, dv, C.byref(wts), C.byref(mask), p(out), p(attn), p(ws), nb,
                               N.stream()), 'lamp_mha_fwd')
         return {'out': out, 'attn': attn}
     got = run_both(dev, body)
@@ -575,7 +578,7 @@ def test_mha_fwd_exact_workspace(dev, N, H, self_attn, act):
     md = blocked.to(dev)
     mstruct, mkeep = N.make_mask(md, B, lq, lk)
     xqd = xq.to(dev)
-    wout, wattn = N.mha(xqd, xqd if self_attn else xkv.to(dev), wts, dk, dk, mstruct, True, act=act)
+    wout, wattn = N.mha(xqd, xqd if self_attn else xkv.to(dev), wts, dk, dv, mstruct, True, act=act)
     same_bits(got['out'], wout, 'lamp_mha_fwd out')
     same_bits(got['attn'], wattn, 'lamp_mha_fwd attn')
 
@@ -713,19 +716,20 @@ def test_ffn_bwd_weight_gradients_split_k_like_the_per_launch_route(dev, N, pdro
 
 
 # ------------------------------------------------------------------ training composites: lamp_mha_train_fwd + lamp_mha_bwd
-def mha_reference(N, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, s_attn, s_out):
+def mha_reference(N, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, s_attn, s_out, dv=None):
+    dv = dk if dv is None else dv
     B, lq, d = xq.shape
     lk = xkv.size(1)
     names = ['wq', 'wk', 'wv', 'ln_g', 'ln_b'] + (['fc'] if w['fc'] is not None else [])
     lv = dict((k, w[k].double().requires_grad_()) for k in names)
     XQ, XKV = xq.double().requires_grad_(), xkv.double().requires_grad_()
-    split = lambda t, l: t.view(B, l, H, dk).permute(2, 0, 1, 3)  # noqa: E731
+    split = lambda t, l: t.view(B, l, H, -1).permute(2, 0, 1, 3)  # noqa: E731
     q, k, v = XQ @ lv['wq'].t(), XKV @ lv['wk'].t(), XKV @ lv['wv'].t()
     s = (split(q, lq) @ split(k, lk).transpose(-1, -2)) / dk ** 0.5
     P = torch.softmax(s.masked_fill(blocked, float('-inf')), -1)
     keep_a = N.dropout_keep_mask(H * B * lq * lk, p_attn, s_attn).view(H, B, lq, lk) if p_attn else 1.0
     Pd = P * keep_a / (1 - p_attn)
-    a = (Pd @ split(v, lk)).permute(1, 2, 0, 3).reshape(B, lq, H * dk)
+    a = (Pd @ split(v, lk)).permute(1, 2, 0, 3).reshape(B, lq, H * dv)
     o = a @ lv['fc'].t() if 'fc' in lv else a
     keep_o = N.dropout_keep_mask(B * lq * d, p_out, s_out).view(B, lq, d) if p_out else 1.0
     y = F.layer_norm(o * keep_o / (1 - p_out) + XQ, (d,), lv['ln_g'], lv['ln_b'], 1e-5)
@@ -738,17 +742,18 @@ def mha_reference(N, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, s_attn, s_ou
     return ref
 
 
-def mha_arena_run(N, ar, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, s_attn, s_out, defer):
+def mha_arena_run(N, ar, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, s_attn, s_out, defer, dv=None):
     L = N.lib()
+    dv = dk if dv is None else dv
     B, lq, d = xq.shape
-    lk, hd = xkv.size(1), H * dk
-    desc = N.MhaTrainDesc(B, lq, lk, d, H, dk, dk, 1.0 / dk ** 0.5, p_attn, p_out, s_attn, s_out)
+    lk, hd, hdv = xkv.size(1), H * dk, H * dv
+    desc = N.MhaTrainDesc(B, lq, lk, d, H, dk, dv, 1.0 / dk ** 0.5, p_attn, p_out, s_attn, s_out)
     wts = arena_mha_weights(N, ar, w, H)
     has_fc = w['fc'] is not None
     XQ, XKV, DY = ar.inp(xq, 'xq'), ar.inp(xkv, 'xkv'), ar.inp(dy, 'dy')
     Mb = ar.inp(blocked.to(torch.uint8), 'mask')
     mask = N.Mask(N.LAMP_MASK_U8, 0, p(Mb), 0, lk, None, 0, 0)
-    q, k, v, a = ar.out((B, lq, hd), 'q'), ar.out((B, lk, hd), 'k'), ar.out((B, lk, hd), 'v'), ar.out((B, lq, hd), 'a')
+    q, k, v, a = ar.out((B, lq, hd), 'q'), ar.out((B, lk, hd), 'k'), ar.out((B, lk, hdv), 'v'), ar.out((B, lq, hdv), 'a')
     P = ar.out((H * B, lq, lk), 'P')
     Pd = ar.out((H * B, lq, lk), 'Pd') if p_attn else None
     lse = ar.scratch(H * B * lq * 4, 'lse')
@@ -757,13 +762,13 @@ def mha_arena_run(N, ar, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, s_attn, 
     ok(L.lamp_mha_train_fwd(C.byref(desc), C.byref(wts), p(XQ), p(XKV), p(XKV), C.byref(mask), p(q), p(k), p(v), p(a), p(P), p(Pd),
                             p(lse), p(o), p(y), N.stream()), 'lamp_mha_train_fwd')
     dxq, d_o = ar.out((B * lq, d), 'dxq'), (ar.out((B * lq, d), 'd_o') if p_out else None)
-    da = ar.scratch(B * lq * hd * 4, 'da') if has_fc else None
+    da = ar.scratch(B * lq * hdv * 4, 'da') if has_fc else None
     dP = ar.scratch(H * B * lq * lk * 4, 'dP')
-    dq, dk_, dv_ = ar.out((B * lq, hd), 'dq'), ar.out((B * lk, hd), 'dk'), ar.out((B * lk, hd), 'dv')
+    dq, dk_, dv_ = ar.out((B * lq, hd), 'dq'), ar.out((B * lk, hd), 'dk'), ar.out((B * lk, hdv), 'dv')
     dxk = ar.out((B * lk, d), 'dxk')
     dg, db = ar.out((d,), 'dgamma'), ar.out((d,), 'dbeta')
-    dwq, dwk, dwv = ar.out((hd, d), 'dwq'), ar.out((hd, d), 'dwk'), ar.out((hd, d), 'dwv')
-    dfc = ar.out((d, hd), 'dfc') if has_fc else None
+    dwq, dwk, dwv = ar.out((hd, d), 'dwq'), ar.out((hd, d), 'dwk'), ar.out((hdv, d), 'dwv')
+    dfc = ar.out((d, hdv), 'dfc') if has_fc else None
     nb = L.lamp_mha_bwd_workspace_bytes(C.byref(desc))
     ws = ar.scratch(nb, 'workspace')
     part, npb, job = None, 0, None
@@ -829,18 +834,32 @@ def check_mha(got, ref, Kq=None, Kk=None):
 @pytest.mark.parametrize('defer', [False, True])
 @pytest.mark.parametrize('p_attn,p_out', [(0.0, 0.0), (0.25, 0.2)])
 def test_mha_train_fwd_and_bwd(dev, N, p_attn, p_out, defer):
-    g = rnd(70)
-    B, lq, lk, H, dk, d = 2, 37, 23, 4, 16, 64
-    w = sublayer_weights(d, 96, H, dk, g)
+    mha_train_case(dev, N, 4, 64, 16, 16, p_attn, p_out, defer, seed=70)
+
+
+def mha_train_case(dev, N, H, d, dk, dv, p_attn, p_out, defer, seed):
+    g = rnd(seed)
+    B, lq, lk = 2, 37, 23
+    w = sublayer_weights(d, 96, H, dk, g, dv)
     xq, xkv, dy = torch.randn(B, lq, d, generator=g), torch.randn(B, lk, d, generator=g), torch.randn(B, lq, d, generator=g)
     blocked = torch.rand(lq, lk, generator=g) < 0.3
     blocked[:, 0] = False
-    got = run_both(dev, lambda ar: mha_arena_run(N, ar, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, 99, 100, defer))
-    check_mha(got, mha_reference(N, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, 99, 100))
+    got = run_both(dev, lambda ar: mha_arena_run(N, ar, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, 99, 100, defer, dv))
+    check_mha(got, mha_reference(N, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, 99, 100, dv))
     for composite in (True, False):     # the wrapper route, and the per-launch route: the same bits
         want = mha_autograd_route(N, xq, xkv, w, blocked, dy, H, p_attn, p_out, 99, 100, dev, composite)
         for k in want:
             same_bits(got[k], want[k], 'lamp_mha_bwd %s (composite=%s)' % (k, composite))
+
+
+@pytest.mark.parametrize('defer', [False, True])
+@pytest.mark.parametrize('p_attn,p_out', [(0.0, 0.0), (0.25, 0.2)])
+@pytest.mark.parametrize('H,d,dk,dv', [(3, 64, 24, 40), (1, 64, 48, 64)])
+def test_mha_train_fwd_and_bwd_general_head_geometry(dev, N, H, d, dk, dv, p_attn, p_out, defer):
+    """test_mha_train_fwd_and_bwd with n_head * d_k != n_head * d_v != d_model (MhaBwdProds over (d, hdk, hdv), the attention
+    dropout counter over H * B * lq * lk, q / k buffers hdk wide and v / a buffers hdv wide), and with one head without fc at
+    d_v = d_model != d_k.  (d_k or d_v > 128 is not a composite shape: lamp_amd/training.py keeps the per-launch route.)"""
+    mha_train_case(dev, N, H, d, dk, dv, p_attn, p_out, defer, seed=700 + H + dk + dv)
 
 
 @pytest.mark.parametrize('p_attn,p_out', [(0.0, 0.0), (0.1, 0.1)])
@@ -864,6 +883,38 @@ def test_mha_bwd_weight_gradients_split_k_like_the_per_launch_route(dev, N, p_at
     got = run_both(dev, lambda ar: mha_arena_run(N, ar, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, 99, 100, False),
                    capacity=96 << 20)
     check_mha(got, mha_reference(N, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, 99, 100), Kq=B * lq, Kk=B * lk)
+    for composite in (True, False):
+        want = mha_autograd_route(N, xq, xkv, w, blocked, dy, H, p_attn, p_out, 99, 100, dev, composite)
+        for k in want:
+            same_bits(got[k], want[k], 'lamp_mha_bwd %s (composite=%s)' % (k, composite))
+
+
+@pytest.mark.parametrize('p_attn,p_out', [(0.0, 0.0), (0.1, 0.1)])
+@pytest.mark.parametrize('H,dk,dv', [(16, 128, 64), (16, 64, 128), (3, 24, 40), (1, 48, 64)])
+def test_mha_bwd_weight_gradients_split_k_with_hdk_not_hdv(dev, N, H, dk, dv, p_attn, p_out):
+    """The shape of test_mha_bwd_weight_gradients_split_k_like_the_per_launch_route (B * lk = 1200 key rows, d_model = 64) with
+    n_head * d_k != n_head * d_v: 2048 / 1024, 1024 / 2048, 72 / 120 and one head of 48 / 64.  dwk [hdk, 64] and dwv [hdv, 64]
+    over K = 1200 are two products of different heights, each with its own K split: the workspace of exactly
+    lamp_mha_bwd_workspace_bytes() must hold the larger, and every output has the bits of the per-launch route."""
+    g = rnd(800 + H + dk + dv)
+    B, lq, lk, d = 8, 20, 150, 64
+    w = sublayer_weights(d, 96, H, dk, g, dv)
+    for k in ('wq', 'wk', 'wv', 'fc'):
+        if w[k] is not None:
+            w[k] = w[k] * 0.25
+    xq, xkv, dy = torch.randn(B, lq, d, generator=g), torch.randn(B, lk, d, generator=g), torch.randn(B, lq, d, generator=g)
+    blocked = torch.rand(lq, lk, generator=g) < 0.3
+    blocked[:, 0] = False
+    L = N.lib()
+    desc = N.MhaTrainDesc(B, lq, lk, d, H, dk, dv, 1.0 / dk ** 0.5, p_attn, p_out, 99, 100)
+    need = max(L.lamp_gemm_workspace_bytes(H * dk, d, B * lk, 1), L.lamp_gemm_workspace_bytes(H * dv, d, B * lk, 1),
+               L.lamp_gemm_workspace_bytes(H * dk, d, B * lq, 1), L.lamp_gemm_workspace_bytes(d, H * dv, B * lq, 1))
+    if H == 16:
+        assert L.lamp_gemm_workspace_bytes(2048, d, B * lk, 1) > 0 and L.lamp_gemm_workspace_bytes(2048, 2048, B * lk, 1) == 0
+    assert L.lamp_mha_bwd_workspace_bytes(C.byref(desc)) >= need
+    got = run_both(dev, lambda ar: mha_arena_run(N, ar, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, 99, 100, False, dv),
+                   capacity=96 << 20)
+    check_mha(got, mha_reference(N, xq, xkv, w, blocked, dy, H, dk, p_attn, p_out, 99, 100, dv), Kq=B * lq, Kk=B * lk)
     for composite in (True, False):
         want = mha_autograd_route(N, xq, xkv, w, blocked, dy, H, p_attn, p_out, 99, 100, dev, composite)
         for k in want:

@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import head_geometry_common as HG
 from conftest import max_abs_diff
 from oracle import lamp_ref as R
 
@@ -84,7 +85,15 @@ def test_every_parameter_gradient_matches_oracle_autograd(dev, name):
     assert max_abs_diff(ev, logits.detach()) < 2e-5
 
 
-@pytest.mark.parametrize('case', ['reuters_like', 'tiny_none_h1', 'inveye_h8'])
+def build_geometry(name, dev, dropout=0.0):
+    """build() for a case of tests/head_geometry_common.py: n_head, n_head2, d_k and d_v independent of each other and of d_model."""
+    m, sd, blocked, seq, spos, g, tgt, kind = HG.grad_case(name)
+    if dropout:
+        m = HG.build(HG.GRAD_CASES[name][0], seed=HG.GRAD_SEEDS[name], dropout=dropout, dec_dropout=dropout)[0]
+    return m.to(dev), sd, blocked, seq, spos, g['h'], tgt
+
+
+@pytest.mark.parametrize('case', ['reuters_like', 'tiny_none_h1', 'inveye_h8', 'G1', 'G2'])
 @pytest.mark.parametrize('dropout', [0.0, 0.1])
 def test_deferred_weight_gradients_equal_the_autograd_route(dev, dropout, case):
     """lamp_amd/training.py queues dW = dY^T.X of every projection and computes them in one grouped launch when the
@@ -92,7 +101,10 @@ def test_deferred_weight_gradients_equal_the_autograd_route(dev, dropout, case):
     identical data gradients, `.grad` accumulation across two backward passes, and nothing deferred for non-leaf
     weights."""
     from lamp_amd import training
-    m, sd, blocked, seq, spos, h, tgt = build(CASES[case], dev, dropout=dropout)
+    if case in CASES:
+        m, sd, blocked, seq, spos, h, tgt = build(CASES[case], dev, dropout=dropout)
+    else:   # G1: hdk != hdv != d_model and blocks of 3 and 2 heads; G2: the enc-attention has one head and no fc
+        m, sd, blocked, seq, spos, h, tgt = build_geometry(case, dev, dropout=dropout)
     m.train()
 
     def grads(defer, passes=1, composite=True, stale=0):
@@ -218,15 +230,20 @@ def test_ffn_with_dropout_matches_torch_restatement_with_the_same_mask(dev):
         assert max_abs_diff(a.grad, b.grad) <= 2e-4 * b.grad.abs().max().item() + 1e-9
 
 
-@pytest.mark.parametrize('H,p_attn,p_out', [(4, 0.0, 0.0), (4, 0.25, 0.2), (1, 0.25, 0.0)])
-def test_mha_with_dropout_matches_torch_restatement_with_the_same_masks(dev, H, p_attn, p_out):
+@pytest.mark.parametrize('H,p_attn,p_out,dk,dv', [(4, 0.0, 0.0, 16, 16), (4, 0.25, 0.2, 16, 16), (1, 0.25, 0.0, 16, 16),
+                                                  (3, 0.25, 0.2, 24, 40)],
+                         ids=['4-0.0-0.0', '4-0.25-0.2', '1-0.25-0.0', '3-0.25-0.2-dk24-dv40'])
+def test_mha_with_dropout_matches_torch_restatement_with_the_same_masks(dev, H, p_attn, p_out, dk, dv):
+    """(H, d_k, d_v) = (3, 24, 40) at d_model 64: q / k are 72 wide, v and the attention output 120; the attention-dropout
+    counter runs over H * B * lq * lk and the output dropout over B * lq * d_model whatever the head widths."""
     from lamp_amd import _native as N
     from lamp_amd import training
     g = torch.Generator().manual_seed(2 + H)
-    B, lq, lk, d, dk = 3, 21, 34, 64, 16
+    B, lq, lk, d = 3, 21, 34, 64
     xq, xkv = torch.randn(B, lq, d, generator=g), torch.randn(B, lk, d, generator=g)
-    wq, wk, wv = (torch.randn(H * dk, d, generator=g) * 0.2 for _ in range(3))
-    fc = torch.randn(d, H * dk, generator=g) * 0.2 if H > 1 else None
+    wq, wk = (torch.randn(H * dk, d, generator=g) * 0.2 for _ in range(2))
+    wv = torch.randn(H * dv, d, generator=g) * 0.2
+    fc = torch.randn(d, H * dv, generator=g) * 0.2 if H > 1 else None
     lg, lb = 1 + 0.1 * torch.randn(d, generator=g), 0.1 * torch.randn(d, generator=g)
     blocked = torch.rand(lq, lk, generator=g) < 0.3
     blocked[:, 0] = False
@@ -245,12 +262,12 @@ def test_mha_with_dropout_matches_torch_restatement_with_the_same_masks(dev, H, 
         XQ, XKV, WQ, WK, WV, FC, LG, LB = leaves
     else:
         (XQ, XKV, WQ, WK, WV, LG, LB), FC = leaves, None
-    split = lambda t, l: t.view(B, l, H, dk).permute(2, 0, 1, 3)  # noqa: E731
+    split = lambda t, l: t.view(B, l, H, -1).permute(2, 0, 1, 3)  # noqa: E731
     q, k, v = split(XQ @ WQ.t(), lq), split(XKV @ WK.t(), lk), split(XKV @ WV.t(), lk)
     s = (q @ k.transpose(-1, -2)) / dk ** 0.5
     P = torch.softmax(s.masked_fill(blocked, float('-inf')), -1)                     # (H, B, lq, lk)
     keep_a = N.dropout_keep_mask(H * B * lq * lk, p_attn, s_attn).view(H, B, lq, lk)
-    a = ((P * keep_a / (1 - p_attn)) @ v).permute(1, 2, 0, 3).reshape(B, lq, H * dk)
+    a = ((P * keep_a / (1 - p_attn)) @ v).permute(1, 2, 0, 3).reshape(B, lq, H * dv)
     o = a @ FC.t() if FC is not None else a
     keep_o = N.dropout_keep_mask(B * lq * d, p_out, s_out).view(B, lq, d)
     ref = F.layer_norm(o * keep_o / (1 - p_out) + XQ, (d,), LG, LB, 1e-5)
@@ -364,6 +381,40 @@ def test_gradients_with_wide_heads(dev):
             continue
         ref = sd64[pname].grad
         assert max_abs_diff(p.grad, ref) <= 3e-4 * ref.abs().max().item() + 1e-9, pname
+
+
+@pytest.mark.parametrize('name', sorted(HG.GRAD_CASES))
+def test_gradients_at_general_head_geometries(dev, name):
+    """n_head, n_head2, d_k and d_v independent of each other and of d_model (tests/head_geometry_common.py): every parameter's
+    gradient against torch.autograd on the fp64 oracle at dropout 0, at the rule of test_gradients_with_wide_heads.  G4a / G4b:
+    the per-launch route because of d_k alone, then of d_v alone; G6: 260 label queries; G1_live / G1_sigmoid: the live encoder
+    self-attention and sigmoid decoder attention at G1.  Seeds: HG.GRAD_SEEDS, chosen on the CPU so that the fp32 oracle's own
+    autograd is inside the bar for every parameter (a ReLU kink cannot fake a mismatch)."""
+    m, sd, blocked, seq, spos, g, tgt, kind = HG.grad_case(name)
+    ref_logits, _, ref_loss, g64 = HG.oracle_run(kind, sd, seq, spos, g, blocked, tgt)
+    m = m.to(dev).train()
+    logits, _, _ = m((seq.to(dev), spos.to(dev)), None, None, tgt.to(dev))
+    loss = F.binary_cross_entropy_with_logits(logits, tgt.to(dev))
+    loss.backward()
+    assert max_abs_diff(logits, ref_logits) < 1e-4 and abs(loss.item() - ref_loss) < 1e-5
+    checked, worst = 0, (0.0, None)
+    for pname, p in m.named_parameters():
+        if pname == 'encoder.position_enc.weight':
+            assert p.grad is None
+            continue
+        if 'encoder.layer_stack' in pname and 'slf_attn' in pname and kind != 'live':
+            assert p.grad is None and g64[pname] is None, pname     # dead code in the reference: no gradient there either
+            continue
+        ref = HG.reference_gradient(g64, pname)
+        assert p.grad is not None and ref is not None and p.grad.shape == ref.shape, pname
+        err, scale = max_abs_diff(p.grad, ref), ref.abs().max().item()
+        worst = max(worst, (err / (3e-4 * scale + 1e-9), pname))
+        assert err <= 3e-4 * scale + 1e-9, (pname, err, scale)
+        checked += 1
+    print('%s: %d gradients, worst %.3f of the bar (%s)' % (name, checked, worst[0], worst[1]))
+    n_fc = sum(1 for k in sd if k.endswith('fc.weight') and (kind == 'live' or not k.startswith('encoder.')))
+    skipped = ('tgt_word_proj.weight', 'encoder.position_enc.weight')
+    assert checked == len([k for k in g64 if g64[k] is not None and k not in skipped]) and n_fc >= 2
 
 
 @pytest.mark.parametrize('H', [1, 4])

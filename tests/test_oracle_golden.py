@@ -76,6 +76,40 @@ def test_model(name):
             assert max_abs_diff(p, d['int_pred_%d' % i]) < TOL
 
 
+@pytest.mark.parametrize('name', ['G1', 'G2'])
+def test_model_at_a_general_head_geometry(name):
+    """The reference's own modules away from d_k = d_v = d_model / n_head and n_head2 = n_head (tests/golden/geometry.npz: G1 =
+    3 / 2 heads, d_k 24, d_v 40; G2 = 1 / 2 heads, d_k 48, d_v 64 = d_model): logits, encoder rows, every attention map and the
+    intermediate predictions, at the bars of test_model."""
+    from head_geometry_common import load_golden_geometry
+    d, sd, g, blocked = load_golden_geometry(name)
+    assert (g['h'] * g['dk'], g['h'] * g['dv']) != (g['d'], g['d']) and g['h'] != g['h2'] and g['dk'] != g['dv']
+    assert sd['decoder.layer_stack.0.enc_attn.w_qs.weight'].shape == (g['h'] * g['dk'], g['d'])
+    assert sd['decoder.layer_stack.0.slf_attn.w_vs.weight'].shape == (g['h2'] * g['dv'], g['d'])
+    assert ('decoder.layer_stack.0.enc_attn.fc.weight' in sd) == (g['h'] > 1)
+    if 'ref_label_mask' in d:
+        assert torch.equal(blocked, d['ref_label_mask'].view(blocked.shape) != 0)
+    for as_written in (False, True):
+        logits, enc, _ = R.forward(sd, d['src_seq'], d['src_pos'], g['h'], blocked, n_head2=g['h2'], as_written=as_written)
+        assert logits.shape == d['logits'].shape
+        assert max_abs_diff(enc, d['enc_output']) < TOL
+        assert max_abs_diff(logits, d['logits']) < 5e-5
+    _, _, enc_attns, dec2 = R.forward(sd, d['src_seq'], d['src_pos'], g['h'], blocked, n_head2=g['h2'], return_attns=True)
+    B, Lq, T = d['src_seq'].size(0), g['L'], d['src_seq'].size(1)
+    assert len(enc_attns[0]) == g['n_enc'] == 1 and len(dec2[0]) == len(dec2[1]) == g['n_dec'] == 2
+    assert len([k for k in d if k.startswith('attn_')]) == 5
+    for i, a in enumerate(enc_attns[0]):
+        assert a.shape == (g['h'] * B, T, T) and max_abs_diff(a, d['attn_enc_%d' % i]) < TOL
+    for i, a in enumerate(dec2[0]):
+        assert a.shape == (g['h2'] * B, Lq, Lq) and max_abs_diff(a, d['attn_dec_slf_%d' % i]) < TOL
+    for i, a in enumerate(dec2[1]):
+        assert a.shape == (g['h'] * B, Lq, T) and max_abs_diff(a, d['attn_dec_enc_%d' % i]) < TOL
+    _, _, ips = R.forward(sd, d['src_seq'], d['src_pos'], g['h'], blocked, n_head2=g['h2'], int_preds=True)
+    assert len(ips) == len([k for k in d if k.startswith('int_pred_')]) == 3
+    for i, p in enumerate(ips):
+        assert max_abs_diff(p, d['int_pred_%d' % i]) < TOL
+
+
 def test_allpad_row_is_nan_only_there():
     d, sd = load_golden('model_allpad_row')
     logits, _, _ = R.forward(sd, d['src_seq'], d['src_pos'], d['n_head'], _blocked(d, sd))

@@ -390,6 +390,41 @@ def _run_train_end_to_end(root):
     assert more[0]['train_loss'] < hist[0]['train_loss']
 
 
+def test_run_train_with_a_general_head_geometry_and_run_eval_reads_it_from_the_checkpoint():
+    """run_train -n_head 2 -n_head2 4 -d_k 8 -d_v 24 at d_model 32 (n_head * d_k = 16, n_head * d_v = 48, the label
+    self-attention 32 / 96 wide), one epoch; run_eval is given none of the three flags: it takes them from the checkpoint's
+    settings, and its metrics are those of the in-process evaluation."""
+    from lamp_amd import run_eval, run_train
+    with tempfile.TemporaryDirectory(prefix='lamp_run_') as root:
+        assert 'test' not in root
+        data_path = os.path.join(root, 'train_valid_data.pt')
+        torch.save(TC.synthetic_dataset(n_train=64, n_valid=16, n_test=16), data_path)
+        args = ['-data', data_path, '-dataset', 'syn', '-d_model', '32', '-n_head', '2', '-n_layers_enc', '2', '-label_mask',
+                'prior', '-batch_size', '16']
+        hist = run_train.main(args + ['-epoch', '1', '-lr', '0.003', '-dropout', '0.0', '-results_dir', os.path.join(root, 'res'),
+                                      '-name', 'geo', '-seed', '1', '-n_head2', '4', '-d_k', '8', '-d_v', '24'])
+        assert len(hist) == 1 and np.isfinite(hist[0]['train_loss']) and np.isfinite(hist[0]['test_loss'])
+        ckpt = torch.load(hist[0]['checkpoint'], map_location='cpu', weights_only=False)
+        st = ckpt['settings']
+        assert (st.n_head, st.n_head2, st.d_k, st.d_v) == (2, 4, 8, 24)
+        sd = ckpt['model']
+        assert sd['decoder.layer_stack.0.enc_attn.w_qs.weight'].shape == (16, 32)
+        assert sd['decoder.layer_stack.0.enc_attn.w_vs.weight'].shape == (48, 32)
+        assert sd['decoder.layer_stack.1.slf_attn.w_ks.weight'].shape == (32, 32)
+        assert sd['decoder.layer_stack.1.slf_attn.fc.weight'].shape == (32, 96)
+        out = run_eval.main(args + ['-checkpoint', hist[0]['checkpoint'], '-split', 'test'])
+        assert out['bce_total'] / out['n_samples'] == hist[0]['test_loss']        # exactly the epoch's own test loss
+        mine = hist[0]['metrics']['test']
+        for key, name in (('ACC', 'subset_accuracy'), ('HA', 'hamming_accuracy'), ('ebF1', 'example_f1'), ('miF1', 'micro_f1'),
+                          ('maF1', 'macro_f1')):
+            assert (np.isnan(out[name]) and np.isnan(mine[key])) or abs(out[name] - mine[key]) < 1e-12, (key, out[name], mine[key])
+        # a bare state dict carries no settings: the flags say it
+        bare = os.path.join(root, 'bare.pt')
+        torch.save(sd, bare)
+        out2 = run_eval.main(args + ['-checkpoint', bare, '-split', 'test', '-n_head2', '4', '-d_k', '8', '-d_v', '24'])
+        assert out2['bce_total'] == out['bce_total']
+
+
 # ------------------------------------------------------------------ the one-hot model
 class _Batches(object):
     def __init__(self, batches, n, batch_size):
