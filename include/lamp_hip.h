@@ -255,6 +255,19 @@ int lamp_linear_prec_fwd(const float* A, int64_t M, int32_t K, int64_t lda,
                          const float* residual, int64_t ldr, int32_t relu,
                          float* C, int64_t ldc, int32_t precision, lamp_stream_t stream);
 
+/* lamp_linear_fwd for 1 <= n_seg <= 4 weight matrices W[s] [N, K] that share A, one launch: C[s] = act(A . W[s]^T + bias[s]) (+ residual;
+ * meaningful with one segment), bit for bit what n_seg calls of lamp_linear_fwd give.  W, C: host arrays of n_seg device pointers;
+ * bias: such an array with nullable entries, or NULL.
+ *   W_pack (nullable; host array of n_seg nullable entries): lamp_pack_weight(W[s], N, K, ldw, format 0).  When every segment has
+ *     one, N % 16 == 0, K % 32 == 0 and C / bias / residual can move as 16-byte accesses, launches of fewer than 2048 64 x 64 tiles
+ *     load their weight fragments straight from the packs (csrc/gemm.hip, the packed-W tile); otherwise the packs are ignored.
+ *     Same bits either way.
+ *   m_dev (nullable): the live row count in device memory; rows at and past min(*m_dev, M) are neither computed nor written
+ *     (M then only sizes the launch). */
+int lamp_linear_packed_fwd(const float* A, int64_t M, int32_t K, int64_t lda, const float* const* W, const float* const* W_pack,
+                           int32_t n_seg, int32_t N, int64_t ldw, const float* const* bias, const float* residual, int64_t ldr,
+                           int32_t relu, float* const* C, int64_t ldc, const int32_t* m_dev, lamp_stream_t stream);
+
 /* nn.LayerNorm over the last dim, biased variance, eps inside the sqrt (lamp/SubLayers.py:68,130).
  * y may alias x.  d must be a multiple of 4. */
 int lamp_layernorm_fwd(const float* x, int64_t M, int32_t d, const float* gamma, const float* beta,
@@ -632,6 +645,35 @@ size_t lamp_forward_opts_workspace_bytes(const lamp_model* m, const lamp_fwd_opt
 int lamp_forward_opts(const lamp_model* m, const lamp_fwd_options* opts, const int64_t* src_seq, const int64_t* src_pos,
                       int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
                       size_t workspace_bytes, lamp_stream_t stream);
+
+/* Optional, weights-only: lamp_pack_weight(format 0) copies of the weight matrices whose projections run as launches of the
+ * tile GEMM at sizes where its one-wave-row tile is chosen -- that tile then loads its weight fragments straight from the pack
+ * (one contiguous KiB per wave instruction) and no longer passes the weight through LDS.  Same bits with and without, member by
+ * member: a NULL member (or array, or struct) leaves that launch on the row-major weight, as does a shape the pack cannot express
+ * (output width not a multiple of 16, d_model / d_inner not a multiple of 32), a LAMP_FWD_MATMUL_* flag, or an output / bias /
+ * residual that cannot move as 16-byte accesses.  Like lamp_model.chain_packs they depend on weights only: build them once per
+ * weight version; each is as large as its matrix (1 MiB for 512 x 512).  The K / V projection of the encoder rows takes none. */
+typedef struct lamp_dec_gemm_pack {
+    const float* enc_q;  /* dec_layers[i].enc_attn.w_qs */
+    const float* slf_q;  /* dec_layers[i].slf_attn.w_qs, w_ks, w_vs: one three-segment launch, packed when all three are given */
+    const float* slf_k;
+    const float* slf_v;
+} lamp_dec_gemm_pack;
+typedef struct lamp_enc_gemm_pack {
+    const float* w1;     /* enc_layers[i].pos_ffn.w1 */
+    const float* w2;     /* enc_layers[i].pos_ffn.w2 */
+} lamp_enc_gemm_pack;
+typedef struct lamp_gemm_packs {
+    const lamp_enc_gemm_pack* enc;  /* host array of n_layers_enc entries, or NULL */
+    const lamp_dec_gemm_pack* dec;  /* host array of n_layers_dec entries, or NULL */
+} lamp_gemm_packs;
+
+/* lamp_forward_opts with weight packs for its GEMM launches (opts and packs nullable; workspace: lamp_forward_opts_workspace_bytes).
+ * The packs ride beside the model instead of inside it: lamp_model keeps its layout, and a library without this entry point is
+ * never handed one. */
+int lamp_forward_packs(const lamp_model* m, const lamp_fwd_options* opts, const lamp_gemm_packs* packs, const int64_t* src_seq,
+                       const int64_t* src_pos, int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux,
+                       void* workspace, size_t workspace_bytes, lamp_stream_t stream);
 
 /* ---- the one-hot genomics encoder (GraphEncoder(onehot=True), lamp/Encoders.py:46-51,68-73) ----------------------
  * For src_seq / src_pos int64 [B, T] over a vocabulary of n_vocab (9) symbols, with T2 = T / 2:

@@ -240,6 +240,17 @@ class LAMP(nn.Module):
                 out += [l.slf_attn.fc.weight, l.pos_ffn.w_1.weight, l.pos_ffn.w_2.weight]
         return out
 
+    def _gemm_pack_weights(self):
+        """The matrices lamp_gemm_packs covers: every encoder layer's pos_ffn (w_1, w_2), every decoder layer's enc_attn.w_qs and
+        slf_attn (w_qs, w_ks, w_vs).  -> (encoder pairs, decoder quads; None where a block does not exist)"""
+        enc = [(l.pos_ffn.w_1.weight, l.pos_ffn.w_2.weight) for l in self.encoder.layer_stack]
+        dec = []
+        for l in self.decoder.layer_stack:
+            slf = getattr(l, 'slf_attn', None)
+            dec.append((l.enc_attn.w_qs.weight,) + (tuple(getattr(slf, n).weight for n in ('w_qs', 'w_ks', 'w_vs')) if slf is not None
+                                                     else (None, None, None)))
+        return enc, dec
+
     def _native_model(self):
         """Build (and cache, keyed on every weight's data_ptr) the lamp_model struct."""
         replica = getattr(self, '_is_replica', False)
@@ -260,11 +271,13 @@ class LAMP(nn.Module):
         packs = self.use_chain_packs and not replica      # weights-only repacks: same one-off cost, same staleness rule
         onehot = bool(getattr(self.encoder, 'onehot', False))
         live = self.enc_self_attn
+        # fragment-major copies for the tile GEMM launches (lamp_forward_packs; the one-hot forward has no such entry point)
+        gpacks = bool(self.use_gemm_packs and not replica and not onehot and getattr(N.lib(), 'lamp_forward_packs', None))
         # weights-only tables, likewise; a live layer 0 starts with the attention, not with W1: nothing to fold into
         fold = self.fold_embedding and not replica and len(self.encoder.layer_stack) > 0 and not onehot and not live
         sparse = bool(self.use_sparse_label_attention and self.use_mask_bits and self.decoder.label_rows_sparse and bias is None)
         key = tuple(p.data_ptr() for p in params) + (N.ptr(mask), N.ptr(bits), N.ptr(tiles), self.use_label_tiles,
-                                                      hoist, self.use_mask_bits, packs, fold, sparse, live, bias is not None)
+                                                      hoist, self.use_mask_bits, packs, fold, sparse, live, bias is not None, gpacks)
         if hoist:  # the hoisted projection below is stale once either operand changes
             l0 = self.decoder.layer_stack[0].enc_attn
             key += (self.decoder.tgt_word_emb.weight._version, l0.w_qs.weight._version)
@@ -272,6 +285,8 @@ class LAMP(nn.Module):
             key += tuple(w._version for w in self._chain_weights())
             if live:
                 key += tuple(w._version for w in self._enc_chain_weights())
+        if gpacks:
+            key += tuple(w._version for group in self._gemm_pack_weights() for ws in group for w in ws if w is not None)
         if fold:
             key += tuple(w._version for w in self._fold_weights() if w is not None)
         if onehot:   # the tap table and W2's repack are weights-only: rebuilt per weight version
@@ -334,6 +349,21 @@ class LAMP(nn.Module):
                     continue
                 enc_pack_arr[i] = _chain_pack(l.slf_attn.fc.weight, l.pos_ffn.w_1.weight, l.pos_ffn.w_2.weight, pack_keep)
             torch.cuda.current_stream().synchronize()
+        gemm_keep = None
+        if gpacks:
+            # the same format-0 copies for the projections and encoder FFN matrices that run as tile-GEMM launches
+            # (lamp_gemm_packs): weights only, rebuilt once per weight version like the chain packs; same bits with and without
+            enc_ws, dec_ws = self._gemm_pack_weights()
+            tensors = []
+
+            def pk(w):
+                t = N.weight_pack(w, 0) if w is not None else None
+                tensors.append(t)
+                return N.ptr(t)
+            enc_gp = (N.EncGemmPack * max(1, len(enc_ws)))(*[N.EncGemmPack(*[pk(w) for w in ws]) for ws in enc_ws])
+            dec_gp = (N.DecGemmPack * max(1, len(dec_ws)))(*[N.DecGemmPack(*[pk(w) for w in ws]) for ws in dec_ws])
+            gemm_keep = (N.GemmPacks(enc_gp, dec_gp), enc_gp, dec_gp, tensors)
+            torch.cuda.current_stream().synchronize()
         fold_keep = None
         if fold:
             # encoder layer 0's W1 folded into the embedding tables (lamp_model.enc0_emb_w1 / enc0_pos_w1, include/lamp_hip.h):
@@ -357,7 +387,7 @@ class LAMP(nn.Module):
             fe = N.onehot_frontend(t1, b1c, w2c, b2c, w2p)
             onehot_keep = (fe, t1, w2c, b1c, b2c, w2p)
             torch.cuda.current_stream().synchronize()
-        built = (m, enc_arr, dec_arr, q0, pack_arr, pack_keep, fold_keep, onehot_keep, enc_pack_arr)
+        built = (m, enc_arr, dec_arr, q0, pack_arr, pack_keep, fold_keep, onehot_keep, enc_pack_arr, gemm_keep)
         if not replica:
             self._native_cache = (key, built)
         return built
@@ -426,6 +456,7 @@ class LAMP(nn.Module):
         built = self._native_model()
         model, enc_arr, dec_arr = built[:3]
         fe = built[7][0] if self.onehot else None
+        gp = built[9][0] if built[9] is not None else None
         T_in = T
         if fe is not None:
             T = T_in // 2   # lamp/Encoders.py:69-73: the encoder sees T / 2 rows
@@ -504,6 +535,11 @@ class LAMP(nn.Module):
                                                  T_in, logits.data_ptr(), enc_output.data_ptr(),
                                                  C.byref(aux) if aux is not None else None, ws.data_ptr(), ws.numel(),
                                                  N.stream()), 'lamp_onehot_forward_opts')
+        elif gp is not None and fe is None:
+            N.check(lib.lamp_forward_packs(C.byref(model), C.byref(opts) if opts is not None else None, C.byref(gp), seq.data_ptr(),
+                                           pos.data_ptr(), B, T, logits.data_ptr(), enc_output.data_ptr(),
+                                           C.byref(aux) if aux is not None else None, ws.data_ptr(), ws.numel(), N.stream()),
+                    'lamp_forward_packs')
         elif opts is not None:
             N.check(lib.lamp_forward_opts(C.byref(model), C.byref(opts), seq.data_ptr(), pos.data_ptr(), B, T,
                                           logits.data_ptr(), enc_output.data_ptr(), C.byref(aux) if aux is not None else None,
@@ -530,6 +566,10 @@ class LAMP(nn.Module):
     cache_layer0_query = True
     # Keep fragment-major copies of the decoder sub-chains' weight matrices (lamp_pack_weight) for the fused chain launch.
     use_chain_packs = True
+    # Keep fragment-major copies of the encoder FFN matrices and of the decoder's query / label self-attention projections
+    # (lamp_gemm_packs): the tile GEMM's one-wave-row tile reads its weight fragments straight from them.  Same bits; one extra copy
+    # of each packed matrix in device memory.
+    use_gemm_packs = True
     # Fold encoder layer 0's first FFN matrix into the embedding tables (weights-only: Emb . W1^T and Pos . W1^T + b1, one
     # GEMM fewer per forward; results move in the last bits, a re-association).  False = the unfolded route.
     fold_embedding = True

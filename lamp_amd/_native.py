@@ -86,6 +86,18 @@ class Model(C.Structure):
                 ('enc0_emb_w1', _vp), ('enc0_pos_w1', _vp), ('label_mask_allowed', C.c_int64)]
 
 
+class DecGemmPack(C.Structure):  # include/lamp_hip.h: lamp_dec_gemm_pack
+    _fields_ = [('enc_q', _vp), ('slf_q', _vp), ('slf_k', _vp), ('slf_v', _vp)]
+
+
+class EncGemmPack(C.Structure):  # include/lamp_hip.h: lamp_enc_gemm_pack
+    _fields_ = [('w1', _vp), ('w2', _vp)]
+
+
+class GemmPacks(C.Structure):  # include/lamp_hip.h: lamp_gemm_packs
+    _fields_ = [('enc', C.POINTER(EncGemmPack)), ('dec', C.POINTER(DecGemmPack))]
+
+
 class GemmDesc(C.Structure):  # include/lamp_hip.h: lamp_gemm_desc
     _fields_ = [('A', _vp), ('B', _vp), ('C', _vp), ('M', C.c_int32), ('N', C.c_int32), ('K', C.c_int32),
                 ('batch0', C.c_int32), ('batch1', C.c_int32), ('accumulate', C.c_int32),
@@ -137,6 +149,8 @@ PROTOTYPES = {
     'lamp_strerror': (C.c_char_p, [C.c_int]),
     'lamp_linear_fwd': (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _vp]),
     'lamp_linear_prec_fwd': (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp]),
+    'lamp_linear_packed_fwd': (C.c_int, [_vp, _i64, _i32, _i64, C.POINTER(_vp), C.POINTER(_vp), _i32, _i32, _i64, C.POINTER(_vp), _vp, _i64,
+                                         _i32, C.POINTER(_vp), _i64, _vp, _vp]),
     'lamp_layernorm_fwd': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _f, _vp, _vp]),
     'lamp_sdpa_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f,
                                 C.POINTER(Mask), C.POINTER(AttnLayout), _vp]),
@@ -182,6 +196,8 @@ PROTOTYPES = {
     'lamp_forward_opts_workspace_bytes': (_sz, [C.POINTER(Model), C.POINTER(FwdOptions), _i32, _i32, _i32]),
     'lamp_forward_opts': (C.c_int, [C.POINTER(Model), C.POINTER(FwdOptions), _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(Aux),
                                     _vp, _sz, _vp]),
+    'lamp_forward_packs': (C.c_int, [C.POINTER(Model), C.POINTER(FwdOptions), C.POINTER(GemmPacks), _vp, _vp, _i32, _i32, _vp, _vp,
+                                     C.POINTER(Aux), _vp, _sz, _vp]),
     'lamp_onehot_forward_opts_workspace_bytes': (_sz, [C.POINTER(Model), C.POINTER(OnehotFrontend), C.POINTER(FwdOptions),
                                                        _i32, _i32, _i32]),
     'lamp_onehot_forward_opts': (C.c_int, [C.POINTER(Model), C.POINTER(OnehotFrontend), C.POINTER(FwdOptions), _vp, _vp, _i32,
@@ -218,6 +234,10 @@ PROTOTYPES = {
                                  C.POINTER(C.c_double)]),
 }
 
+# entry points added without an ABI bump (no struct changed): a library of the same ABI version built before them lacks the
+# symbols -- same-box A/B runs against the previous build (LAMP_HIP_LIBRARY) -- and their callers ask with getattr
+LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs')
+
 _lib = None
 _lock = threading.Lock()
 
@@ -238,7 +258,7 @@ def load_library(path):
     if version != ABI_VERSION and not old_ok:
         raise RuntimeError('lamp_amd: ABI version mismatch in ' + path)
     for name, (res, args) in PROTOTYPES.items():
-        if old_ok and not hasattr(handle, name):
+        if (old_ok or name in LATE_ENTRY_POINTS) and not hasattr(handle, name):
             continue
         fn = getattr(handle, name)
         fn.restype = res
@@ -577,6 +597,25 @@ def weight_pack(w, fmt=0):
     out = torch.empty(n * k, dtype=torch.float32, device=w.device)
     check(fn(ptr(w), n, k, k, fmt, ptr(out), stream()), 'lamp_pack_weight')
     return out
+
+
+def linear_packed(x, weights, packs=None, biases=None, residual=None, relu=False, m_dev=None, M=None):
+    """lamp_linear_packed_fwd: the 1-4 matrices of `weights` ([N, K] each) applied to the rows of x in ONE launch -> list of [M, N].
+    packs: weight_pack(w, 0) per matrix (entries may be None); m_dev: int32 device tensor holding the live row count (rows past
+    it are left as allocated: zeros here)."""
+    require_device(x, *weights)
+    x2 = f32c(x).reshape(-1, x.size(-1))
+    M = x2.size(0) if M is None else M
+    K, n, N = x2.size(1), len(weights), weights[0].size(0)
+    ws = [f32c(w.detach()) for w in weights]
+    outs = [torch.zeros((M, N), dtype=torch.float32, device=x.device) for _ in ws]
+    arr = lambda ts: (_vp * n)(*[ptr(t) for t in ts])
+    bs = [f32c(b) if b is not None else None for b in biases] if biases is not None else None
+    res = f32c(residual) if residual is not None else None
+    check(lib().lamp_linear_packed_fwd(ptr(x2), M, K, K, arr(ws), arr(packs) if packs is not None else None, n, N, K,
+                                       arr(bs) if bs is not None else None, ptr(res), N, int(bool(relu)), arr(outs), N,
+                                       ptr(m_dev), stream()), 'lamp_linear_packed_fwd')
+    return outs
 
 
 def diag_logits(y, w_out):

@@ -96,10 +96,11 @@ static inline int fwd_matmul_prec(const lamp_fwd_options* o) {
 }
 
 // prec: LAMP_PREC_* -- which kernel family multiplies (gemm.hip, or gemm_split.hip's bf16x3 / bf16x6 split products)
+// Wp (nullable; entries nullable): lamp_pack_weight(W[i], format 0) per segment, for the fp32 tile GEMM's packed-W tile (GemmParams::Wp)
 static int linear(const float* A, int64_t M, int K, int64_t lda, const float* const* W, int nseg, int N,
                   int64_t ldw, const float* const* bias, const float* R, int64_t ldr, int relu,
                   float* const* C, int64_t ldc, int prec, hipStream_t s, const int* m_dev = nullptr,
-                  const float* A_dense = nullptr, const ResGather* rg = nullptr) {
+                  const float* A_dense = nullptr, const ResGather* rg = nullptr, const float* const* Wp = nullptr) {
     GemmParams p{};
     p.A = A; p.lda = lda; p.M = M; p.K = K; p.N = N; p.nseg = nseg; p.ldw = ldw; p.ldc = ldc;
     p.R = R; p.ldr = ldr; p.relu = relu; p.m_dev = m_dev; p.A_dense = A_dense;
@@ -109,6 +110,7 @@ static int linear(const float* A, int64_t M, int K, int64_t lda, const float* co
     }
     for (int i = 0; i < nseg; ++i) {
         p.W[i] = W[i];
+        p.Wp[i] = Wp ? Wp[i] : nullptr;
         p.bias[i] = bias ? bias[i] : nullptr;
         p.C[i] = C[i];
     }
@@ -151,17 +153,19 @@ static void attn_mask(AttnParams& a, const lamp_mask* mask) {
 // width, Q with both when it reads those rows too.  m_dev / A_dense (GemmParams): the key / value rows are packed.
 static int project_qkv(const lamp_mha_weights& w, int d, int dk, int dv, const float* xq, int64_t Mq, float* Q,
                        const float* xk, const float* xv, int64_t Mk, float* K, float* V, int prec, hipStream_t s,
-                       const int* m_dev, const float* A_dense) {
+                       const int* m_dev, const float* A_dense, const float* const* Wp = nullptr) {
     const int hdk = w.n_head * dk, hdv = w.n_head * dv;
     const bool one_kv = K && V && xk == xv && hdk == hdv;
     const bool one_qkv = one_kv && Q && xq == xk && Mq == Mk && !m_dev;
     const float* W[3] = {w.w_qs, w.w_ks, w.w_vs};
     float* C[3] = {Q, K, V};
-    if (Q) LAMP_CK(linear(xq, Mq, d, d, W, one_qkv ? 3 : 1, hdk, d, nullptr, nullptr, 0, 0, C, hdk, prec, s));
+    const float* const* P1 = Wp ? Wp + 1 : nullptr;   // Wp: packs of {w_qs, w_ks, w_vs}, entries nullable (a launch needs all of its own)
+    const float* const* P2 = Wp ? Wp + 2 : nullptr;
+    if (Q) LAMP_CK(linear(xq, Mq, d, d, W, one_qkv ? 3 : 1, hdk, d, nullptr, nullptr, 0, 0, C, hdk, prec, s, nullptr, nullptr, nullptr, Wp));
     if (one_qkv) return 0;
-    if (one_kv) return linear(xk, Mk, d, d, W + 1, 2, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, prec, s, m_dev, A_dense);
-    if (K) LAMP_CK(linear(xk, Mk, d, d, W + 1, 1, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, prec, s, m_dev, A_dense));
-    if (V) LAMP_CK(linear(xv, Mk, d, d, W + 2, 1, hdv, d, nullptr, nullptr, 0, 0, C + 2, hdv, prec, s, m_dev, A_dense));
+    if (one_kv) return linear(xk, Mk, d, d, W + 1, 2, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, prec, s, m_dev, A_dense, nullptr, P1);
+    if (K) LAMP_CK(linear(xk, Mk, d, d, W + 1, 1, hdk, d, nullptr, nullptr, 0, 0, C + 1, hdk, prec, s, m_dev, A_dense, nullptr, P1));
+    if (V) LAMP_CK(linear(xv, Mk, d, d, W + 2, 1, hdv, d, nullptr, nullptr, 0, 0, C + 2, hdv, prec, s, m_dev, A_dense, nullptr, P2));
     return 0;
 }
 
@@ -187,6 +191,7 @@ struct FfnParams {
     bool hidden_ready = false;
     const ResGather* rg = nullptr;
     int prec = LAMP_PREC_FP32;   // matmul precision of the two GEMMs (the forward's LAMP_FWD_MATMUL_* flags)
+    const float *w1_pack = nullptr, *w2_pack = nullptr;   // lamp_gemm_packs: format-0 packs of w1 / w2 for the packed-W tile
 };
 
 static int ffn_core(const FfnParams& f, hipStream_t s) {
@@ -198,13 +203,15 @@ static int ffn_core(const FfnParams& f, hipStream_t s) {
         const float* W[1] = {w.w1};
         const float* b[1] = {w.b1};
         float* C[1] = {f.hidden};
-        LAMP_CK(linear(f.x, f.M, d, d, W, 1, dff, d, b, nullptr, 0, 1, C, dff, f.prec, s, f.rows_dev));
+        const float* P[1] = {f.w1_pack};
+        LAMP_CK(linear(f.x, f.M, d, d, W, 1, dff, d, b, nullptr, 0, 1, C, dff, f.prec, s, f.rows_dev, nullptr, nullptr, P));
     }
     {
         const float* W[1] = {w.w2};
         const float* b[1] = {w.b2};
         float* C[1] = {f.out};
-        LAMP_CK(linear(f.hidden, f.M, dff, dff, W, 1, d, dff, b, f.x, d, 0, C, d, f.prec, s, f.rows_dev, nullptr, f.rg));
+        const float* P[1] = {f.w2_pack};
+        LAMP_CK(linear(f.hidden, f.M, dff, dff, W, 1, d, dff, b, f.x, d, 0, C, d, f.prec, s, f.rows_dev, nullptr, f.rg, P));
     }
     LayerNormParams ln{f.out, f.M, d, w.ln_g, w.ln_b, f.out};
     if (f.scatter) {
@@ -261,6 +268,7 @@ struct MhaCall {
     const float* xkv_dense = nullptr;  // with keys_packed: the padded rows, read instead when nothing was skipped
     int act = LAMP_ATTN_SOFTMAX;       // LAMP_ATTN_SIGMOID: sigmoid attention (attention_sigmoid.hip), maps in the same pass
     int prec = LAMP_PREC_FP32;         // matmul precision of the projections and of a separate-launch fc (never of the chain launch)
+    const float* const* w_packs = nullptr;   // lamp_gemm_packs: format-0 packs of {w_qs, w_ks, w_vs} (entries nullable)
 };
 
 
@@ -277,7 +285,7 @@ static int mha_attend(const MhaCall& c, const MhaScratch& sc, hipStream_t s) {
     const bool kv = !c.kv_ready;
     LAMP_CK(project_qkv(w, d, dk, dv, c.xq, c.xq_shared ? lq : int64_t(B) * lq, c.q_ready ? nullptr : sc.Q, c.xkv, c.xkv,
                         int64_t(B) * lk, kv ? sc.K : nullptr, kv && need_v ? sc.V : nullptr, c.prec, s,
-                        c.keys_packed ? c.keys->rows : nullptr, c.keys_packed ? c.xkv_dense : nullptr));
+                        c.keys_packed ? c.keys->rows : nullptr, c.keys_packed ? c.xkv_dense : nullptr, c.w_packs));
 
     // A key-token mask without a plan (lamp_mha_fwd on its own): count each sample's keys here, padded layout, so that
     // the module-by-module route takes the same per-sample key split as lamp_forward -- same bits.
@@ -424,6 +432,15 @@ int lamp_linear_prec_fwd(const float* A, int64_t M, int32_t K, int64_t lda, cons
     float* Cs[1] = {C};
     if (lda < K || ldw < K || ldc < N || (residual && ldr < N)) return LAMP_E_DIMS;
     return linear(A, M, K, lda, Ws, 1, N, ldw, bs, residual, ldr, relu, Cs, ldc, precision, hipStream_t(stream));
+}
+
+int lamp_linear_packed_fwd(const float* A, int64_t M, int32_t K, int64_t lda, const float* const* W, const float* const* W_pack,
+                           int32_t n_seg, int32_t N, int64_t ldw, const float* const* bias, const float* residual, int64_t ldr,
+                           int32_t relu, float* const* C, int64_t ldc, const int32_t* m_dev, lamp_stream_t stream) {
+    if (!W || !C) return LAMP_E_NULL;
+    if (n_seg < 1 || n_seg > GEMM_MAX_SEG || lda < K || ldw < K || ldc < N || (residual && ldr < N)) return LAMP_E_DIMS;
+    return linear(A, M, K, lda, W, n_seg, N, ldw, bias, residual, ldr, relu, C, ldc, LAMP_PREC_FP32, hipStream_t(stream), m_dev,
+                  nullptr, nullptr, W_pack);
 }
 
 int lamp_layernorm_fwd(const float* x, int64_t M, int32_t d, const float* gamma, const float* beta, float eps,
@@ -984,6 +1001,10 @@ struct Pass {
     const lamp_chain_pack* enc_packs = nullptr;      // lamp_fwd_options::enc_chain_packs
     int dec_act = LAMP_ATTN_SOFTMAX;                 // LAMP_FWD_DEC_SIGMOID: both attention blocks of every decoder layer
     int prec = LAMP_PREC_FP32;                       // LAMP_FWD_MATMUL_*: every linear() of the pass (FfnParams / MhaCall::prec)
+    const lamp_gemm_packs* gp = nullptr;             // lamp_forward_packs: weight packs of the tile GEMM launches
+    void ffn_packs(FfnParams& f, int layer) const {  // encoder layer's pos_ffn
+        if (gp && gp->enc) { f.w1_pack = gp->enc[layer].w1; f.w2_pack = gp->enc[layer].w2; }
+    }
 };
 
 // GraphEncoder.forward (lamp/Encoders.py:64-110) on the packed non-PAD token rows (+ ONE shared PAD row: all PAD positions
@@ -1014,6 +1035,7 @@ static int encode_packed(Pass& p) {
         f.prec = p.prec;
         f.rows_dev = p.sp.rows + 1; f.hidden_ready = folded && i == 0; f.rg = gather_res && i == 0 ? &rg : nullptr;
         if (i + 1 == m->n_layers_enc) { f.scatter = &p.sp; f.nb = p.nb; f.T = T; f.y_flat = p.x; }
+        p.ffn_packs(f, i);
         LAMP_CK(ffn_core(f, p.s));
     }
     p.xk = w.Xp;
@@ -1049,6 +1071,7 @@ static int encode_packed_live(Pass& p) {
         LAMP_CK(launch_layernorm(ln, p.s));
         FfnParams f{w.Xp, Mub, d, dff, &m->enc_layers[i].pos_ffn, w.Xp, w.H};
         f.rows_dev = w.live_rows; f.prec = p.prec;
+        p.ffn_packs(f, i);
         LAMP_CK(ffn_core(f, p.s));
     }
     LAMP_CK(launch_scatter_rows(w.Xp, d, p.nb, T, p.sp, p.x, p.s));
@@ -1091,6 +1114,7 @@ static int encode_padded(Pass& p) {
         float* map = p.aux && p.aux->enc_self_attn ? p.aux->enc_self_attn[i] : nullptr;
         FfnParams f{p.x, Me, d, dff, &l.pos_ffn, p.x, w.H};   // lamp/Layers.py:18
         f.prec = p.prec;
+        p.ffn_packs(f, i);
         if (p.g.live) {
             // lamp/Layers.py:16 with its output kept: x <- slf_attn(x, x, x), then pos_ffn(x).  The row-local tail
             // (fc + residual -> LayerNorm -> W1 -> W2 + residual -> LayerNorm) is the decoder's sub-chain.
@@ -1179,6 +1203,11 @@ static int decoder_layer(Pass& p, int i) {
     enc.xq_shared = i == 0; enc.q_ready = i == 0 ? m->dec0_query : nullptr; enc.kv_ready = g.n_ahead > 0;
     enc.keys = &p.sp; enc.keys_packed = p.packed; enc.xkv_dense = p.x;
     enc.act = p.dec_act; enc.prec = p.prec;
+    // packs: the query projections of both blocks and the label self-attention's K / V; the K / V projection of the encoder rows has none
+    const lamp_dec_gemm_pack* dp = p.gp && p.gp->dec ? p.gp->dec + i : nullptr;
+    const float* enc_pk[3] = {dp ? dp->enc_q : nullptr, nullptr, nullptr};
+    const float* slf_pk[3] = {dp ? dp->slf_q : nullptr, dp ? dp->slf_k : nullptr, dp ? dp->slf_v : nullptr};
+    enc.w_packs = enc_pk;
     LAMP_CK(mha_attend(enc, sc, p.s));
     LAMP_CK(mha_tail(enc, sc, &f1, pk, &ffn_ran, p.s));
     if (!ffn_ran) LAMP_CK(ffn_core(f1, p.s));   // lamp/Layers.py:36
@@ -1189,7 +1218,7 @@ static int decoder_layer(Pass& p, int i) {
         // label->label messages over the label graph (lamp/Layers.py:40)
         MhaCall slf{Y, Y, p.nb, L, L, d, g.dk, g.dv, &l.slf_attn, &p.label_mask, Y,
                     p.aux && p.aux->dec_self_attn ? p.aux->dec_self_attn[i] : nullptr, p.B, int(p.b0)};
-        slf.act = p.dec_act; slf.prec = p.prec;
+        slf.act = p.dec_act; slf.prec = p.prec; slf.w_packs = slf_pk;
         LAMP_CK(mha_attend(slf, w.mha, p.s));
         LAMP_CK(mha_tail(slf, w.mha, &f2, pk ? pk + 1 : nullptr, &ffn_ran, p.s));
     }
@@ -1256,7 +1285,8 @@ static int check_forward(const lamp_model* m, const lamp_onehot_frontend* fe, co
 // every micro-batch split.
 static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const FwdDims& g, const int64_t* src_seq,
                    const int64_t* src_pos, int32_t B, int32_t T_in, float* logits, float* enc_output, const lamp_aux* aux,
-                   void* workspace, size_t workspace_bytes, hipStream_t s, const lamp_fwd_options* o = nullptr) {
+                   void* workspace, size_t workspace_bytes, hipStream_t s, const lamp_fwd_options* o = nullptr,
+                   const lamp_gemm_packs* gp = nullptr) {
     const Carver size = fwd_size(g);
     if (workspace_bytes < size.bound(1)) return LAMP_E_WORKSPACE;
     const int64_t mb = std::min<int64_t>(B, (workspace_bytes - size.fixed) / size.per);
@@ -1306,6 +1336,7 @@ static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const Fw
         // LAMP_FWD_MATMUL_*: every linear() of the pass -- encoder FFN, K/V, Q and Q/K/V projections, the separate-launch tails --
         // takes the split kernel (gemm_split.hip); the chain launch, attention, conv2 and the read-out are not linear() calls
         p.prec = fwd_matmul_prec(o);
+        p.gp = gp;
         LAMP_CK(!packed ? encode_padded(p) : g.live ? encode_packed_live(p) : encode_packed(p));
         if (g.n_ahead)
             LAMP_CK(project_kv_layers(p.xk, int64_t(nb) * g.T, g.d, g.dk, g.dv, m->dec_layers, g.n_ahead, w.K_ahead,
@@ -1323,7 +1354,7 @@ size_t lamp_forward_workspace_bytes(const lamp_model* m, int32_t micro_batch, in
 
 static int forward_tokens(const lamp_model* m, const lamp_fwd_options* o, const int64_t* src_seq, const int64_t* src_pos,
                           int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
-                          size_t workspace_bytes, lamp_stream_t stream) {
+                          size_t workspace_bytes, lamp_stream_t stream, const lamp_gemm_packs* gp = nullptr) {
     FwdDims g;
     LAMP_CK(check_forward(m, nullptr, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, &g, o));
     // lamp_forward_workspace_bytes(m, 1, T, want_attn) -- the K/V-ahead buffers counted -- is the least a call accepts, not the
@@ -1335,7 +1366,7 @@ static int forward_tokens(const lamp_model* m, const lamp_fwd_options* o, const 
         2 * m->n_layers_dec <= GEMM_MAX_SEG && m->n_layers_dec > 1 && workspace_bytes >= fwd_size(g).bound(size_t(B));
     if (!kv_ahead) g.n_ahead = 0;
     return forward(m, nullptr, g, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes,
-                   hipStream_t(stream), o);
+                   hipStream_t(stream), o, gp);
 }
 
 int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T,
@@ -1355,6 +1386,12 @@ int lamp_forward_opts(const lamp_model* m, const lamp_fwd_options* opts, const i
                       int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
                       size_t workspace_bytes, lamp_stream_t stream) {
     return forward_tokens(m, opts, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, stream);
+}
+
+int lamp_forward_packs(const lamp_model* m, const lamp_fwd_options* opts, const lamp_gemm_packs* packs, const int64_t* src_seq,
+                       const int64_t* src_pos, int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux,
+                       void* workspace, size_t workspace_bytes, lamp_stream_t stream) {
+    return forward_tokens(m, opts, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, stream, packs);
 }
 
 // ------------------------------------------------------------------ one-hot genomics encoder (conv.hip)

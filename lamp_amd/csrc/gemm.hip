@@ -48,9 +48,18 @@ __device__ __forceinline__ int div_1_to_8(int n, int d) {
     return int(__umulhi(unsigned(n), mul) >> (d == 3 ? 1 : 2));
 }
 
-constexpr int gemm_min_waves(int bm, int bn, int bk, int mf) { return (mf == 16 && bm == 64 && bn == 64 && bk == 16) ? 5 : 1; }
+// wpack (the packed-W instantiation, see gemm_body): its LDS carve holds A only -- 10 KiB for the 32x64x32 tile, fifteen workgroups
+// per CU where the staged carve (30 KiB) allowed five -- so LDS no longer bounds the residency and registers would: the kernel
+// compiles to 68 (two A sets, two W fragment sets, prefetched epilogue operands), seven waves per SIMD (one per workgroup here:
+// 1x4 waves).  The largest launches it serves have 8.4 (decoder Q/K/V, 2160 tiles on 256 CUs) to 9.4 (encoder FFN, 2416)
+// workgroups per CU: two rounds at five to eight per CU, three at four -- and of the two-round residencies FIVE measured
+// fastest (GemmTile::LDS_LAUNCH_BYTES holds the launch there).  So five is both the bound asked of the compiler (<= 96 registers)
+// and what runs.
+constexpr int gemm_min_waves(int bm, int bn, int bk, int mf, bool wpack = false) {
+    return (wpack || (mf == 16 && bm == 64 && bn == 64 && bk == 16)) ? 5 : 1;
+}
 
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MF = 32>
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MF = 32, bool WPACK = false>
 struct GemmTile {
     static constexpr int NT = WAVES_M * WAVES_N * 64;
     static constexpr int WTM = BM / WAVES_M;
@@ -69,11 +78,18 @@ struct GemmTile {
     static constexpr int LDS_STRIDE = BK + (MF == 16 ? LAMP_LDS_PAD16 : 4);
     static constexpr int A_LD = BM * BK / 4 / NT;  // float4 loads per thread per tile
     static constexpr int B_LD = BN * BK / 4 / NT;
-    static constexpr size_t LDS_BYTES = size_t(2) * (BM + BN) * LDS_STRIDE * sizeof(float);
+    static constexpr size_t LDS_BYTES = size_t(2) * (BM + (WPACK ? 0 : BN)) * LDS_STRIDE * sizeof(float);   // WPACK: W never enters LDS
+    // What the launch ASKS for.  The packed-W carve (10 KiB for 32x64x32) would let seven workgroups share a CU (68 registers); the
+    // launches it serves have 8.4-9.4 workgroups per CU, i.e. a full first round and a second one of 1.4-2.4 workgroups that runs
+    // with little to hide its load latency behind.  Asking for the staged carve's size keeps five per CU -- two even rounds.
+    // Measured on the decoder Q/K/V launch (2160 tiles): 37.6 us at five per CU against 40.6 / 40.3 / 40.6 at seven / seven (by
+    // LDS) / six and 38.6 at four; the other launches (720 and 2416 tiles) do not care, 16.5-16.6 and 41.5-41.9 us throughout
+    // (profiles/gemm_packed_w_ab.txt).
+    static constexpr size_t LDS_LAUNCH_BYTES = WPACK ? size_t(2) * (BM + BN) * LDS_STRIDE * sizeof(float) : LDS_BYTES;
     // Waves per SIMD the register allocator must leave room for.  The 64x64x16 tile serves launches of ~1200 tiles
     // (encoder FFN at batch 32: 1208): five workgroups per CU hold them all at once, four leave a second, mostly empty
     // round (44 -> 51 us when the 16-byte epilogue operands pushed the kernel from 92 to 100 registers).
-    static constexpr int MIN_WAVES = gemm_min_waves(BM, BN, BK, MF);
+    static constexpr int MIN_WAVES = gemm_min_waves(BM, BN, BK, MF, WPACK);
     static_assert(MF == 32 || MF == 16, "MFMA block edge");
     static_assert(WTM % MF == 0 && WTN % MF == 0, "wave tile must be a multiple of the MFMA block");
     static_assert(BK % (MF == 32 ? 8 : 16) == 0, "BK must cover whole fragment reads");
@@ -94,13 +110,19 @@ __device__ __forceinline__ const float* uniform_ptr(const float* q) {
     return reinterpret_cast<const float*>((uint64_t(hi) << 32) | lo);
 }
 // The whole tile program: one tile per workgroup, derived from blockIdx.  (Staging variants that lost their measurements --
-// LDS-DMA with compiler-scheduled / inline-assembly fragment reads, W fragments straight from global memory or from a packed
-// copy, two dependent GEMMs in one persistent launch -- are not carried here any more: csrc/experiments/README.md.)
+// LDS-DMA with compiler-scheduled / inline-assembly fragment reads, W fragments straight from the row-major weight, two
+// dependent GEMMs in one persistent launch -- are not carried here any more: csrc/experiments/README.md.)
 // RGATHER: the residual is gathered from two tables through per-row indices (GemmParams::rg_tok) instead of read from R.
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool KTAIL, int MF, bool RPRE, bool VEC, bool RGATHER>
+// WPACK: the W fragments come straight from a fragment-major copy of the weight (GemmParams::Wp, lamp_pack_weight format 0)
+// into registers, one k-tile ahead; only A goes through LDS.  In an NT product a lane's 16-byte load of four consecutive k of
+// its weight row IS its 16x16x4 fragment, and in the packed order the 64 lanes' fragments of one chunk are one contiguous KiB:
+// no global -> register -> ds_write -> ds_read round trip for W.  For tiles with ONE wave row only (WAVES_M == 1: every wave is
+// the sole consumer of its weight columns, nothing is fetched twice).  Same fragments, same MFMA order, same bits.
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool KTAIL, int MF, bool RPRE, bool VEC, bool RGATHER, bool WPACK>
 __device__ __forceinline__ void gemm_body(const GemmParams& p, int tiles_n_seg, int tiles_n, int tiles_m, int panel_split,
                                           FastDiv fd_group, FastDiv fd_seg) {
-    using T = GemmTile<BM, BN, BK, WAVES_M, WAVES_N, MF>;
+    using T = GemmTile<BM, BN, BK, WAVES_M, WAVES_N, MF, WPACK>;
+    static_assert(!WPACK || (MF == 16 && BK == 32 && WAVES_M == 1 && !KTAIL), "packed W: 16x16x4 fragments of whole 32-deep k-tiles, one wave row");
     // lane -> (row within an MFMA block, which group of 4 consecutive k this lane's b128 read covers)
     constexpr int KQ = 64 / MF;             // 2 for 32x32x2, 4 for 16x16x4
     constexpr int KCH = 4 * KQ;             // k covered by one round of fragment reads: 8 or 16
@@ -198,8 +220,10 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, int tiles_n_seg, 
     // held in vector registers compiles to a waterfall loop -- hand the compiler scalars)
     const __amdgpu_buffer_rsrc_t rsA =
         make_rsrc(uniform_ptr(Abase + m0 * p.lda), __builtin_amdgcn_readfirstlane(unsigned((uint64_t(rows_m - 1) * lda + p.K) * 4u)));
-    const __amdgpu_buffer_rsrc_t rsW =
-        make_rsrc(uniform_ptr(p.W[seg] + int64_t(n0) * p.ldw), __builtin_amdgcn_readfirstlane(unsigned((uint64_t(rows_n - 1) * ldw + p.K) * 4u)));
+    // WPACK: the whole pack ([N, K] floats; the launcher keeps it under 2 GiB) -- fragment blocks of columns past N fall outside it and read as zeros
+    const __amdgpu_buffer_rsrc_t rsW = WPACK
+        ? make_rsrc(uniform_ptr(p.Wp[seg]), __builtin_amdgcn_readfirstlane(unsigned(uint64_t(p.N) * uint64_t(p.K) * 4u)))
+        : make_rsrc(uniform_ptr(p.W[seg] + int64_t(n0) * p.ldw), __builtin_amdgcn_readfirstlane(unsigned((uint64_t(rows_n - 1) * ldw + p.K) * 4u)));
 
     acc_t acc[T::MI][T::NI];
 #pragma unroll
@@ -214,6 +238,23 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, int tiles_n_seg, 
     // does not cover an L2/MALL round trip).
     float4 ra0[T::A_LD], rb0[T::B_LD], ra1[T::A_LD], rb1[T::B_LD];
     unsigned voa[T::A_LD], vob[T::B_LD];  // byte offsets of this thread's float4s inside the tile
+    // WPACK: the W fragments of the even / odd k-step, [chunk][block]; the pack holds, per 16 columns and 32 k, the two chunks' fragments
+    // lane by lane (2 KiB): block cb, k-tile kt, chunk c at ((cb * K / 32 + kt) * 2 + c) KiB
+    constexpr int NWF = WPACK ? (BK / KCH) * T::NI : 1;
+    float4 wf0[NWF], wf1[NWF];
+    unsigned vow[NWF];
+    if constexpr (WPACK) {
+#pragma unroll
+        for (int c = 0; c < BK / KCH; ++c)
+#pragma unroll
+            for (int j = 0; j < T::NI; ++j)
+                vow[c * T::NI + j] = unsigned((n0 + wn * T::WTN + j * MF) >> 4) * unsigned(p.K >> 5) * 2048u + unsigned(c) * 1024u + unsigned(lane) * 16u;
+    }
+    auto wload = [&](int k0, float4 (&wf)[NWF]) {
+        const unsigned so = unsigned(k0) * 64u;   // k-tile k0 / 32, 2 KiB each; uniform -> soffset
+#pragma unroll
+        for (int x = 0; x < NWF; ++x) wf[x] = bload4(rsW, vow[x], so);
+    };
 #pragma unroll
     for (int i = 0; i < T::A_LD; ++i) {
         const int idx = tid + i * T::NT;
@@ -244,8 +285,10 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, int tiles_n_seg, 
             const unsigned so = unsigned(k0) * 4u;  // uniform -> soffset
 #pragma unroll
             for (int i = 0; i < T::A_LD; ++i) ra[i] = bload4(rsA, voa[i], so);
+            if constexpr (!WPACK) {
 #pragma unroll
-            for (int i = 0; i < T::B_LD; ++i) rb[i] = bload4(rsW, vob[i], so);
+                for (int i = 0; i < T::B_LD; ++i) rb[i] = bload4(rsW, vob[i], so);
+            }
         }
     };
     auto lstore = [&](int buf, const float4 (&ra)[T::A_LD], const float4 (&rb)[T::B_LD]) {
@@ -257,11 +300,13 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, int tiles_n_seg, 
             const int row = idx / C4, c4 = idx - row * C4;
             *reinterpret_cast<float4*>(a + row * S + c4 * 4) = ra[i];
         }
+        if constexpr (!WPACK) {
 #pragma unroll
-        for (int i = 0; i < T::B_LD; ++i) {
-            const int idx = tid + i * T::NT;
-            const int row = idx / C4, c4 = idx - row * C4;
-            *reinterpret_cast<float4*>(b + row * S + c4 * 4) = rb[i];
+            for (int i = 0; i < T::B_LD; ++i) {
+                const int idx = tid + i * T::NT;
+                const int row = idx / C4, c4 = idx - row * C4;
+                *reinterpret_cast<float4*>(b + row * S + c4 * 4) = rb[i];
+            }
         }
     };
     auto mfma_chunk = [&](const float4 (&fa)[T::MI], const float4 (&fb)[T::NI]) {
@@ -288,7 +333,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, int tiles_n_seg, 
         __builtin_amdgcn_s_setprio(0);
 #endif
     };
-    auto compute = [&](int buf) {
+    auto compute = [&](int buf, const float4 (&wf)[NWF]) {
         const float* a = As + buf * BM * S + (wm * T::WTM + l31) * S + hi * 4;
         const float* b = Bs + buf * BN * S + (wn * T::WTN + l31) * S + hi * 4;
 #pragma unroll
@@ -297,7 +342,10 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, int tiles_n_seg, 
 #pragma unroll
             for (int i = 0; i < T::MI; ++i) fa[i] = *reinterpret_cast<const float4*>(a + i * MF * S + c * KCH);
 #pragma unroll
-            for (int j = 0; j < T::NI; ++j) fb[j] = *reinterpret_cast<const float4*>(b + j * MF * S + c * KCH);
+            for (int j = 0; j < T::NI; ++j) {
+                if constexpr (WPACK) fb[j] = wf[c * T::NI + j];
+                else fb[j] = *reinterpret_cast<const float4*>(b + j * MF * S + c * KCH);
+            }
             mfma_chunk(fa, fb);
         }
     };
@@ -375,23 +423,56 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, int tiles_n_seg, 
     }
 
     lstore(0, ra0, rb0);
-    if (nk > 1) gload(BK, ra0, rb0);      // tile 1 -> set 0
-    if (nk > 2) gload(2 * BK, ra1, rb1);  // tile 2 -> set 1
+    // WPACK: the k loop below is straight-line code -- no load, LDS store or barrier under a condition.  A conditional load ends in a
+    // control-flow merge, and behind a merge (as at a loop's back edge with a different history) the compiler's wait counts fall
+    // back to "everything in flight": the loop with `if (kt + 3 < nk)` around its requests waited vmcnt(0) in front of every LDS
+    // store, i.e. ran at a prefetch distance of one k-step whatever the source said.  Requests past the last k-tile fetch that
+    // tile again instead (a scalar min on the tile index; in bounds, never used), LDS stores past it fill the buffer nobody reads
+    // any more, and the prologue issues its requests in the loop's own order, so that the counts of the first trip are those of
+    // every trip.
+    [[maybe_unused]] auto ktile = [&](int t) { return (t < nk ? t : nk - 1) * BK; };
+    if constexpr (WPACK) {
+        gload(ktile(1), ra0, rb0);   // as step -2 would have: A tile 1 -> set 0, W tile 0 -> set 0
+        wload(ktile(0), wf0);
+        gload(ktile(2), ra1, rb1);   // as step -1: A tile 2 -> set 1, W tile 1 -> set 1
+        wload(ktile(1), wf1);
+    } else {
+        if (nk > 1) gload(BK, ra0, rb0);      // tile 1 -> set 0
+        if (nk > 2) gload(2 * BK, ra1, rb1);  // tile 2 -> set 1
+    }
     __syncthreads();
 #ifdef LAMP_TUNING
     const unsigned long long t_loop = p.trace ? wall_clock64() : 0ull;
     const unsigned long long c_loop = p.trace ? __builtin_readcyclecounter() : 0ull;   // shader-clock cycles (s_memtime)
 #endif
 
+    if constexpr (WPACK) {
+        // step t (parity e): tile t in LDS[e] and W set e; A tile t + 1 in A set e, tile t + 2 in set 1 - e; W tile t + 1 in W set 1 - e.
+        // The step multiplies, stores A tile t + 1 to LDS[1 - e], then refills both sets it has emptied: A tile t + 3, W tile t + 2.
+        int kt = 0;
+        for (; kt + 1 < nk; kt += 2) {
+            compute(0, wf0);
+            lstore(1, ra0, rb0);
+            gload(ktile(kt + 3), ra0, rb0);
+            wload(ktile(kt + 2), wf0);
+            __syncthreads();
+            compute(1, wf1);
+            lstore(0, ra1, rb1);
+            gload(ktile(kt + 4), ra1, rb1);
+            wload(ktile(kt + 3), wf1);
+            __syncthreads();
+        }
+        if (kt < nk) compute(0, wf0);   // an odd number of k-tiles: the last one, in LDS[0] and W set 0
+    } else
     for (int kt = 0; kt < nk; kt += 2) {
         // even step: tile kt in LDS[0]; tile kt+1 in set 0, tile kt+2 in set 1
-        compute(0);
+        compute(0, wf0);
         if (kt + 1 < nk) lstore(1, ra0, rb0);
         if (kt + 3 < nk) gload((kt + 3) * BK, ra0, rb0);
         __syncthreads();
         if (kt + 1 >= nk) break;
         // odd step: tile kt+1 in LDS[1]; tile kt+2 in set 1, tile kt+3 in set 0
-        compute(1);
+        compute(1, wf1);
         if (kt + 2 < nk) lstore(0, ra1, rb1);
         if (kt + 4 < nk) gload((kt + 4) * BK, ra1, rb1);
         __syncthreads();
@@ -464,12 +545,12 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, int tiles_n_seg, 
 #endif
 }
 
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool KTAIL, int MF, bool RPRE, bool VEC, bool RGATHER = false>
-__global__ __launch_bounds__(WAVES_M* WAVES_N * 64, (gemm_min_waves(BM, BN, BK, MF))) void gemm_nt_kernel(GemmParams p, int tiles_n_seg,
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool KTAIL, int MF, bool RPRE, bool VEC, bool RGATHER = false, bool WPACK = false>
+__global__ __launch_bounds__(WAVES_M* WAVES_N * 64, (gemm_min_waves(BM, BN, BK, MF, WPACK))) void gemm_nt_kernel(GemmParams p, int tiles_n_seg,
                                                                           int tiles_n, int tiles_m,
                                                                           int panel_split, FastDiv fd_group,
                                                                           FastDiv fd_seg) {
-    gemm_body<BM, BN, BK, WAVES_M, WAVES_N, KTAIL, MF, RPRE, VEC, RGATHER>(p, tiles_n_seg, tiles_n, tiles_m, panel_split, fd_group, fd_seg);
+    gemm_body<BM, BN, BK, WAVES_M, WAVES_N, KTAIL, MF, RPRE, VEC, RGATHER, WPACK>(p, tiles_n_seg, tiles_n, tiles_m, panel_split, fd_group, fd_seg);
 }
 
 #ifdef LAMP_TUNING
@@ -480,15 +561,15 @@ static size_t g_extra_lds = 0;
 extern "C" __attribute__((visibility("default"))) void lamp_debug_set_gemm_extra_lds(int bytes) { g_extra_lds = size_t(bytes); }
 #endif
 
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool KTAIL, int MF, bool VEC, bool RGATHER = false>
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool KTAIL, int MF, bool VEC, bool RGATHER = false, bool WPACK = false>
 static int launch_cfg2(const GemmParams& p, hipStream_t s) {
-    using T = GemmTile<BM, BN, BK, WAVES_M, WAVES_N, MF>;
+    using T = GemmTile<BM, BN, BK, WAVES_M, WAVES_N, MF, WPACK>;
     constexpr bool RPRE = T::MI * T::NI * (MF == 32 ? 16 : 4) <= 16;
-    auto kern = gemm_nt_kernel<BM, BN, BK, WAVES_M, WAVES_N, KTAIL, MF, RPRE, VEC, RGATHER>;
-    size_t LDS = T::LDS_BYTES;
+    auto kern = gemm_nt_kernel<BM, BN, BK, WAVES_M, WAVES_N, KTAIL, MF, RPRE, VEC, RGATHER, WPACK>;
+    size_t LDS = T::LDS_LAUNCH_BYTES;
     static AttrOnce once;
 #ifdef LAMP_TUNING
-    LDS += g_extra_lds;   // residency experiments: more LDS per workgroup = fewer workgroups per CU
+    if (g_extra_lds) LDS = T::LDS_BYTES + g_extra_lds;   // residency experiments: more LDS per workgroup = fewer workgroups per CU
     if (int e = once.set(reinterpret_cast<const void*>(kern), 160 * 1024)) return e;
 #else
     if (int e = once.set(reinterpret_cast<const void*>(kern), LDS)) return e;
@@ -539,6 +620,23 @@ static int launch_cfg(const GemmParams& p, hipStream_t s) {
     }
     if (p.K % BK) return launch_cfg2<BM, BN, BK, WAVES_M, WAVES_N, true, MF, false>(p, s);
     return launch_cfg2<BM, BN, BK, WAVES_M, WAVES_N, false, MF, false>(p, s);
+}
+
+// The packed-W instantiations: the 32x64x32 tile (1x4 waves) with the 16-byte epilogue, whole k-tiles; with and without the
+// gathered residual.  Everything else a launch may ask for stays on the LDS-staged kernels (gemm_packed_ok).
+static int launch_packed(const GemmParams& p, hipStream_t s) {
+    if (p.rg_tok) return launch_cfg2<32, 64, 32, 1, 4, false, 16, true, true, true>(p, s);
+    return launch_cfg2<32, 64, 32, 1, 4, false, 16, true, false, true>(p, s);
+}
+
+// What the pack can express: every segment has one (format 0: N a multiple of 16, K of 32), in-pack byte offsets fit 31 bits,
+// and the launch takes the 16-byte epilogue.  Anything else takes the staged kernel, silently, with the same bits.
+static bool gemm_packed_ok(const GemmParams& p) {
+    // (+ 64: a tile's fragment blocks past N are addressed too -- and read as zeros -- before the range check drops them)
+    if (!p.vec_epilogue || (p.N & 15) || (p.K & 31) || (int64_t(p.N) + 64) * p.K * 4 >= 0x7fffffffLL) return false;
+    for (int i = 0; i < p.nseg; ++i)
+        if (!p.Wp[i] || !aligned16(p.Wp[i])) return false;
+    return true;
 }
 
 #ifdef LAMP_TUNING
@@ -599,7 +697,7 @@ int launch_gemm(const GemmParams& p_in, hipStream_t s) {
         case 6: return launch_cfg<64, 64, 16, 2, 2>(p, s);
         case 7: return launch_cfg<128, 64, 16, 2, 2>(p, s);
         case 8: return launch_cfg<256, 128, 16, 4, 2>(p, s);
-        case 9: return launch_cfg<32, 64, 32, 1, 4, 16>(p, s);   // waves 32x16 (2 blocks of 16x16)
+        case 9: return gemm_packed_ok(p) ? launch_packed(p, s) : launch_cfg<32, 64, 32, 1, 4, 16>(p, s);   // waves 32x16 (2 blocks of 16x16)
         case 10: return launch_cfg<64, 32, 32, 4, 1, 16>(p, s);  // waves 16x32
         case 11: return launch_cfg<64, 64, 16, 2, 2, 16>(p, s);
         case 12: return launch_cfg<64, 64, 32, 2, 2, 16>(p, s);  // waves 32x32 as 2x2 blocks of 16x16
@@ -626,7 +724,15 @@ int launch_gemm(const GemmParams& p_in, hipStream_t s) {
     const int64_t t64 = tiles(64, 64);
     if (tiles(128, 64) >= 2048 && p.K >= 512) return launch_cfg<128, 64, 16, 2, 2, 16>(p, s);  // short K: fewer, deeper steps
     if (t64 >= 2048) return launch_cfg<64, 64, 32, 2, 2, 16>(p, s);
-    if (t64 >= 1200) return launch_cfg<64, 64, 16, 2, 2, 16>(p, s);
+    // Weight packs (GemmParams::Wp): the 32x64x32 tile reads its W fragments straight from them.  The 2x2-wave tiles above gain
+    // nothing from packs (two waves would fetch every fragment).  LAMP_PACKED_FFN_TILE: launches of 1200-2047 64x64 tiles -- the
+    // encoder FFN at batch 32 -- move from 64x64x16 to the packed 32x64x32 tile as well (profiles/gemm_packed_w_ab.txt).
+#ifndef LAMP_PACKED_FFN_TILE
+#define LAMP_PACKED_FFN_TILE 1
+#endif
+    const bool packed = gemm_packed_ok(p);
+    if (t64 >= 1200 && !(LAMP_PACKED_FFN_TILE && packed)) return launch_cfg<64, 64, 16, 2, 2, 16>(p, s);
+    if (packed) return launch_packed(p, s);
     return launch_cfg<32, 64, 32, 1, 4, 16>(p, s);  // 4 waves of 32x16 (2 blocks each)
 }
 

@@ -24,6 +24,8 @@ struct GemmParams {
     int N;  // per segment
     int nseg;
     const float* W[GEMM_MAX_SEG];
+    const float* Wp[GEMM_MAX_SEG];   // nullable, per segment: lamp_pack_weight(W[s], format 0) -- the packed-W tile reads its fragments from
+                                     // it when EVERY segment has one and the shape allows (gemm.hip: gemm_packed_ok); same bits without
     int64_t ldw;
     const float* bias[GEMM_MAX_SEG];
     float* C[GEMM_MAX_SEG];

@@ -136,6 +136,53 @@ def lib_ab(rounds=9):
         print('%-30s' % name + ''.join('%17.1f/%6.1fT ' % (m, 2.0 * M * Nn * K / m / 1e6) for m in med))
 
 
+def gemm_packed(rounds=9):
+    """Packed-W tile (csrc/gemm.hip, GemmParams::Wp: W fragments straight from a lamp_pack_weight format-0 copy) against the
+    LDS-staged kernels on the launches of the reuters forward at batch 32, round-robin medians in one process.  Columns: the
+    heuristic's staged choice, the forced staged 32x64x32 and 64x64x16 tiles, the packed 32x64x32 tile, and what the heuristic
+    picks when it is handed the packs; every packed result is compared bit for bit with the staged one first."""
+    import statistics
+    lib = N.lib()
+    force = lib.lamp_debug_force_gemm_tile
+    force.argtypes = [ctypes.c_int]
+    force.restype = None
+    dev = torch.device('cuda:0')
+    # name, M, N, K, segments, relu, residual
+    shapes = [('dec 2880x512x512', 2880, 512, 512, 1, 0, 0), ('decQKV 2880x(3x512)x512', 2880, 512, 512, 3, 0, 0),
+              ('encFFN1 9664x512x512 +b relu', 9664, 512, 512, 1, 1, 0), ('encFFN2 9664x512x512 +b +R', 9664, 512, 512, 1, 0, 1),
+              ('encKV 9664x(4x512)x512', 9664, 512, 512, 4, 0, 0)]
+    cols = [('staged heur', 0, False), ('staged 32x64x32', 9, False), ('staged 64x64x16', 11, False), ('packed 32x64x32', 9, True),
+            ('packed heur', 0, True)]
+    print('%-30s' % 'shape (median us)' + ''.join('%18s' % c[0] for c in cols))
+    for name, M, Nn, K, nseg, relu, res in shapes:
+        x = torch.randn(M, K, device=dev)
+        ws = [torch.randn(Nn, K, device=dev) / K ** 0.5 for _ in range(nseg)]
+        packs = [N.weight_pack(w, 0) for w in ws]
+        bs = [torch.randn(Nn, device=dev) for _ in range(nseg)] if (relu or res) else None
+        r = torch.randn(M, Nn, device=dev) if res else None
+        outs = {}
+        for cname, tile, pk in cols:
+            force(tile)
+            outs[cname] = N.linear_packed(x, ws, packs if pk else None, bs, r, relu)
+        force(0)
+        for cname, _, _ in cols[1:]:
+            assert all(torch.equal(a, b) for a, b in zip(outs[cname], outs[cols[0][0]])), (name, cname)
+        keep = [torch.empty(M, Nn, device=dev) for _ in range(nseg)]
+        arr = lambda ts: (ctypes.c_void_p * nseg)(*[N.ptr(t) for t in ts])
+        aw, ap, ab, ac = arr(ws), arr(packs), arr(bs) if bs else None, arr(keep)
+        samples = [[] for _ in cols]
+        for _ in range(rounds):
+            for i, (_, tile, pk) in enumerate(cols):
+                force(tile)
+
+                def fn():
+                    N.check(lib.lamp_linear_packed_fwd(x.data_ptr(), M, K, K, aw, ap if pk else None, nseg, Nn, K, ab, N.ptr(r), Nn, relu,
+                                                       ac, Nn, None, N.stream()), 'linear_packed')
+                samples[i].append(time_fn(fn, iters=20, warm=2))
+        force(0)
+        print('%-30s' % name + ''.join('%18.1f' % statistics.median(v) for v in samples))
+
+
 WALK_SHAPES = [('delic ffn1 31456x2048x1024', 31456, 2048, 1024, 1, 1, 0), ('delic ffn2 31456x1024x2048', 31456, 1024, 2048, 1, 0, 1),
                ('delic fc 31456x1024x1024 +R', 31456, 1024, 1024, 1, 0, 1), ('delic qkv 31456x(3x1024)x1024', 31456, 1024, 1024, 3, 0, 0),
                ('reuters kv 9664x(4x512)x512', 9664, 512, 512, 4, 0, 0), ('syn ffn1 65536x2048x1024', 65536, 2048, 1024, 1, 1, 0)]
@@ -874,4 +921,4 @@ def gemm_clock():
 if __name__ == '__main__':
     which = sys.argv[1] if len(sys.argv) > 1 else 'gemm'
     {'gemm': gemm, 'gemm_ab': gemm_ab, 'lib_ab': lib_ab, 'walk': walk, 'walk_pmc': walk_pmc, 'gemm_gen': gemm_gen, 'attn': attn, 'steady': steady, 'sparse': sparse, 'sparse_rows': sparse_rows,
-     'gemm_trace': gemm_trace, 'gemm_clock': gemm_clock, 'attn_lib_ab': attn_lib_ab, 'attn_tile': attn_tile, 'chain': chain, 'ln': ln, 'attn_one': attn_one, 'attn_maps': attn_maps, 'attn_trace': attn_trace, 'residency': residency, 'slab': slab}[which]()
+     'gemm_trace': gemm_trace, 'gemm_clock': gemm_clock, 'attn_lib_ab': attn_lib_ab, 'attn_tile': attn_tile, 'chain': chain, 'ln': ln, 'attn_one': attn_one, 'attn_maps': attn_maps, 'attn_trace': attn_trace, 'residency': residency, 'slab': slab, 'gemm_packed': gemm_packed}[which]()
