@@ -70,8 +70,9 @@ enum lamp_mask_kind {
                                      the softmax, S = <q, k> / temperature + bias; -inf = blocked, exactly as a masked entry (a
                                      row of -inf comes out NaN, only that row); +inf and NaN are the caller's error.  stride_b
                                      == 0: shared over the batch; heads always share it.  softmax(s + log w) = w exp(s) / sum w
-                                     exp(s): a bias of log w re-weights the attention by w.  A constant: no gradient flows to it,
-                                     the backward entries take no bias (dS = softmax backward of the saved map).  ptr 16-byte
+                                     exp(s): a bias of log w re-weights the attention by w.  A constant to the backward
+                                     entries, which take no bias (dS = softmax backward of the saved map); a caller that trains
+                                     the bias reduces that dS itself (lamp_attn_bias_bwd).  ptr 16-byte
                                      aligned, stride_q % 4 == 0 and stride_b % 4 == 0 (a lane fetches its four consecutive keys
                                      with one 16-byte load; every row is readable up to the next multiple of 4 floats), else
                                      LAMP_E_ALIGN.  Served by every entry that takes a lamp_mask (csrc/attention_bias.hip;
@@ -526,6 +527,28 @@ int lamp_layernorm_bwd(const float* x, const float* residual, int64_t residual_r
 size_t lamp_colsum_workspace_bytes(int64_t M, int64_t N);
 int lamp_colsum(const float* x, int64_t M, int64_t N, int64_t ldx, float* out, void* workspace,
                 size_t workspace_bytes, lamp_stream_t stream);
+
+/* The gradient of a learnable LAMP_MASK_BIAS_F32 score bias shared by batch and heads.  S = Q K^T / temperature + bias, so
+ *   dbias[q*ld + k] = scale * sum_{n < n_slices} dS[(n*lq + q)*lk + k]
+ * with dS [n_slices, lq, lk] contiguous -- what lamp_mha_bwd / lamp_mha_act_bwd leave in their dP argument (n_slices = n_head * B)
+ * and lamp_softmax_bwd writes -- and scale = 1 / inv_temperature (dS carries that factor).  bias: the forward's folded bias
+ * [lq, bias_stride_q] or NULL; where it holds -inf, dbias is written as exactly 0 WHATEVER dS holds there (a fully blocked
+ * row's NaN does not reach the parameter).  A NaN behind an allowed entry stays in that element.  ld >= lk; columns lk .. ld - 1
+ * of dbias are not written.  Two launches, no atomics: lamp_colsum's first stage over the [n_slices, lq * lk] view, then one
+ * pass that adds the partials in a fixed order -- the summation order is a function of n_slices alone, the result is
+ * bit-identical from run to run.  LAMP_E_DIMS (a non-positive size, ld < lk, bias_stride_q < lk), LAMP_E_NULL (dS, dbias,
+ * workspace), LAMP_E_WORKSPACE, in that order, before any launch. */
+size_t lamp_attn_bias_bwd_workspace_bytes(int64_t n_slices, int32_t lq, int32_t lk);
+int lamp_attn_bias_bwd(const float* dS, int64_t n_slices, int32_t lq, int32_t lk, float scale, const float* bias,
+                       int64_t bias_stride_q, float* dbias, int64_t ld, void* workspace, size_t workspace_bytes,
+                       lamp_stream_t stream);
+
+/* The buffer LAMP_FWD_LABEL_BIAS / LAMP_MASK_BIAS_F32 read, from a learnable [L, ld_p] bias and the byte label mask:
+ *   out[q*ld_o + k] = blocked_u8[q*L + k] ? -inf : param[q*ld_p + k]   (k < L);   0 in the pad columns L .. ld_o - 1
+ * with ld_o = (L + 3) & ~3; blocked_u8 NULL = no mask.  One launch, a pure function of its inputs: a weights-only
+ * precomputation that is run again whenever the parameter changed.  LAMP_E_DIMS (L <= 0, ld_p < L), LAMP_E_NULL (param, out). */
+int lamp_label_bias_fold(const float* param, int64_t ld_p, const uint8_t* blocked_u8, int32_t L, float* out,
+                         lamp_stream_t stream);
 
 /* nn.Dropout in training mode (lamp/SubLayers.py:40,113,138): y[e] = keep(e, seed) ? x[e] / (1 - p) : 0 with a
  * counter-based generator -- keep(e, seed) = mix32(e, seed) >= p * 2^32 -- so the mask is a pure function of

@@ -37,8 +37,10 @@ class GraphDecoder(nn.Module):
     def __init__(self, n_tgt_vocab, n_max_seq, n_layers=6, n_head=8, n_head2=8, d_k=64, d_v=64,
                  d_word_vec=512, d_model=512, d_inner_hid=1024, dropout=0.1, dropout2=0.1,
                  no_dec_self_att=False, label_adj_matrix=None, label_mask=None, enc_vec=True,
-                 graph_conv=False, attn_type='softmax', dec_attn_type=None, label_bias=None):
+                 graph_conv=False, attn_type='softmax', dec_attn_type=None, label_bias=None, learn_label_bias=False):
         super().__init__()
+        if learn_label_bias and label_bias is None:   # a learnable graph without a prior starts from zeros
+            label_bias = torch.zeros(n_tgt_vocab, n_tgt_vocab)
         if label_bias is not None:
             # the weighted label graph: an additive (L, L) bias on the label -> label scores, shared by batch and heads
             if no_dec_self_att:
@@ -91,15 +93,55 @@ class GraphDecoder(nn.Module):
                 bias = bias.masked_fill(blocked != 0, float('-inf'))
             bias = N.pad_bias_rows(bias)
         self.register_buffer('label_bias_f32', bias, persistent=False)
+        # the learnable label graph: the (L, L) bias as the caller passed it is a Parameter (in the state_dict; -inf entries and
+        # entries under the mask receive a gradient of exactly 0 and never move), and the buffer above -- still what every
+        # kernel reads, at the same address -- is folded from it again whenever it changed (current_label_bias)
+        self.register_parameter('label_bias', nn.Parameter(label_bias.detach().to(torch.float32).cpu().clone())
+                                if learn_label_bias else None)
+        self._label_bias_key = None
         self.layer_stack = nn.ModuleList(
             DecoderLayer(d_model, d_inner_hid, n_head, n_head2, d_k, d_v, dropout=dropout, dropout2=dropout2,
                          no_dec_self_att=no_dec_self_att, attn_type=attn_type, dec_attn_type=dec_attn_type) for _ in range(n_layers))
 
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        """A state_dict without ``label_bias`` (a run with a constant bias or with none) loads into a learnable decoder, which
+        keeps the bias it was built with: the graph starts from the prior and is trained from there."""
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        if self.label_bias is not None and prefix + 'label_bias' in missing_keys:
+            missing_keys.remove(prefix + 'label_bias')
+
+    def current_label_bias(self):
+        """``label_bias_f32`` (or None), current with the learnable ``label_bias``: lamp_label_bias_fold writes the buffer in
+        place when the parameter's version or address -- or the buffer's own, after .to() -- differ from the last fold's
+        (load_state_dict and optimizer steps bump the version; both are host integers, nothing is read back).  Outside
+        training the fold is followed by a one-off stream synchronisation, as the other weights-only tables of the eval path
+        are: forwards may be issued from several streams.  An nn.DataParallel replica folds its own copy of the parameter
+        into a fresh buffer on every forward."""
+        buf, p = self.label_bias_f32, self.label_bias
+        if p is None:
+            return buf
+        mask = self.label_mask_u8
+        if getattr(self, '_is_replica', False):
+            with torch.no_grad():
+                buf = N.label_bias_fold(p.detach(), mask, torch.empty_like(buf))
+            self.label_bias_f32 = buf
+            return buf
+        key = (p._version, p.data_ptr(), buf.data_ptr(), N.ptr(mask))
+        if key != self._label_bias_key:
+            N.label_bias_fold(p.detach(), mask, buf)
+            if not self.training:
+                torch.cuda.current_stream().synchronize()
+            self._label_bias_key = key
+        return buf
+
     def label_mask_struct(self):
-        bias = self.label_bias_f32
+        bias = self.current_label_bias()
         if bias is not None:   # LAMP_MASK_BIAS_F32: dense -- no tiles, no bits, no sparse flag, in eval and in training
             N.require_device(bias)
-            return N.Mask(N.LAMP_MASK_BIAS_F32, 0, bias.data_ptr(), 0, bias.size(1), None, 0, 0)
+            ms = N.Mask(N.LAMP_MASK_BIAS_F32, 0, bias.data_ptr(), 0, bias.size(1), None, 0, 0)
+            if self.label_bias is not None:   # training.mha_train hands the pair to _MHAFn: the gradient reaches the parameter
+                ms.learnable = (self.label_bias, bias)
+            return ms
         m = self.label_mask_u8
         if m is None:
             return None
@@ -125,7 +167,7 @@ class GraphDecoder(nn.Module):
             from . import training
             y = training._LabelRowsFn.apply(self.tgt_word_emb.weight, B)
             if label_mask is not None:
-                label_mask = N.Mask(label_mask.kind, 0, label_mask.ptr, label_mask.stride_b, label_mask.stride_q, None, 0, 0)
+                label_mask = N.dense_mask(label_mask)
         else:
             y = self.tgt_word_emb.weight.unsqueeze(0).expand(B, -1, -1).contiguous()
         # lamp/Decoders.py:136-138: with a vector encoder there is nothing to pad-mask

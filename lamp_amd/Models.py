@@ -71,9 +71,9 @@ class LAMP(nn.Module):
                  embs_share_weight=True, encoder='selfatt', decoder='sa_m', enc_transform='', onehot=False,
                  no_enc_pos_embedding=False, no_dec_self_att=False, loss='ce', label_adj_matrix=None,
                  label_mask=None, matching_mlp=False, graph_conv=False, attn_type='softmax', int_preds=False,
-                 dec_attn_type=None, label_bias=None, enc_self_attn=False):
+                 dec_attn_type=None, label_bias=None, learn_label_bias=False, enc_self_attn=False):
         super().__init__()
-        if label_bias is not None and decoder != 'graph':
+        if (label_bias is not None or learn_label_bias) and decoder != 'graph':
             raise NotImplementedError('label_bias belongs to the graph decoder, not to decoder=%r' % (decoder,))
         if dec_attn_type is not None and decoder != 'graph':
             raise NotImplementedError('dec_attn_type belongs to the graph decoder, not to decoder=%r' % (decoder,))
@@ -112,7 +112,8 @@ class LAMP(nn.Module):
                 d_word_vec=d_word_vec, d_model=d_model, d_k=d_k, d_v=d_v, d_inner_hid=d_inner_hid,
                 dropout=dec_dropout, dropout2=dec_dropout2, no_dec_self_att=no_dec_self_att,
                 label_adj_matrix=label_adj_matrix, label_mask=label_mask, enc_vec=self.enc_vec,
-                graph_conv=graph_conv, attn_type=attn_type, dec_attn_type=dec_attn_type, label_bias=label_bias)
+                graph_conv=graph_conv, attn_type=attn_type, dec_attn_type=dec_attn_type, label_bias=label_bias,
+                learn_label_bias=bool(learn_label_bias))
         elif decoder == 'mlp':
             self.decoder = MLPDecoder(
                 n_tgt_vocab, n_max_seq_e, n_max_seq_d, n_layers=n_layers_dec, n_head=n_head, d_word_vec=d_word_vec,
@@ -163,6 +164,8 @@ class LAMP(nn.Module):
         updates via ``p.data`` do not bump ``p._version``, which is what the cache otherwise watches)."""
         self._native_cache = None
         self._param_list = None
+        if getattr(getattr(self, 'decoder', None), '_label_bias_key', None) is not None:
+            self.decoder._label_bias_key = None   # a learnable label bias is folded into its buffer again on the next forward
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         """nn.Module.load_state_dict; additionally accepts checkpoints saved from an nn.DataParallel wrapper
@@ -264,7 +267,7 @@ class LAMP(nn.Module):
         mask = self.decoder.label_mask_u8
         tiles = self.decoder.label_tiles
         bits = self.decoder.label_mask_bits
-        bias = getattr(self.decoder, 'label_bias_f32', None)
+        bias = self.decoder.current_label_bias()   # (a learnable bias: folded again here when the parameter changed)
         if bias is not None:   # LAMP_FWD_LABEL_BIAS: the bias rides in the label_mask slot, its companions stay empty
             mask, tiles, bits = bias, None, None
         hoist = self.cache_layer0_query and not replica   # the hoisted projection needs a one-off stream sync

@@ -185,6 +185,9 @@ PROTOTYPES = {
                                      _vp, _sz, _vp]),
     'lamp_colsum_workspace_bytes': (_sz, [_i64, _i64]),
     'lamp_colsum': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    'lamp_attn_bias_bwd_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'lamp_attn_bias_bwd': (C.c_int, [_vp, _i64, _i32, _i32, _f, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
+    'lamp_label_bias_fold': (C.c_int, [_vp, _i64, _vp, _i32, _vp, _vp]),
     'lamp_dropout': (C.c_int, [_vp, _i64, _f, C.c_uint32, _vp, _vp]),
     'lamp_softmax_bwd': (C.c_int, [_vp, _vp, _i64, _i32, _f, _vp, _vp]),
     'lamp_diag_logits_bwd': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -236,7 +239,8 @@ PROTOTYPES = {
 
 # entry points added without an ABI bump (no struct changed): a library of the same ABI version built before them lacks the
 # symbols -- same-box A/B runs against the previous build (LAMP_HIP_LIBRARY) -- and their callers ask with getattr
-LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs')
+LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs', 'lamp_attn_bias_bwd_workspace_bytes', 'lamp_attn_bias_bwd',
+                     'lamp_label_bias_fold')
 
 _lib = None
 _lock = threading.Lock()
@@ -361,6 +365,16 @@ def make_mask(mask, B, lq, lk):
     sb = 0 if m.size(0) == 1 else m.stride(0)
     sq = 0 if m.size(1) == 1 else m.stride(1)
     return Mask(LAMP_MASK_U8, 0, m.data_ptr(), sb, sq, None, 0), m
+
+
+def dense_mask(m):
+    """A copy of the descriptor without flags, tile list and pair count: what the map-writing (training) attention takes, which
+    visits every key tile.  A learnable bias's (parameter, folded buffer) pair (GraphDecoder.label_mask_struct) rides along."""
+    out = Mask(m.kind, 0, m.ptr, m.stride_b, m.stride_q, None, 0, 0)
+    learnable = getattr(m, 'learnable', None)
+    if learnable is not None:
+        out.learnable = learnable
+    return out
 
 
 def pad_bias_rows(bias):
@@ -842,7 +856,8 @@ def mha_bwd(desc, xq, xk, xv, q, k, v, a, P, Pd, o, dy, wq, wk, wv, fc, ln_g, se
             defer_reduce=False, shared_qk=False, act=LAMP_ATTN_SOFTMAX):
     """lamp_mha_bwd -> dict of gradients and of the buffers deferred weight gradients are computed from; shared_qk: xq and xk
     are one tensor (self-attention) -- r['dxq'] is then its whole gradient and r['dxk'] None; with defer_reduce,
-    r['pending'] = ([job], buffers to keep alive): dgamma / dbeta are finished by reduce_partials_grouped later."""
+    r['pending'] = ([job], buffers to keep alive): dgamma / dbeta are finished by reduce_partials_grouped later; r['dS']: the
+    score gradient (H * B, lq, lk)."""
     B, lq, lk, d, H, dk, dv = desc.B, desc.lq, desc.lk, desc.d_model, desc.n_head, desc.d_k, desc.d_v
     dev = xq.device
     e = torch.empty
@@ -880,6 +895,7 @@ def mha_bwd(desc, xq, xk, xv, q, k, v, a, P, Pd, o, dy, wq, wk, wv, fc, ln_g, se
     else:
         check(L.lamp_mha_bwd(C.byref(desc), C.byref(wts), *tail), 'lamp_mha_bwd')
     r['pending'] = ([job[0]], (part, vec)) if defer_reduce else None
+    r['dS'] = dP   # (H * B, lq, lk), slice h * B + b: the score gradient the call leaves in its dP argument (attn_bias_bwd reads it)
     if shared_qk:   # r['dxq'] is the gradient of the one tensor behind xq and xk
         r['dxk'] = None
     if r['d_o'] is None:
@@ -943,6 +959,37 @@ def colsum(x):
     nb = lib().lamp_colsum_workspace_bytes(M, Nn)
     ws = workspace(nb, xc.device)
     check(lib().lamp_colsum(ptr(xc), M, Nn, Nn, ptr(out), ptr(ws), nb, stream()), 'lamp_colsum')
+    return out
+
+
+def attn_bias_bwd(dS, scale, folded=None, out=None):
+    """lamp_attn_bias_bwd: dS (.., lq, lk) contiguous fp32 -> (lq, lk) = scale * its sum over every leading axis, exactly 0
+    where `folded` (the forward's (lq, >= lk) bias buffer, or None) holds -inf.  out: a (lq, ld >= lk) tensor to fill instead."""
+    require_device(dS, folded, out)
+    if dS.dtype != torch.float32 or not dS.is_contiguous():
+        raise ValueError('attn_bias_bwd takes the contiguous fp32 dS buffer as the backward leaves it')
+    lq, lk = dS.shape[-2:]
+    n = dS.numel() // (lq * lk)
+    if out is None:
+        out = torch.empty((lq, lk), dtype=torch.float32, device=dS.device)
+    nb = lib().lamp_attn_bias_bwd_workspace_bytes(n, lq, lk)
+    ws = workspace(nb, dS.device)
+    check(lib().lamp_attn_bias_bwd(ptr(dS), n, lq, lk, float(scale), ptr(folded), folded.stride(0) if folded is not None else 0,
+                                   ptr(out), out.stride(0), ptr(ws), nb, stream()), 'lamp_attn_bias_bwd')
+    return out
+
+
+def label_bias_fold(param, blocked_u8, out):
+    """lamp_label_bias_fold: the learnable (L, L) bias and the byte label mask (or None) -> `out`, the (L, (L + 3) & ~3) buffer
+    the bias kernels read (blocked = -inf, pad columns 0), in place."""
+    require_device(param, blocked_u8, out)
+    L = param.size(0)
+    if (param.dtype != torch.float32 or param.dim() != 2 or param.size(1) != L or param.stride(1) != 1 or
+            tuple(out.shape) != (L, (L + 3) & ~3) or out.dtype != torch.float32 or not out.is_contiguous() or
+            (blocked_u8 is not None and (blocked_u8.dtype != torch.uint8 or tuple(blocked_u8.shape) != (L, L) or
+                                         not blocked_u8.is_contiguous()))):
+        raise ValueError('label_bias_fold: fp32 (L, L) parameter, uint8 (L, L) mask or None, fp32 (L, (L + 3) & ~3) output')
+    check(lib().lamp_label_bias_fold(ptr(param), param.stride(0), ptr(blocked_u8), L, ptr(out), stream()), 'lamp_label_bias_fold')
     return out
 
 

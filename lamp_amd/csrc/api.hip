@@ -582,6 +582,22 @@ int lamp_colsum(const float* x, int64_t M, int64_t N, int64_t ldx, float* out, v
     return launch_colsum(x, M, N, ldx, out, workspace, workspace_bytes, hipStream_t(stream));
 }
 
+size_t lamp_attn_bias_bwd_workspace_bytes(int64_t n_slices, int32_t lq, int32_t lk) {
+    return attn_bias_bwd_workspace_bytes(n_slices, lq, lk);
+}
+
+int lamp_attn_bias_bwd(const float* dS, int64_t n_slices, int32_t lq, int32_t lk, float scale, const float* bias,
+                       int64_t bias_stride_q, float* dbias, int64_t ld, void* workspace, size_t workspace_bytes,
+                       lamp_stream_t stream) {
+    return launch_attn_bias_bwd(dS, n_slices, lq, lk, scale, bias, bias_stride_q, dbias, ld, workspace, workspace_bytes,
+                                hipStream_t(stream));
+}
+
+int lamp_label_bias_fold(const float* param, int64_t ld_p, const uint8_t* blocked_u8, int32_t L, float* out,
+                         lamp_stream_t stream) {
+    return launch_label_bias_fold(param, ld_p, blocked_u8, L, out, hipStream_t(stream));
+}
+
 int lamp_dropout(const float* x, int64_t n, float p, uint32_t seed, float* y, lamp_stream_t stream) {
     return launch_dropout(x, n, p, seed, y, hipStream_t(stream));
 }

@@ -195,6 +195,37 @@ __global__ __launch_bounds__(256) void reduce_group_kernel(ReduceGroup g) {
                           int(blockIdx.x) - g.block_begin[idx]);
 }
 
+// Second stage of the learnable label bias's gradient (lamp_attn_bias_bwd): dbias[q][k] = scale * sum_p partial[p][q * lk + k],
+// the partials added in the order p = 0, 1, ... (P is a function of n_slices alone), and exactly 0 where the forward's folded
+// bias is -inf whatever the partials hold there (a fully blocked row's NaN stays out of the parameter).  One thread per
+// (q, k), consecutive threads on consecutive k: every load and the store are coalesced along k.
+__global__ __launch_bounds__(256) void attn_bias_bwd_reduce_kernel(const float* __restrict__ partial, int P, int64_t n, int lk,
+                                                                   float scale, const float* __restrict__ bias,
+                                                                   int64_t bias_stride_q, float* __restrict__ dbias, int64_t ld) {
+    const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int64_t q = e / lk;
+    const int k = int(e - q * lk);
+    float s = 0.f;
+    for (int p = 0; p < P; ++p) s += partial[int64_t(p) * n + e];
+    const bool blocked = bias != nullptr && bias[q * bias_stride_q + k] == -INFINITY;
+    dbias[q * ld + k] = blocked ? 0.f : scale * s;
+}
+
+// The buffer the bias kernels read, from a learnable (L, L) bias: out[q][k] = blocked[q * L + k] ? -inf : param[q * ld_p + k]
+// for k < L, 0 in the pad columns L .. ld_o - 1 (lamp_label_bias_fold).
+__global__ __launch_bounds__(256) void label_bias_fold_kernel(const float* __restrict__ param, int64_t ld_p,
+                                                              const uint8_t* __restrict__ blocked, int L, int ld_o,
+                                                              float* __restrict__ out) {
+    const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= int64_t(L) * ld_o) return;
+    const int64_t q = e / ld_o;
+    const int k = int(e - q * ld_o);
+    float v = 0.f;
+    if (k < L) v = (blocked != nullptr && blocked[q * L + k]) ? -INFINITY : param[q * ld_p + k];
+    out[e] = v;
+}
+
 // Counter-based dropout (mix32 / DropoutSpec in lamp_kernels.h).  The same call with the same seed applied to the
 // gradient is the backward pass.
 __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x, int64_t n, unsigned threshold,
@@ -360,6 +391,41 @@ int launch_colsum(const float* x, int64_t M, int64_t N, int64_t ldx, float* out,
         return 0;
     }
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)gr), dim3(256), 0, s, partial, chunks, N, N, out, out, out);
+    return int(hipGetLastError());
+}
+
+size_t attn_bias_bwd_workspace_bytes(int64_t n_slices, int lq, int lk) {
+    if (n_slices <= 0 || lq <= 0 || lk <= 0) return 0;
+    return colsum_workspace_bytes(n_slices, int64_t(lq) * lk);
+}
+
+int launch_attn_bias_bwd(const float* dS, int64_t n_slices, int lq, int lk, float scale, const float* bias, int64_t bias_stride_q,
+                         float* dbias, int64_t ld, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (n_slices <= 0 || lq <= 0 || lk <= 0 || ld < lk || (bias && bias_stride_q < lk)) return LAMP_E_DIMS;
+    const int64_t n = int64_t(lq) * lk;
+    const int64_t gx = (n + 255) / 256;
+    if (gx > 0x7fffffffLL) return LAMP_E_DIMS;
+    if (!dS || !dbias || !ws) return LAMP_E_NULL;
+    if (ws_bytes < attn_bias_bwd_workspace_bytes(n_slices, lq, lk)) return LAMP_E_WORKSPACE;
+    // first stage: the column sum's own partial kernel over the [n_slices, lq * lk] view of dS
+    const int chunks = colsum_chunks(n_slices);
+    const int64_t rows_per_chunk = (n_slices + chunks - 1) / chunks;
+    float* partial = static_cast<float*>(ws);
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)gx, chunks), dim3(256), 0, s, dS, n_slices, n, n, rows_per_chunk,
+                       partial);
+    if (int e = int(hipGetLastError())) return e;
+    hipLaunchKernelGGL(attn_bias_bwd_reduce_kernel, dim3((unsigned)gx), dim3(256), 0, s, partial, chunks, n, lk, scale, bias,
+                       bias_stride_q, dbias, ld);
+    return int(hipGetLastError());
+}
+
+int launch_label_bias_fold(const float* param, int64_t ld_p, const uint8_t* blocked, int L, float* out, hipStream_t s) {
+    if (L <= 0 || L > 0x7ffffff0 || ld_p < L) return LAMP_E_DIMS;
+    if (!param || !out) return LAMP_E_NULL;
+    const int ld_o = (L + 3) & ~3;
+    const int64_t gx = (int64_t(L) * ld_o + 255) / 256;
+    if (gx > 0x7fffffffLL) return LAMP_E_DIMS;
+    hipLaunchKernelGGL(label_bias_fold_kernel, dim3((unsigned)gx), dim3(256), 0, s, param, ld_p, blocked, L, ld_o, out);
     return int(hipGetLastError());
 }
 

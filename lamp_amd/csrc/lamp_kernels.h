@@ -222,6 +222,11 @@ int launch_colsum(const float* x, int64_t M, int64_t N, int64_t ldx, float* out,
 // job_out (both above): skip the second-stage launch and describe it instead -- the partials in ws then have to outlive the
 // call until launch_reduce_group has run them (lamp_reduce_partials_grouped)
 int launch_reduce_group(const lamp_reduce_job* jobs, int n, hipStream_t s);
+// the learnable label bias: dbias = scale * sum over slices of dS, 0 where the folded bias is -inf; and the fold itself
+size_t attn_bias_bwd_workspace_bytes(int64_t n_slices, int lq, int lk);
+int launch_attn_bias_bwd(const float* dS, int64_t n_slices, int lq, int lk, float scale, const float* bias, int64_t bias_stride_q,
+                         float* dbias, int64_t ld, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_label_bias_fold(const float* param, int64_t ld_p, const uint8_t* blocked, int L, float* out, hipStream_t s);
 int launch_dropout(const float* x, int64_t n, float p, uint32_t seed, float* y, hipStream_t s);
 int launch_softmax_bwd(const float* P, const float* dP, int64_t rows, int lk, float scale, float* dS, hipStream_t s,
                        const DropoutSpec* drop = nullptr);   // drop: dP is the gradient of dropout(P), mask applied on load

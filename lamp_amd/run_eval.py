@@ -176,6 +176,17 @@ def load_checkpoint_label_bias(ckpt):
     return kind, float(getattr(settings, 'label_bias_scale', 1.0))
 
 
+def load_checkpoint_learn_label_bias(ckpt):
+    """Whether a LOADED checkpoint (load_checkpoint_object) holds a trained label graph (run_train -learn_label_bias): its
+    'settings' say so, or -- a bare state_dict, saved from an nn.DataParallel wrapper or not -- its weights hold
+    `decoder.label_bias`.  The bias then comes from the weights and is not rebuilt from the train split."""
+    if isinstance(ckpt, dict) and 'model' in ckpt:
+        if bool(getattr(ckpt.get('settings'), 'learn_label_bias', False)):
+            return True
+        ckpt = ckpt['model']
+    return isinstance(ckpt, dict) and ('decoder.label_bias' in ckpt or 'module.decoder.label_bias' in ckpt)
+
+
 def load_checkpoint_head_geometry(ckpt):
     """{'n_head2' / 'd_k' / 'd_v': value} for each of run_train's `-n_head2`, `-d_k` and `-d_v` that the 'settings' of a LOADED
     checkpoint (load_checkpoint_object) carry as a positive integer; empty for one that says nothing about them (a bare
@@ -250,16 +261,19 @@ def main(argv=None):
     stored = load_checkpoint_label_bias(ckpt)
     geometry = dict(n_head2=opt.n_head2, d_k=opt.d_k, d_v=opt.d_v)
     geometry.update(load_checkpoint_head_geometry(ckpt))   # the checkpoint's settings override the flags
+    learn = load_checkpoint_learn_label_bias(ckpt)
     del ckpt
     if stored is not None:   # the checkpoint's settings override the flags
         bias_kind, bias_scale = stored
-    bias = D.build_label_bias(data, bias_kind, bias_scale, device)
+    # a trained label graph is among the weights (decoder.label_bias): nothing to rebuild but the mask above
+    bias = None if learn else D.build_label_bias(data, bias_kind, bias_scale, device)
     model = LAMP(n_src, n_labels, data['settings'].max_seq_len, n_labels, n_layers_enc=opt.n_layers_enc,
                  n_layers_dec=opt.n_layers_dec, n_head=h, n_head2=geometry['n_head2'], d_word_vec=d, d_model=d,
                  d_inner_hid=opt.d_inner_hid, d_k=geometry['d_k'], d_v=geometry['d_v'], encoder='graph', decoder='graph',
                  no_enc_pos_embedding=opt.no_enc_pos_embedding, no_dec_self_att=opt.no_dec_self_att,
                  label_adj_matrix=adj, label_mask=opt.label_mask, dec_dropout2=False, onehot=opt.onehot, enc_self_attn=live,
-                 dec_attn_type=None if attn_type == 'softmax' else attn_type, label_bias=bias)
+                 dec_attn_type=None if attn_type == 'softmax' else attn_type, label_bias=bias,
+                 learn_label_bias=learn)
     if state is not None:
         model.load_state_dict(state)
     model = model.to(device).eval()

@@ -83,6 +83,10 @@ def parse(argv=None):
                          "co-occurrence counts (LAMP(label_bias=...)): adj = scale on every prior edge (with -label_mask none: "
                          "the soft prior), logp = scale * smoothed log P(j | i); stored in the checkpoint's settings for run_eval")
     ap.add_argument('-label_bias_scale', type=float, default=1.0)
+    ap.add_argument('-learn_label_bias', action='store_true',
+                    help="train the label graph: the score bias is a parameter (LAMP(learn_label_bias=True)), initialised from "
+                         "-label_bias adj|logp or from zeros with none; -label_mask still decides which edges exist at all; "
+                         "stored in the checkpoint's settings (and the bias in its weights) for run_eval")
     ap.add_argument('-optim_impl', choices=['lamp', 'torch'], default=DEFAULT_OPTIM_IMPL,
                     help='lamp = lamp_amd.optim (one lamp_optim_step launch per step); torch = torch.optim (fused=True for adam)')
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4], help='batches in flight in the valid / test epochs')
@@ -160,6 +164,9 @@ def derive(opt):
     opt.label_bias_scale = float(getattr(opt, 'label_bias_scale', 1.0))
     if opt.label_bias != 'none':
         name += '.lbias_%s_%s' % (opt.label_bias, opt.label_bias_scale)
+    opt.learn_label_bias = bool(getattr(opt, 'learn_label_bias', False))
+    if opt.learn_label_bias:
+        name += '.lbias_learn'
     if opt.name:
         name += '.' + str(opt.name)
     opt.model_name = os.path.join(opt.results_dir, opt.dataset, name)
@@ -196,7 +203,8 @@ def build_model(opt, data, device):
                 encoder=opt.encoder, decoder=opt.decoder, onehot=opt.onehot, no_enc_pos_embedding=opt.no_enc_pos_embedding,
                 no_dec_self_att=opt.no_dec_self_att, loss=opt.loss, label_adj_matrix=adj, label_mask=opt.label_mask,
                 int_preds=opt.int_preds, enc_self_attn=opt.enc_self_att,
-                dec_attn_type=None if opt.attn_type == 'softmax' else opt.attn_type, label_bias=bias)
+                dec_attn_type=None if opt.attn_type == 'softmax' else opt.attn_type, label_bias=bias,
+                learn_label_bias=opt.learn_label_bias)
 
 
 def build_optimizer(model, opt):
@@ -211,8 +219,10 @@ def build_optimizer(model, opt):
 
 
 def checkpoint_settings(opt):
-    """The Namespace that travels in the checkpoint: plain values only, so that it unpickles anywhere."""
-    return argparse.Namespace(**{k: v for k, v in vars(opt).items() if isinstance(v, (bool, int, float, str, type(None)))})
+    """The Namespace that travels in the checkpoint: plain values only, so that it unpickles anywhere.  `learn_label_bias`
+    travels only when it is set: without the flag the settings are what they were before it existed."""
+    return argparse.Namespace(**{k: v for k, v in vars(opt).items() if isinstance(v, (bool, int, float, str, type(None)))
+                                 and (k != 'learn_label_bias' or v)})
 
 
 def save_model(opt, epoch_i, model, valid_loss, valid_losses):

@@ -364,8 +364,11 @@ class _MHAFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xq, xkv, wq, wk, wv, fc, ln_g, ln_b, n_head, mask, keep, p_attn, p_out, seed_attn, seed_out,
-                xv=None, defer=None, act=0):
-        """act: N.LAMP_ATTN_SIGMOID for sigmoid attention (no row normalisation; blocked entries 0).  xkv: the key source and, unless ``xv`` is given, the value source too (every layer of the reference passes one
+                xv=None, defer=None, act=0, bias=None, bias_folded=None):
+        """bias: the learnable (lk, lk) score bias of the decoder's label self-attention (GraphDecoder(learn_label_bias=True)) or
+        None; ``mask`` then already is the LAMP_MASK_BIAS_F32 descriptor of ``bias_folded``, the padded buffer folded from it
+        (blocked = -inf), and the backward returns d bias = temperature * sum over heads and batch of dS, 0 where that buffer
+        is -inf.  act: N.LAMP_ATTN_SIGMOID for sigmoid attention (no row normalisation; blocked entries 0).  xkv: the key source and, unless ``xv`` is given, the value source too (every layer of the reference passes one
         tensor for both, lamp/Layers.py:16,35,40; the module itself accepts two, lamp/SubLayers.py:77-93)."""
         ctx.defer = defer   # (wq, wk, wv, fc, ln_g, ln_b) as the leaf Parameters, or None
         # self-attention: one tensor is query, key and value source -- its three gradient branches are summed in place by the
@@ -377,6 +380,10 @@ class _MHAFn(torch.autograd.Function):
         dk, dv = wq.size(0) // H, wv.size(0) // H
         inv_t = 1.0 / float(dk) ** 0.5
         ctx.act = act
+        if bias is not None and (act == N.LAMP_ATTN_SIGMOID or bias_folded is None or tuple(bias.shape) != (lq, lk)):
+            raise NotImplementedError('a learnable score bias: softmax attention, (lq, lk), with its folded buffer')
+        # (not through save_for_backward: the buffer is refreshed in place from the parameter, and only its -inf pattern is read)
+        ctx.bias_folded = bias_folded if bias is not None else None
         ctx.composite = (COMPOSITE_CALLS and dk <= 128 and dv <= 128 and
                          _plain(xq, xkv, xv, wq, wk, wv, fc, ln_g, ln_b) and (fc is not None or H * dv == d))
         if ctx.composite:
@@ -419,6 +426,7 @@ class _MHAFn(torch.autograd.Function):
         B, lq, lk, H, dk, dv, inv_t, p_attn, p_out, seed_attn, seed_out, has_fc, has_xv = ctx.cfg
         d = xq.size(-1)
         defer = ctx.defer.live() if ctx.defer is not None else None
+        want_dbias = ctx.bias_folded is not None and ctx.needs_input_grad[18]
         if ctx.composite:
             wait, wait_fc = defer is not None, defer is not None and p_out > 0
             desc = N.MhaTrainDesc(B, lq, lk, d, H, dk, dv, inv_t, p_attn, p_out, seed_attn & 0xffffffff,
@@ -436,8 +444,9 @@ class _MHAFn(torch.autograd.Function):
                 _weight_grads.add(defer[2], r['dv'], xv.view(-1, d) if has_xv else xkv2)
             if wait_fc and has_fc:
                 _weight_grads.add(defer[3], r['d_o'], a.view(-1, H * dv))
+            dbias = N.attn_bias_bwd(r['dS'], 1.0 / inv_t, ctx.bias_folded) if want_dbias else None
             return (r['dxq'].view(xq.shape), None if ctx.shared_qk else r['dxk'].view(xkv.shape), r['dwq'], r['dwk'], r['dwv'], r['dfc'], r['dgamma'],
-                    r['dbeta']) + (None,) * 7 + (r['dxv'].view(xv.shape) if has_xv else None, None, None)
+                    r['dbeta']) + (None,) * 7 + (r['dxv'].view(xv.shape) if has_xv else None, None, None, dbias, None)
         xq2, xkv2 = xq.reshape(-1, d), xkv.reshape(-1, d)
         xv2 = xv.reshape(-1, d) if has_xv else xkv2
         dz, do, dg, db, _ = N.layernorm_bwd(o.view(xq2.shape), xq2, ln_g, dy.reshape(xq2.shape), dropout_p=p_out,
@@ -465,6 +474,7 @@ class _MHAFn(torch.autograd.Function):
             N.sigmoid_attn_bwd(P4, dP, inv_t, out=dP)                                             # dS = P (1 - P) dP / t (in place)
         else:
             N.softmax_bwd(P4, dP, inv_t, out=dP)                                                  # dS (in place)
+        dbias = N.attn_bias_bwd(dP, 1.0 / inv_t, ctx.bias_folded) if want_dbias else None          # d bias = t * sum_{h, b} dS
         dq_buf, dk_buf = torch.empty_like(q), torch.empty_like(k)
         N.matmul_nt(dP, kh.transpose(-1, -2), out=heads(dq_buf, lq, dk))                          # dQ = dS K
         N.matmul_nt(dP.transpose(-1, -2), qh.transpose(-1, -2), out=heads(dk_buf, lk, dk))        # dK = dS^T Q
@@ -482,14 +492,14 @@ class _MHAFn(torch.autograd.Function):
         if ctx.shared_qk:   # one tensor behind query, key and value: the three branches summed in place (as lamp_mha_bwd does)
             N.matmul_nt(dk2, wk.t(), out=dxq, accumulate=True)
             N.matmul_nt(dv2, wv.t(), out=dxq, accumulate=True)
-            return (dxq.view(xq.shape), None, dwq, dwk, dwv, dfc, dg, db) + (None,) * 7 + (None, None, None)
+            return (dxq.view(xq.shape), None, dwq, dwk, dwv, dfc, dg, db) + (None,) * 7 + (None, None, None, dbias, None)
         dxkv = N.matmul_nt(dk2, wk.t())
         dxv = None
         if has_xv:
             dxv = N.matmul_nt(dv2, wv.t()).view(xv.shape)
         else:
             N.matmul_nt(dv2, wv.t(), out=dxkv, accumulate=True)
-        return (dxq.view(xq.shape), dxkv.view(xkv.shape), dwq, dwk, dwv, dfc, dg, db) + (None,) * 7 + (dxv, None, None)
+        return (dxq.view(xq.shape), dxkv.view(xkv.shape), dwq, dwk, dwv, dfc, dg, db) + (None,) * 7 + (dxv, None, None, dbias, None)
 
 
 class _ReadoutFn(torch.autograd.Function):
@@ -515,11 +525,12 @@ def ffn_train(mod, x, seeds):
 
 def mha_train(mod, xq, xkv, mask, keep, seeds, xv=None):
     fc = mod.fc.weight if hasattr(mod, 'fc') else None
+    bias, folded = getattr(mask, 'learnable', None) or (None, None)   # GraphDecoder.label_mask_struct: (parameter, its folded buffer)
     return _MHAFn.apply(xq, xkv, mod.w_qs.weight, mod.w_ks.weight, mod.w_vs.weight, fc, mod.layer_norm.weight,
                         mod.layer_norm.bias, mod.n_head, mask, keep, float(mod.attention.dropout.p),
                         float(mod.dropout.p), seeds.next(), seeds.next(), xv,
                         _deferrable(mod.w_qs.weight, mod.w_ks.weight, mod.w_vs.weight, fc, mod.layer_norm.weight,
-                                    mod.layer_norm.bias), getattr(mod.attention, 'act', 0))
+                                    mod.layer_norm.bias), getattr(mod.attention, 'act', 0), bias, folded)
 
 
 class _LinearFn(torch.autograd.Function):
@@ -629,7 +640,7 @@ def forward_train(model, src_seq, src_pos, return_attns=False, int_preds=False, 
     y = _LabelRowsFn.apply(dec.tgt_word_emb.weight, B)
     label_mask = dec.label_mask_struct()
     if label_mask is not None:  # the map-writing attention variant visits every tile
-        label_mask = N.Mask(label_mask.kind, 0, label_mask.ptr, label_mask.stride_b, label_mask.stride_q, None, 0, 0)
+        label_mask = N.dense_mask(label_mask)
     int_outs, slf_attns, enc_dec_attns = [], [], []
     for layer in dec.layer_stack:
         y, a_enc = mha_train(layer.enc_attn, y, x, pad_mask, keep, seeds)

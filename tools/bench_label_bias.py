@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The weighted label graph (LAMP(label_bias=...)) against today's routes, same process and device (GPU only).
 
-    python tools/bench_label_bias.py [--out profiles/label_bias_bench.json] [--skip-4096]
+    python tools/bench_label_bias.py [--out profiles/label_bias_bench.json] [--skip-4096] [--only-learn]
 
 1. The label self-attention launch (lamp_sdpa_fwd, no maps, head-fused layout, batch 32, d_k = d_v = 128, 4 heads) with the
    graph as a LAMP_MASK_BIAS_F32 bias (csrc/attention_bias.hip) against the descriptor GraphDecoder hands the library today for
@@ -9,6 +9,10 @@
    4096, for 'none' and 'prior' graphs.  At 4096 the prior is the Bernoulli(0.05) graph whose route today is the pair kernel.
    The two are timed alternately, best of the rounds.
 2. The reuters-shaped batch-32 forward (samples/s) and one training step (ms) with and without a bias.
+3. The learnable bias (LAMP(learn_label_bias=True)): lamp_attn_bias_bwd against lamp_colsum on the same dS [H B = 128, L, L] at
+   L = 90, 159 and 983, alternating; and the reuters-shaped training step with a constant bias (the flag off) against the same
+   model with the flag on, alternating round by round -- every round's ratio is kept, the report gives their median and range.
+   --only-learn runs this part alone and merges it into an existing result file.
 """
 import argparse
 import ctypes as C
@@ -45,6 +49,92 @@ def time_us_alternating(fns, iters, warm=5, rounds=4):
             torch.cuda.synchronize()
             best[i] = min(best[i], e0.elapsed_time(e1) / iters * 1e3)
     return best
+
+
+def time_us_rounds(fns, iters, warm=5, rounds=8):
+    """Every round's time per call of each function ([fn][round]), the functions taking turns round by round."""
+    for fn in fns:
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[i].append(e0.elapsed_time(e1) / iters * 1e3)
+    return times
+
+
+def ratio_summary(num, den):
+    """Median, minimum and maximum of the per-round ratios num[r] / den[r]."""
+    r = sorted(a / b for a, b in zip(num, den))
+    mid = r[len(r) // 2] if len(r) % 2 else 0.5 * (r[len(r) // 2 - 1] + r[len(r) // 2])
+    return dict(median=round(mid, 4), min=round(r[0], 4), max=round(r[-1], 4), rounds=len(r))
+
+
+def bias_bwd_rows(dev, n_slices=128):
+    """lamp_attn_bias_bwd (with the -inf select of a 20 % prior) against lamp_colsum on the same dS."""
+    rows = []
+    lib = N.lib()
+    for L in (90, 159, 983):
+        dS = torch.randn(n_slices, L, L, device=dev) * 0.01
+        adj = synthetic.make_adjacency(L, 0.2, 0)
+        folded = N.pad_bias_rows(torch.zeros(L, L).masked_fill(adj == 0, float('-inf'))).to(dev)
+        out = torch.empty(L, L, device=dev)
+        nb = lib.lamp_attn_bias_bwd_workspace_bytes(n_slices, L, L)
+        assert nb == lib.lamp_colsum_workspace_bytes(n_slices, L * L)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+
+        def bwd():
+            N.check(lib.lamp_attn_bias_bwd(dS.data_ptr(), n_slices, L, L, 8.0, folded.data_ptr(), folded.size(1), out.data_ptr(), L,
+                                           ws.data_ptr(), nb, N.stream()), 'lamp_attn_bias_bwd')
+
+        def colsum():
+            N.check(lib.lamp_colsum(dS.data_ptr(), n_slices, L * L, L * L, out.data_ptr(), ws.data_ptr(), nb, N.stream()),
+                    'lamp_colsum')
+        t_bwd, t_col = time_us_rounds([bwd, colsum], iters=100 if L < 983 else 20)
+        row = dict(labels=L, n_slices=n_slices, bytes_read=4 * n_slices * L * L, attn_bias_bwd_us=round(min(t_bwd), 2),
+                   colsum_us=round(min(t_col), 2), bwd_over_colsum=ratio_summary(t_bwd, t_col))
+        rows.append(row)
+        print(row, flush=True)
+    return rows
+
+
+def learn_step_rows(dev, B=32):
+    """The reuters-shaped training step: a constant bias (the flag off) against the learnable bias, same weights."""
+    from lamp_amd.Models import LAMP
+    V, L, T, d, h = 2000, 90, 302, 512, 4
+    sd = synthetic.make_state_dict(V, L, T + 1, d, 1024, h, 2, 2, seed=0)
+    adj = synthetic.make_adjacency(L, 0.2, 0)
+    seq, pos = synthetic.make_batch(B, V, T, seed=0)
+    seq, pos = seq.to(dev), pos.to(dev)
+    tgt = (torch.rand(B, L, device=dev) < 0.05).float()
+    bias = torch.randn(L, L, generator=torch.Generator().manual_seed(0))
+    steps = []
+    for learn in (False, True):
+        m = LAMP(V, L, T + 1, L, n_layers_enc=2, n_layers_dec=2, n_head=h, n_head2=h, d_word_vec=d, d_model=d, d_inner_hid=1024,
+                 d_k=d // h, d_v=d // h, encoder='graph', decoder='graph', label_adj_matrix=adj.clone(), label_mask='prior',
+                 dec_dropout2=False, label_bias=bias, learn_label_bias=learn)
+        m.load_state_dict(sd)
+        m = m.to(dev).train()
+        opt = torch.optim.Adam(list(m.get_trainable_parameters()), lr=1e-4, fused=True)
+
+        def f(m=m, opt=opt):
+            opt.zero_grad(set_to_none=True)
+            logits = m((seq, pos), None, None, tgt)[0]
+            F.binary_cross_entropy_with_logits(logits, tgt).backward()
+            opt.step()
+        steps.append(f)
+    t_const, t_learn = time_us_rounds(steps, iters=20, warm=5, rounds=10)
+    out = dict(batch=B, constant_bias_step_ms=round(min(t_const) / 1e3, 3), learnable_bias_step_ms=round(min(t_learn) / 1e3, 3),
+               learnable_over_constant=ratio_summary(t_learn, t_const))
+    print(out, flush=True)
+    return out
 
 
 def descriptors(L, graph, density, dev):
@@ -133,11 +223,25 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'label_bias_bench.json'))
     ap.add_argument('--skip-4096', action='store_true')
+    ap.add_argument('--only-learn', action='store_true', help='part 3 alone, merged into the result file if it exists')
     a = ap.parse_args()
     dev = torch.device('cuda:0')
+    learn = dict(attn_bias_bwd=bias_bwd_rows(dev), reuters_batch32_train_step=learn_step_rows(dev))
+    if a.only_learn:
+        res = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        res.update(device=torch.cuda.get_device_name(0), torch=torch.__version__, learn_label_bias=learn)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+        print(json.dumps(res))
+        return
     sizes = [s for s in SIZES if not (a.skip_4096 and s[0] == 4096)]
     res = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, launches=launches(dev, sizes),
-               reuters_batch32=model_rows(dev))
+               reuters_batch32=model_rows(dev), learn_label_bias=learn)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, 'w') as f:
         json.dump(res, f, indent=1)
