@@ -794,6 +794,46 @@ int lamp_threshold_counts(const float* probs, int64_t ld_probs, const float* tar
                           int32_t* sample_tp, int32_t* sample_pred, int32_t* sample_gold, int32_t* sample_mismatch,
                           lamp_stream_t stream);
 
+/* ---- ranking the labels of one sample: top-k predictions, precision / nDCG / recall at k (csrc/rank_at_k.hip) ---------
+ * THE ORDER.  In a row of scores, element a at column i ranks before element b at column j when one of these holds:
+ *   1. a is a number and b is NaN;
+ *   2. both are numbers and a > b as floats;
+ *   3. neither of the above decides (equal numbers, or both NaN) and i < j.
+ * So +0.0 and -0.0 are tied, +inf is the largest value, -inf ranks above every NaN, and a row of equal scores yields columns
+ * 0 .. k-1.  A row's result depends on that row's L scores and on k only: not on n_rows, the row's position, the row stride or
+ * what lies in the padding beyond column L.
+ *
+ * lamp_topk_labels: scores fp32 [n_rows, L], row stride ld >= L (elements), device-resident, not modified; any finite or
+ * non-finite values (logits or probabilities).  idx int32 [n_rows, k] (row stride ld_idx >= k) receives the columns of the k
+ * first-ranked elements in rank order; val (nullable) fp32 [n_rows, k] (row stride ld_val >= k) the selected elements' own
+ * bits (-0.0 stays -0.0, a NaN keeps its payload).  The gaps of a strided output are not written.  1 <= k <= 64, k <= L,
+ * L <= 32768, n_rows < 2^31.  Every score is read once; no workspace, no atomics, nothing synchronised; the kernel chosen is a
+ * function of L alone.
+ *
+ * lamp_rank_at_k: idx as lamp_topk_labels wrote it, targets fp32 [n_rows, L] (row stride ld_targets >= L).  A hit at rank r
+ * (0-based) of sample i is targets[i, idx[i, r]] != 0 -- the gold rule of lamp_threshold_counts -- and gold_i the number of
+ * nonzero targets of row i (an idx outside [0, L) is no hit).  discount / ideal are HOST arrays the caller computed in fp64:
+ * discount[r] = 1 / log2(r + 2) for r < k, ideal[m] = discount[0] + ... + discount[m-1] for m <= k (k + 1 entries); they are
+ * read before the call returns.  The device outputs, each k entries, entry j-1 for rank j = 1 .. k:
+ *   hits_at_rank[j-1] = sum_i hit_{i, j-1}                                                             (int64)
+ *   ndcg_sum[j-1]     = sum_i ( sum_{r<j} hit_{i,r} discount[r] ) / ideal[min(j, gold_i)]              (fp64)
+ *   recall_sum[j-1]   = sum_i ( sum_{r<j} hit_{i,r} ) / gold_i                                         (fp64)
+ *   n_with_gold       = samples with gold_i > 0                                                        (one int64)
+ * A sample without a gold label adds 0 to both fp64 sums (and still counts in n_rows, by which the caller divides), as
+ * sklearn.metrics.ndcg_score(..., ignore_ties=True) has it.  precision@j = (hits_at_rank[0] + ... + hits_at_rank[j-1]) /
+ * (n_rows j).  Per-sample terms are written to the workspace first and added in an order fixed by n_rows: the same bits from
+ * run to run; the integer outputs are also invariant under a permutation of the rows.  The workspace needs no alignment.
+ *
+ * Both validate before any launch, in this order: LAMP_E_DIMS (a non-positive size, ld < L, k > L, ld_idx < k, ld_val < k
+ * with val given), LAMP_E_NULL, LAMP_E_UNSUPPORTED (k > 64, L > 32768, n_rows >= 2^31), LAMP_E_WORKSPACE.
+ * lamp_rank_at_k_workspace_bytes is 0 for a request that is not served. */
+int lamp_topk_labels(const float* scores, int64_t ld, int64_t n_rows, int32_t L, int32_t k, int32_t* idx, int64_t ld_idx,
+                     float* val, int64_t ld_val, lamp_stream_t stream);
+size_t lamp_rank_at_k_workspace_bytes(int64_t n_rows, int32_t k);
+int lamp_rank_at_k(const int32_t* idx, int64_t ld_idx, const float* targets, int64_t ld_targets, int64_t n_rows, int32_t L,
+                   int32_t k, const double* discount, const double* ideal, int64_t* hits_at_rank, double* ndcg_sum,
+                   double* recall_sum, int64_t* n_with_gold, void* workspace, size_t workspace_bytes, lamp_stream_t stream);
+
 /* ---- the training step around the model (train.py:37-48, main.py:99) ------------------------------------------------ */
 
 /* train.py:37-44 forward AND backward in one launch: F.sigmoid(pred), F.binary_cross_entropy_with_logits(.., reduction='mean')

@@ -562,6 +562,27 @@ class LAMP(nn.Module):
             return logits, enc_output, [enc_attns], [slf_attns, encdec_attns]
         return logits, enc_output, None
 
+    def predict_topk(self, src, k, adj=None):
+        """The k most likely labels of every sample: an eval forward under no_grad, the LOGITS ranked on the device in the
+        order include/lamp_hip.h defines (lamp_topk_labels: larger first, the lower column on a tie) -- the sigmoid is monotone
+        but saturates in fp32 and would turn distinct logits into index-ordered ties -- and the sigmoid applied to the (B, k)
+        winners only.  -> (probs float32 (B, k), labels int64 (B, k)), labels being columns of the logit matrix.  Works on the
+        fused and on the module-by-module route; there is no CPU path."""
+        from . import metrics
+        if not src[0].is_cuda:
+            N.require_device(src[0])   # raises: HIP device only
+        was_training = self.training
+        if was_training:
+            self.eval()
+        try:
+            with torch.no_grad(), torch.cuda.device(src[0].device):
+                logits = self.forward(src, adj, None, None)[0]
+                idx, val = metrics.topk_labels(logits, k, values=True)
+                return torch.sigmoid(val), idx.long()
+        finally:
+            if was_training:
+                self.train(True)
+
     # Upper bound on the scratch a forward may claim; larger batches are processed in micro-batches
     # inside lamp_forward.  8 GiB of 288 GB keeps even the 4096-label configuration at >= 64 samples.
     workspace_limit_bytes = 8 << 30

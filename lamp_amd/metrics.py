@@ -13,8 +13,15 @@ keyword.  Scores are probabilities -- [0, 1] is the contract; a column holding a
 other than 0 / 1 is unranked (NaN), as the reference skipped such labels on ValueError.  A label without positives has NaN
 AUC / AUPR / FDR recall, one without negatives NaN AUC only; the aggregates run over the finite entries.
 
+Ranking a sample's labels (csrc/rank_at_k.hip) is opt-in beside it: topk_labels gives the k best columns
+of every row in the order include/lamp_hip.h defines (a number before a NaN, the larger number first, the lower column on a
+tie), rank_at_k and compute_metrics(at_k=...) the precision, nDCG and recall at those ranks from integer hit counts and
+fixed-order fp64 sums (lamp_rank_at_k), a sample without a gold label adding 0 as sklearn's ndcg_score(ignore_ties=True) has it.
+
 There is no CPU path: without a HIP device compute_metrics raises (N.require_device).
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -118,13 +125,90 @@ def aggregate(values):
     return float(np.mean(v)), float(np.median(v)), float(np.var(v))
 
 
+TOPK_MAX_K, TOPK_MAX_L = 64, 32768   # include/lamp_hip.h: lamp_topk_labels
+
+
+def topk_labels(scores, k, values=True):
+    """The k first-ranked columns of every row of an (n, L) device matrix, in the order include/lamp_hip.h defines (a number
+    before a NaN, the larger number first, the lower column on a tie) -> (int32 (n, k) columns, float32 (n, k) selected scores
+    or None) on the device, nothing synchronised.  1 <= k <= min(L, 64), L <= 32768."""
+    N.require_device(scores)
+    s, ld = _matrix(scores)
+    n, L = s.shape
+    k = int(k)
+    idx = torch.empty((n, k), dtype=torch.int32, device=s.device)
+    val = torch.empty((n, k), dtype=torch.float32, device=s.device) if values else None
+    N.check(N.lib().lamp_topk_labels(N.ptr(s), ld, n, L, k, N.ptr(idx), k, N.ptr(val), k, N.stream()), 'lamp_topk_labels')
+    return idx, val
+
+
+def dcg_tables(k):
+    """(discount, ideal) of lamp_rank_at_k in fp64: discount[r] = 1 / log2(r + 2), ideal[m] = the sum of the first m."""
+    d = 1.0 / np.log2(np.arange(k, dtype=np.float64) + 2.0)
+    ideal = np.concatenate(([0.0], np.cumsum(d)))
+    return d, ideal
+
+
+def _rank_at_k_buffer(scores, targets, k):
+    """-> float64 (3 k + 1) device buffer: ndcg_sum, recall_sum, then hits_at_rank and n_with_gold as int64 bit patterns."""
+    N.require_device(scores, targets)
+    t, ldt = _matrix(targets)
+    if tuple(scores.shape) != tuple(t.shape):
+        raise ValueError('scores %s and targets %s differ in shape' % (tuple(scores.shape), tuple(t.shape)))
+    n, L = t.shape
+    idx, _ = topk_labels(scores, k, values=False)
+    lib = N.lib()
+    nbytes = lib.lamp_rank_at_k_workspace_bytes(n, k)
+    if nbytes == 0:
+        raise ValueError('rank at k: unsupported request (n = %d, k = %d)' % (n, k))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+    out = torch.empty(3 * k + 1, dtype=torch.float64, device=t.device)
+    ints = out[2 * k:].view(torch.int64)
+    d, ideal = dcg_tables(k)
+    N.check(lib.lamp_rank_at_k(N.ptr(idx), k, N.ptr(t), ldt, n, L, k, d.ctypes.data_as(C.POINTER(C.c_double)),
+                               ideal.ctypes.data_as(C.POINTER(C.c_double)), N.ptr(ints[:k]), N.ptr(out[:k]), N.ptr(out[k:2 * k]),
+                               N.ptr(ints[k:]), N.ptr(ws), nbytes, N.stream()), 'lamp_rank_at_k')
+    return out
+
+
+def _check_ks(ks, L):
+    ks = tuple(int(k) for k in ks)
+    if not ks or min(ks) < 1 or max(ks) > min(L, TOPK_MAX_K):
+        raise ValueError('rank at k: every k must lie in 1 .. min(L, %d); got %s with L = %d' % (TOPK_MAX_K, ks, L))
+    return ks
+
+
+def rank_at_k_from_sums(buf, n, k, ks):
+    """The figures of rank_at_k from the host copy of _rank_at_k_buffer."""
+    ints = buf[2 * k:].view(np.int64)
+    out = {}
+    for j in ks:
+        out['P@%d' % j] = float(int(ints[:j].sum())) / float(n * j)
+        out['nDCG@%d' % j] = float(buf[j - 1]) / n
+        out['R@%d' % j] = float(buf[k + j - 1]) / n
+    out['n_with_gold'] = int(ints[k])
+    return out
+
+
+def rank_at_k(scores, targets, ks=(1, 3, 5)):
+    """Precision, nDCG and recall at k of (n, L) device matrices, each sample's labels ranked by topk_labels: a dict with
+    'P@k', 'nDCG@k' and 'R@k' for every requested k (means over all n samples; a sample without a gold label adds 0, as
+    sklearn's ndcg_score(ignore_ties=True) has it) and 'n_with_gold'.  A gold label is a nonzero target.  The scores may be
+    logits or probabilities; the figures come back in one copy."""
+    ks = _check_ks(ks, scores.size(1))
+    k = max(ks)
+    buf = _rank_at_k_buffer(scores, targets, k).cpu().numpy()
+    return rank_at_k_from_sums(buf, scores.size(0), k, ks)
+
+
 def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapsed=0.0, all_metrics=True, device=None,
-                    fdr_cutoff=0.5):
+                    fdr_cutoff=0.5, at_k=None):
     """utils/evals.py:316-407 for the binary-relevance decoders: a dict with the reference's keys -- ACC, HA, ebF1, miF1, maF1,
     meanAUC, medianAUC, meanAUPR, medianAUPR, allAUC, allAUPR, meanFDR, medianFDR, loss, time.  allAUC / allAUPR are float64
     arrays of length L (NaN for a label that cannot be ranked); all_metrics=False gives 0 for the ranking entries, as the
     reference does.  (n, L) tensors of probabilities in [0, 1] and 0 / 1 targets, on the CPU (uploaded once, to `device` or the
-    current HIP device) or on the device; the inputs are not modified."""
+    current HIP device) or on the device; the inputs are not modified.  at_k=(1, 3, 5) adds the keys of rank_at_k for those k
+    (P@k, nDCG@k, R@k, n_with_gold); with the default the dict is what it was."""
     if not all_predictions.is_cuda:
         if not torch.cuda.is_available():
             N.require_device(all_predictions)      # raises: HIP device only
@@ -136,6 +220,9 @@ def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapse
         n, L = all_predictions.shape
         counts_d = _counts_buffer(all_predictions, all_targets, br_threshold)
         ranked_d = _ranking_buffer(all_predictions, all_targets, fdr_cutoff) if all_metrics else None
+        if at_k is not None:
+            ks = _check_ks(at_k, L)
+            at_k_d = _rank_at_k_buffer(all_predictions, all_targets, max(ks))
         counts = counts_d.cpu().numpy()
         out = thresholded_from_counts(counts[:3 * L].reshape(3, L), counts[3 * L:].reshape(4, n), L)
         if all_metrics:
@@ -148,6 +235,8 @@ def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapse
         else:
             for k in RANKING_KEYS:
                 out[k] = 0
+        if at_k is not None:
+            out.update(rank_at_k_from_sums(at_k_d.cpu().numpy(), n, max(ks), ks))
     out['loss'] = loss
     out['time'] = elapsed
     return out

@@ -4,6 +4,7 @@ on the MI355X path.
     python -m lamp_amd.run_eval -data data/reuters/train_valid_test.pt -dataset reuters \
            -d_model 512 -d_inner_hid 512 -n_layers_enc 2 -n_head 4 -label_mask prior \
            [-checkpoint results/.../model.chkpt] [-split test] [-batch_size 32] [-streams 2] [-gpus N] [-all_metrics]
+           [-at_k 1,3,5]
 
 -gpus N starts one process per GPU (rendezvous on 127.0.0.1; "nccl" = RCCL for the final gather only); every rank
 evaluates its contiguous share of the batches -- the forward path needs no collective (lamp_amd/sharding.py).
@@ -17,7 +18,8 @@ adjacency from the train split).  Metrics are the thresholded multi-label basics
 (utils/evals.py:316-372: subset accuracy, Hamming accuracy, example-/micro-/macro-F1 at -br_threshold, with the
 reference's conventions for empty samples / labels); with -all_metrics also the ranking metrics the reference computes with
 all_metrics=True (:208-298: mean / median AUC, AUPR and recall at FDR <= 0.5 over the labels, and the per-label arrays), on the
-device (lamp_amd/metrics.py).
+device (lamp_amd/metrics.py); with -at_k 1,3,5 precision, nDCG and recall at those ranks, each sample's labels ranked on
+the device in the order include/lamp_hip.h defines (the figures are printed on stderr and join the JSON result line).
 """
 import argparse
 import json
@@ -82,6 +84,10 @@ def parse(argv=None):
     ap.add_argument('-all_metrics', action='store_true',
                     help='also report meanAUC / medianAUC / meanAUPR / medianAUPR / meanFDR / medianFDR and the per-label allAUC / '
                          'allAUPR (computed on the device; with -gpus N by rank 0 after the combine)')
+    ap.add_argument('-at_k', type=str, default='',
+                    help='comma-separated ranks, e.g. 1,3,5: also report precision (P@k), nDCG@k and recall (R@k) at those k, each '
+                         "sample's labels ranked on the device (lamp_amd/metrics.py: rank_at_k; every k <= min(n_labels, 64)); "
+                         'independent of -all_metrics; with -gpus N by rank 0 after the combine')
     ap.add_argument('-seed', type=int, default=0, help='weight init seed when no checkpoint is given')
     ap.add_argument('-gpus', type=int, default=1, help='processes (one per GPU) the batches are sharded over')
     opt = ap.parse_args(argv)
@@ -97,6 +103,12 @@ def parse(argv=None):
         opt.d_v = opt.d_model // opt.n_head
     if opt.dataset in ('bibtext', 'delicious', 'bookmarks', 'sider'):
         opt.no_enc_pos_embedding = True
+    try:
+        opt.at_k = tuple(int(v) for v in opt.at_k.split(',') if v.strip())
+    except ValueError:
+        ap.error('-at_k takes comma-separated integers, e.g. 1,3,5')
+    if any(k < 1 or k > 64 for k in opt.at_k):
+        ap.error('-at_k: every k must lie in 1 .. 64')
     # config_args.py:90-91: the genomics datasets read DNA through the one-hot / Conv1d encoder
     opt.onehot = opt.dataset in ONEHOT_DATASETS
     if opt.onehot and opt.merge_stages:
@@ -281,7 +293,7 @@ def main(argv=None):
     split = data[opt.split]
     batches = D.EvalBatcher(split['src'], split['tgt'], opt.batch_size)
     torch.cuda.synchronize()
-    on_device = {} if opt.all_metrics and world == 1 else None   # one rank holds the whole split: nothing goes back up
+    on_device = {} if (opt.all_metrics or opt.at_k) and world == 1 else None   # one rank holds the whole split: nothing goes back up
     t0 = time.perf_counter()
     preds, targets, bce_total = test_epoch(model, batches, n_labels, opt.batch_size, device, streams=opt.streams,
                                            prefetch=opt.prefetch, merge_stage=opt.merge_stages,
@@ -300,6 +312,15 @@ def main(argv=None):
              compute_metrics(preds, targets, bce_total, opt.br_threshold, device=device))
         out.update({k: (m[k].tolist() if hasattr(m[k], 'tolist') else m[k]) for k in RANKING_KEYS})
         out['metrics_seconds'] = time.perf_counter() - t1
+    if opt.at_k and rank == 0:
+        from .metrics import rank_at_k
+        t1 = time.perf_counter()
+        at_k = (rank_at_k(on_device['probs'], on_device['targets'], opt.at_k) if on_device else
+                rank_at_k(preds.to(device), targets.to(device), opt.at_k))
+        out.update(at_k)
+        out['at_k_seconds'] = time.perf_counter() - t1
+        print('  '.join('%s %.6f' % (key, at_k[key]) for key in at_k if key != 'n_with_gold') +
+              '  n_with_gold %d' % at_k['n_with_gold'], file=sys.stderr, flush=True)
     if rank == 0:
         print(json.dumps(out), flush=True)
     plane.close()
