@@ -54,20 +54,29 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
             s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
         }
         const float mean = wsum(s) * inv_d;
-        float ss = 0.f;
+        // corrected two-pass, as ln_row_stats (lamp_kernels.h): the centred values' own sum repairs the first mean's rounding
+        float ss = 0.f, cs = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int c = lane + i * 64;
             if (c < nv) {
                 v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
                 ss += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+                cs += (v[i].x + v[i].y) + (v[i].z + v[i].w);
             }
         }
-        const float rstd = 1.0f / sqrtf(wsum(ss) * inv_d + eps);
+        const float corr = wsum(cs) * inv_d, ssum = wsum(ss);
+        // explicit fmas: the same bits in every instantiation (and those the contracted `sum * inv_d + eps` always gave)
+        // Selects, no branch: a row that keeps its first mean subtracts 0 (exact) and keeps its bits.
+        const float var0 = fmaf(ssum, inv_d, eps);
+        const bool fix = corr * corr > LN_MEAN_FIX * var0;   // wave-uniform
+        const float sub = fix ? corr : 0.f;
+        const float rstd = 1.0f / sqrtf(fix ? fmaxf(fmaf(-corr, corr, var0), eps) : var0);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
-            v[i].x *= rstd; v[i].y *= rstd; v[i].z *= rstd; v[i].w *= rstd;  // zhat
+            v[i].x = (v[i].x - sub) * rstd; v[i].y = (v[i].y - sub) * rstd;  // zhat (padding lanes: dy = 0 there)
+            v[i].z = (v[i].z - sub) * rstd; v[i].w = (v[i].w - sub) * rstd;
             ag[i].x += t[i].x * v[i].x; ag[i].y += t[i].y * v[i].y; ag[i].z += t[i].z * v[i].z; ag[i].w += t[i].w * v[i].w;
             ab[i].x += t[i].x; ab[i].y += t[i].y; ab[i].z += t[i].z; ab[i].w += t[i].w;
             t[i].x *= gg[i].x; t[i].y *= gg[i].y; t[i].z *= gg[i].z; t[i].w *= gg[i].w;  // dy * gamma

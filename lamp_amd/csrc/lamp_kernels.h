@@ -344,6 +344,7 @@ __device__ __forceinline__ float wave64_sum(float v) {
 // are real, the rest zeros).  Shared by layernorm_kernel (pointwise.hip) and the fused decoder chain (chain.hip), with
 // floating-point contraction OFF: what is written is what is computed, in every kernel that inlines it -- the two routes
 // give the same bits (hipcc's fma-contraction choices otherwise differ between instantiations of the same source).
+constexpr float LN_MEAN_FIX = 0x1p-44f;   // (2^-22)^2: the squared mean correction, in units of the variance, from which it is taken
 template <int NV>
 __device__ __forceinline__ void ln_row_stats(const float4 (&v)[NV], int lane, int nv, int d, float eps, float& mean,
                                              float& rstd) {
@@ -352,15 +353,27 @@ __device__ __forceinline__ void ln_row_stats(const float4 (&v)[NV], int lane, in
 #pragma unroll
     for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     mean = wave64_sum(s) / float(d);
-    float ss = 0.f;
+    // Corrected two-pass: the first mean carries the roundings of a sum of magnitude d |mean| (rows of -1e4 + randn: an error of
+    // 5e-4 in y, ten times torch's fp32 LayerNorm).  The centred values are small and their sum is accurate, so
+    // mean + sum(a) / d is the mean to an ulp and sum(a^2) / d - (sum(a) / d)^2 the variance about it.  The correction is taken
+    // only where it shows (LN_MEAN_FIX: it would move y by more than 2^-22 |gamma|; the row's own decision, wave-uniform):
+    // rows of ordinary activations, whose first mean is good to 1e-8 of their spread, keep it and with it every bit.
+    float ss = 0.f, cs = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         if (lane + i * 64 < nv) {
             const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, dd = v[i].w - mean;
             ss += (a * a + b * b) + (cc * cc + dd * dd);
+            cs += (a + b) + (cc + dd);
         }
     }
-    rstd = 1.0f / sqrtf(wave64_sum(ss) / float(d) + eps);
+    const float c = wave64_sum(cs) / float(d);
+    float var = wave64_sum(ss) / float(d);
+    if (c * c > LN_MEAN_FIX * (var + eps)) {
+        var = fmaxf(var - c * c, 0.f);   // >= 0 but for rounding (|mean| beyond 1e8)
+        mean += c;
+    }
+    rstd = 1.0f / sqrtf(var + eps);
 }
 __device__ __forceinline__ float4 ln_row_apply(float4 v, float mean, float rstd, float4 gg, float4 bb) {
 #pragma clang fp contract(off)
