@@ -260,8 +260,9 @@ int lamp_linear_prec_fwd(const float* A, int64_t M, int32_t K, int64_t lda,
  * meaningful with one segment), bit for bit what n_seg calls of lamp_linear_fwd give.  W, C: host arrays of n_seg device pointers;
  * bias: such an array with nullable entries, or NULL.
  *   W_pack (nullable; host array of n_seg nullable entries): lamp_pack_weight(W[s], N, K, ldw, format 0).  When every segment has
- *     one, N % 16 == 0, K % 32 == 0 and C / bias / residual can move as 16-byte accesses, launches of fewer than 2048 64 x 64 tiles
- *     load their weight fragments straight from the packs (csrc/gemm.hip, the packed-W tile); otherwise the packs are ignored.
+ *     one, N % 16 == 0, K % 32 == 0 and C / bias / residual can move as 16-byte accesses, the launch loads its weight fragments
+ *     straight from the packs wherever launch_gemm picks a one-wave-row tile (csrc/gemm.hip, the packed-W tiles: by tile counts);
+ *     otherwise the packs are ignored.
  *     Same bits either way.
  *   m_dev (nullable): the live row count in device memory; rows at and past min(*m_dev, M) are neither computed nor written
  *     (M then only sizes the launch). */
@@ -675,7 +676,8 @@ int lamp_forward_opts(const lamp_model* m, const lamp_fwd_options* opts, const i
  * member: a NULL member (or array, or struct) leaves that launch on the row-major weight, as does a shape the pack cannot express
  * (output width not a multiple of 16, d_model / d_inner not a multiple of 32), a LAMP_FWD_MATMUL_* flag, or an output / bias /
  * residual that cannot move as 16-byte accesses.  Like lamp_model.chain_packs they depend on weights only: build them once per
- * weight version; each is as large as its matrix (1 MiB for 512 x 512).  The K / V projection of the encoder rows takes none. */
+ * weight version; each is as large as its matrix (1 MiB for 512 x 512).  The K / V projection of the encoder rows takes its packs
+ * from lamp_kv_gemm_pack below (lamp_forward_packs_kv); these three structs keep the layout lamp_forward_packs was published with. */
 typedef struct lamp_dec_gemm_pack {
     const float* enc_q;  /* dec_layers[i].enc_attn.w_qs */
     const float* slf_q;  /* dec_layers[i].slf_attn.w_qs, w_ks, w_vs: one three-segment launch, packed when all three are given */
@@ -697,6 +699,22 @@ typedef struct lamp_gemm_packs {
 int lamp_forward_packs(const lamp_model* m, const lamp_fwd_options* opts, const lamp_gemm_packs* packs, const int64_t* src_seq,
                        const int64_t* src_pos, int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux,
                        void* workspace, size_t workspace_bytes, lamp_stream_t stream);
+
+/* The packs of the K / V projection of the encoder rows, per decoder layer: dec_layers[i].enc_attn.w_ks / w_vs.  That projection is
+ * one launch of 2 n segments for n decoder layers of one head geometry (or one launch per layer): the largest launch of a forward,
+ * on the tall packed tile of csrc/gemm.hip.  A launch is packed when every segment of its own has a pack; a NULL member (or
+ * array) leaves it on the row-major weights, with the same bits.  They ride in a struct and an entry point of their own, so that
+ * lamp_dec_gemm_pack keeps its size -- a host array of it is walked by the library -- and a library without this entry point is
+ * never handed them. */
+typedef struct lamp_kv_gemm_pack {
+    const float* enc_k;  /* dec_layers[i].enc_attn.w_ks */
+    const float* enc_v;  /* dec_layers[i].enc_attn.w_vs */
+} lamp_kv_gemm_pack;
+
+/* lamp_forward_packs with kv_packs (nullable): host array of n_layers_dec entries. */
+int lamp_forward_packs_kv(const lamp_model* m, const lamp_fwd_options* opts, const lamp_gemm_packs* packs, const lamp_kv_gemm_pack* kv_packs,
+                          const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T, float* logits, float* enc_output,
+                          const lamp_aux* aux, void* workspace, size_t workspace_bytes, lamp_stream_t stream);
 
 /* ---- the one-hot genomics encoder (GraphEncoder(onehot=True), lamp/Encoders.py:46-51,68-73) ----------------------
  * For src_seq / src_pos int64 [B, T] over a vocabulary of n_vocab (9) symbols, with T2 = T / 2:

@@ -245,14 +245,16 @@ class LAMP(nn.Module):
 
     def _gemm_pack_weights(self):
         """The matrices lamp_gemm_packs covers: every encoder layer's pos_ffn (w_1, w_2), every decoder layer's enc_attn.w_qs and
-        slf_attn (w_qs, w_ks, w_vs).  -> (encoder pairs, decoder quads; None where a block does not exist)"""
+        slf_attn (w_qs, w_ks, w_vs); and lamp_kv_gemm_pack: every decoder layer's enc_attn (w_ks, w_vs), the K / V projection of the
+        encoder rows.  -> (encoder pairs, decoder quads, decoder K / V pairs; None where a block does not exist)"""
         enc = [(l.pos_ffn.w_1.weight, l.pos_ffn.w_2.weight) for l in self.encoder.layer_stack]
         dec = []
         for l in self.decoder.layer_stack:
             slf = getattr(l, 'slf_attn', None)
             dec.append((l.enc_attn.w_qs.weight,) + (tuple(getattr(slf, n).weight for n in ('w_qs', 'w_ks', 'w_vs')) if slf is not None
                                                      else (None, None, None)))
-        return enc, dec
+        kv = [(l.enc_attn.w_ks.weight, l.enc_attn.w_vs.weight) for l in self.decoder.layer_stack]
+        return enc, dec, kv
 
     def _native_model(self):
         """Build (and cache, keyed on every weight's data_ptr) the lamp_model struct."""
@@ -276,11 +278,12 @@ class LAMP(nn.Module):
         live = self.enc_self_attn
         # fragment-major copies for the tile GEMM launches (lamp_forward_packs; the one-hot forward has no such entry point)
         gpacks = bool(self.use_gemm_packs and not replica and not onehot and getattr(N.lib(), 'lamp_forward_packs', None))
+        kvpacks = bool(gpacks and self.use_kv_gemm_packs and getattr(N.lib(), 'lamp_forward_packs_kv', None))
         # weights-only tables, likewise; a live layer 0 starts with the attention, not with W1: nothing to fold into
         fold = self.fold_embedding and not replica and len(self.encoder.layer_stack) > 0 and not onehot and not live
         sparse = bool(self.use_sparse_label_attention and self.use_mask_bits and self.decoder.label_rows_sparse and bias is None)
         key = tuple(p.data_ptr() for p in params) + (N.ptr(mask), N.ptr(bits), N.ptr(tiles), self.use_label_tiles,
-                                                      hoist, self.use_mask_bits, packs, fold, sparse, live, bias is not None, gpacks)
+                                                      hoist, self.use_mask_bits, packs, fold, sparse, live, bias is not None, gpacks, kvpacks)
         if hoist:  # the hoisted projection below is stale once either operand changes
             l0 = self.decoder.layer_stack[0].enc_attn
             key += (self.decoder.tgt_word_emb.weight._version, l0.w_qs.weight._version)
@@ -356,7 +359,7 @@ class LAMP(nn.Module):
         if gpacks:
             # the same format-0 copies for the projections and encoder FFN matrices that run as tile-GEMM launches
             # (lamp_gemm_packs): weights only, rebuilt once per weight version like the chain packs; same bits with and without
-            enc_ws, dec_ws = self._gemm_pack_weights()
+            enc_ws, dec_ws, kv_ws = self._gemm_pack_weights()
             tensors = []
 
             def pk(w):
@@ -365,7 +368,10 @@ class LAMP(nn.Module):
                 return N.ptr(t)
             enc_gp = (N.EncGemmPack * max(1, len(enc_ws)))(*[N.EncGemmPack(*[pk(w) for w in ws]) for ws in enc_ws])
             dec_gp = (N.DecGemmPack * max(1, len(dec_ws)))(*[N.DecGemmPack(*[pk(w) for w in ws]) for ws in dec_ws])
-            gemm_keep = (N.GemmPacks(enc_gp, dec_gp), enc_gp, dec_gp, tensors)
+            kv_gp = None   # the K / V projection's packs have an entry point of their own: a library without it is never handed them
+            if kvpacks:
+                kv_gp = (N.KvGemmPack * max(1, len(kv_ws)))(*[N.KvGemmPack(*[pk(w) for w in ws]) for ws in kv_ws])
+            gemm_keep = (N.GemmPacks(enc_gp, dec_gp), enc_gp, dec_gp, tensors, kv_gp)
             torch.cuda.current_stream().synchronize()
         fold_keep = None
         if fold:
@@ -538,6 +544,11 @@ class LAMP(nn.Module):
                                                  T_in, logits.data_ptr(), enc_output.data_ptr(),
                                                  C.byref(aux) if aux is not None else None, ws.data_ptr(), ws.numel(),
                                                  N.stream()), 'lamp_onehot_forward_opts')
+        elif gp is not None and fe is None and built[9][4] is not None:
+            N.check(lib.lamp_forward_packs_kv(C.byref(model), C.byref(opts) if opts is not None else None, C.byref(gp), built[9][4],
+                                              seq.data_ptr(), pos.data_ptr(), B, T, logits.data_ptr(), enc_output.data_ptr(),
+                                              C.byref(aux) if aux is not None else None, ws.data_ptr(), ws.numel(), N.stream()),
+                    'lamp_forward_packs_kv')
         elif gp is not None and fe is None:
             N.check(lib.lamp_forward_packs(C.byref(model), C.byref(opts) if opts is not None else None, C.byref(gp), seq.data_ptr(),
                                            pos.data_ptr(), B, T, logits.data_ptr(), enc_output.data_ptr(),
@@ -594,6 +605,9 @@ class LAMP(nn.Module):
     # (lamp_gemm_packs): the tile GEMM's one-wave-row tile reads its weight fragments straight from them.  Same bits; one extra copy
     # of each packed matrix in device memory.
     use_gemm_packs = True
+    # ... and of the decoder's enc_attn K / V matrices (lamp_kv_gemm_pack): the K / V projection of the encoder rows, the largest
+    # launch of a forward, on the tall packed tile.  Needs use_gemm_packs.  Same bits; 4 MiB more for reuters (2 layers, d 512).
+    use_kv_gemm_packs = True
     # Fold encoder layer 0's first FFN matrix into the embedding tables (weights-only: Emb . W1^T and Pos . W1^T + b1, one
     # GEMM fewer per forward; results move in the last bits, a re-association).  False = the unfolded route.
     fold_embedding = True

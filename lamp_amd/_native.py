@@ -94,6 +94,10 @@ class EncGemmPack(C.Structure):  # include/lamp_hip.h: lamp_enc_gemm_pack
     _fields_ = [('w1', _vp), ('w2', _vp)]
 
 
+class KvGemmPack(C.Structure):  # include/lamp_hip.h: lamp_kv_gemm_pack
+    _fields_ = [('enc_k', _vp), ('enc_v', _vp)]
+
+
 class GemmPacks(C.Structure):  # include/lamp_hip.h: lamp_gemm_packs
     _fields_ = [('enc', C.POINTER(EncGemmPack)), ('dec', C.POINTER(DecGemmPack))]
 
@@ -201,6 +205,8 @@ PROTOTYPES = {
                                     _vp, _sz, _vp]),
     'lamp_forward_packs': (C.c_int, [C.POINTER(Model), C.POINTER(FwdOptions), C.POINTER(GemmPacks), _vp, _vp, _i32, _i32, _vp, _vp,
                                      C.POINTER(Aux), _vp, _sz, _vp]),
+    'lamp_forward_packs_kv': (C.c_int, [C.POINTER(Model), C.POINTER(FwdOptions), C.POINTER(GemmPacks), C.POINTER(KvGemmPack), _vp, _vp, _i32,
+                                        _i32, _vp, _vp, C.POINTER(Aux), _vp, _sz, _vp]),
     'lamp_onehot_forward_opts_workspace_bytes': (_sz, [C.POINTER(Model), C.POINTER(OnehotFrontend), C.POINTER(FwdOptions),
                                                        _i32, _i32, _i32]),
     'lamp_onehot_forward_opts': (C.c_int, [C.POINTER(Model), C.POINTER(OnehotFrontend), C.POINTER(FwdOptions), _vp, _vp, _i32,
@@ -243,7 +249,7 @@ PROTOTYPES = {
 
 # entry points added without an ABI bump (no struct changed): a library of the same ABI version built before them lacks the
 # symbols -- same-box A/B runs against the previous build (LAMP_HIP_LIBRARY) -- and their callers ask with getattr
-LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs', 'lamp_attn_bias_bwd_workspace_bytes', 'lamp_attn_bias_bwd',
+LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs', 'lamp_forward_packs_kv', 'lamp_attn_bias_bwd_workspace_bytes', 'lamp_attn_bias_bwd',
                      'lamp_label_bias_fold', 'lamp_topk_labels', 'lamp_rank_at_k_workspace_bytes', 'lamp_rank_at_k')
 
 _lib = None

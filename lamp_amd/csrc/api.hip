@@ -1018,6 +1018,7 @@ struct Pass {
     int dec_act = LAMP_ATTN_SOFTMAX;                 // LAMP_FWD_DEC_SIGMOID: both attention blocks of every decoder layer
     int prec = LAMP_PREC_FP32;                       // LAMP_FWD_MATMUL_*: every linear() of the pass (FfnParams / MhaCall::prec)
     const lamp_gemm_packs* gp = nullptr;             // lamp_forward_packs: weight packs of the tile GEMM launches
+    const lamp_kv_gemm_pack* kvp = nullptr;          // lamp_forward_packs_kv: ... and of the K / V projection of the encoder rows
     void ffn_packs(FfnParams& f, int layer) const {  // encoder layer's pos_ffn
         if (gp && gp->enc) { f.w1_pack = gp->enc[layer].w1; f.w2_pack = gp->enc[layer].w2; }
     }
@@ -1159,24 +1160,30 @@ static int encode_padded(Pass& p) {
 // K and V projections of the first n decoder layers' enc-attention from the same encoder output: ONE launch when the
 // 2n weight matrices fit the GEMM's segment list (n <= 2) -- 4 x more tiles per launch than layer by layer.
 static int project_kv_layers(const float* x, int64_t Me, int d, int dk, int dv, const lamp_dec_layer* layers, int n,
-                             float* const* K, float* const* V, int prec, hipStream_t s, const int* m_dev, const float* A_dense) {
+                             float* const* K, float* const* V, int prec, hipStream_t s, const int* m_dev, const float* A_dense,
+                             const lamp_kv_gemm_pack* packs = nullptr) {
     const int h = layers[0].enc_attn.n_head;
     bool uniform = 2 * n <= GEMM_MAX_SEG && h * dk == h * dv;
     for (int i = 1; i < n && uniform; ++i) uniform = layers[i].enc_attn.n_head == h;
     if (uniform) {
         const float* W[GEMM_MAX_SEG];
         float* C[GEMM_MAX_SEG];
+        const float* Wp[GEMM_MAX_SEG];   // lamp_kv_gemm_pack: packs of {w_ks, w_vs} per layer (a missing one leaves the launch on the row-major weights)
         for (int i = 0; i < n; ++i) {
             if (!layers[i].enc_attn.w_ks || !layers[i].enc_attn.w_vs) return LAMP_E_NULL;
             W[2 * i] = layers[i].enc_attn.w_ks;
             W[2 * i + 1] = layers[i].enc_attn.w_vs;
             C[2 * i] = K[i];
             C[2 * i + 1] = V[i];
+            Wp[2 * i] = packs ? packs[i].enc_k : nullptr;
+            Wp[2 * i + 1] = packs ? packs[i].enc_v : nullptr;
         }
-        return linear(x, Me, d, d, W, 2 * n, h * dk, d, nullptr, nullptr, 0, 0, C, h * dk, prec, s, m_dev, A_dense);
+        return linear(x, Me, d, d, W, 2 * n, h * dk, d, nullptr, nullptr, 0, 0, C, h * dk, prec, s, m_dev, A_dense, nullptr, Wp);
     }
-    for (int i = 0; i < n; ++i)
-        LAMP_CK(project_qkv(layers[i].enc_attn, d, dk, dv, nullptr, 0, nullptr, x, x, Me, K[i], V[i], prec, s, m_dev, A_dense));
+    for (int i = 0; i < n; ++i) {
+        const float* Wp[3] = {nullptr, packs ? packs[i].enc_k : nullptr, packs ? packs[i].enc_v : nullptr};
+        LAMP_CK(project_qkv(layers[i].enc_attn, d, dk, dv, nullptr, 0, nullptr, x, x, Me, K[i], V[i], prec, s, m_dev, A_dense, Wp));
+    }
     return 0;
 }
 
@@ -1219,9 +1226,10 @@ static int decoder_layer(Pass& p, int i) {
     enc.xq_shared = i == 0; enc.q_ready = i == 0 ? m->dec0_query : nullptr; enc.kv_ready = g.n_ahead > 0;
     enc.keys = &p.sp; enc.keys_packed = p.packed; enc.xkv_dense = p.x;
     enc.act = p.dec_act; enc.prec = p.prec;
-    // packs: the query projections of both blocks and the label self-attention's K / V; the K / V projection of the encoder rows has none
+    // packs: the projections of both blocks (the K / V projection of the encoder rows usually ran ahead: project_kv_layers)
     const lamp_dec_gemm_pack* dp = p.gp && p.gp->dec ? p.gp->dec + i : nullptr;
-    const float* enc_pk[3] = {dp ? dp->enc_q : nullptr, nullptr, nullptr};
+    const lamp_kv_gemm_pack* kp = p.kvp ? p.kvp + i : nullptr;
+    const float* enc_pk[3] = {dp ? dp->enc_q : nullptr, kp ? kp->enc_k : nullptr, kp ? kp->enc_v : nullptr};
     const float* slf_pk[3] = {dp ? dp->slf_q : nullptr, dp ? dp->slf_k : nullptr, dp ? dp->slf_v : nullptr};
     enc.w_packs = enc_pk;
     LAMP_CK(mha_attend(enc, sc, p.s));
@@ -1302,7 +1310,7 @@ static int check_forward(const lamp_model* m, const lamp_onehot_frontend* fe, co
 static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const FwdDims& g, const int64_t* src_seq,
                    const int64_t* src_pos, int32_t B, int32_t T_in, float* logits, float* enc_output, const lamp_aux* aux,
                    void* workspace, size_t workspace_bytes, hipStream_t s, const lamp_fwd_options* o = nullptr,
-                   const lamp_gemm_packs* gp = nullptr) {
+                   const lamp_gemm_packs* gp = nullptr, const lamp_kv_gemm_pack* kvp = nullptr) {
     const Carver size = fwd_size(g);
     if (workspace_bytes < size.bound(1)) return LAMP_E_WORKSPACE;
     const int64_t mb = std::min<int64_t>(B, (workspace_bytes - size.fixed) / size.per);
@@ -1353,10 +1361,12 @@ static int forward(const lamp_model* m, const lamp_onehot_frontend* fe, const Fw
         // takes the split kernel (gemm_split.hip); the chain launch, attention, conv2 and the read-out are not linear() calls
         p.prec = fwd_matmul_prec(o);
         p.gp = gp;
+        p.kvp = kvp;
         LAMP_CK(!packed ? encode_padded(p) : g.live ? encode_packed_live(p) : encode_packed(p));
         if (g.n_ahead)
             LAMP_CK(project_kv_layers(p.xk, int64_t(nb) * g.T, g.d, g.dk, g.dv, m->dec_layers, g.n_ahead, w.K_ahead,
-                                      w.V_ahead, p.prec, s, packed ? p.sp.rows : nullptr, packed ? p.x : nullptr));
+                                      w.V_ahead, p.prec, s, packed ? p.sp.rows : nullptr, packed ? p.x : nullptr,
+                                      kvp));
         for (int i = 0; i < m->n_layers_dec; ++i) LAMP_CK(decoder_layer(p, i));
     }
     return 0;
@@ -1370,7 +1380,8 @@ size_t lamp_forward_workspace_bytes(const lamp_model* m, int32_t micro_batch, in
 
 static int forward_tokens(const lamp_model* m, const lamp_fwd_options* o, const int64_t* src_seq, const int64_t* src_pos,
                           int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux, void* workspace,
-                          size_t workspace_bytes, lamp_stream_t stream, const lamp_gemm_packs* gp = nullptr) {
+                          size_t workspace_bytes, lamp_stream_t stream, const lamp_gemm_packs* gp = nullptr,
+                          const lamp_kv_gemm_pack* kvp = nullptr) {
     FwdDims g;
     LAMP_CK(check_forward(m, nullptr, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, &g, o));
     // lamp_forward_workspace_bytes(m, 1, T, want_attn) -- the K/V-ahead buffers counted -- is the least a call accepts, not the
@@ -1382,7 +1393,7 @@ static int forward_tokens(const lamp_model* m, const lamp_fwd_options* o, const 
         2 * m->n_layers_dec <= GEMM_MAX_SEG && m->n_layers_dec > 1 && workspace_bytes >= fwd_size(g).bound(size_t(B));
     if (!kv_ahead) g.n_ahead = 0;
     return forward(m, nullptr, g, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes,
-                   hipStream_t(stream), o, gp);
+                   hipStream_t(stream), o, gp, kvp);
 }
 
 int lamp_forward(const lamp_model* m, const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T,
@@ -1408,6 +1419,12 @@ int lamp_forward_packs(const lamp_model* m, const lamp_fwd_options* opts, const 
                        const int64_t* src_pos, int32_t B, int32_t T, float* logits, float* enc_output, const lamp_aux* aux,
                        void* workspace, size_t workspace_bytes, lamp_stream_t stream) {
     return forward_tokens(m, opts, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, stream, packs);
+}
+
+int lamp_forward_packs_kv(const lamp_model* m, const lamp_fwd_options* opts, const lamp_gemm_packs* packs, const lamp_kv_gemm_pack* kv_packs,
+                          const int64_t* src_seq, const int64_t* src_pos, int32_t B, int32_t T, float* logits, float* enc_output,
+                          const lamp_aux* aux, void* workspace, size_t workspace_bytes, lamp_stream_t stream) {
+    return forward_tokens(m, opts, src_seq, src_pos, B, T, logits, enc_output, aux, workspace, workspace_bytes, stream, packs, kv_packs);
 }
 
 // ------------------------------------------------------------------ one-hot genomics encoder (conv.hip)

@@ -55,8 +55,15 @@ __device__ __forceinline__ int div_1_to_8(int n, int d) {
 // workgroups per CU: two rounds at five to eight per CU, three at four -- and of the two-round residencies FIVE measured
 // fastest (GemmTile::LDS_LAUNCH_BYTES holds the launch there).  So five is both the bound asked of the compiler (<= 96 registers)
 // and what runs.
+// The tall packed tiles (one wave row of 64 or 128 rows: 4 or 8 blocks of 16x16 per wave, every W fragment in registers feeds that
+// many MFMAs): 64x64x32 fits the same bound (94-96 registers, no scratch); 128x64x32 holds 32 accumulators and twice the staging
+// registers and spills under it (88 bytes of scratch per lane) -- it is asked for LAMP_PACKED_128_WAVES waves per SIMD instead: at
+// four, 128 registers and no scratch in the tuning build, the only one that carries it.
+#ifndef LAMP_PACKED_128_WAVES
+#define LAMP_PACKED_128_WAVES 4
+#endif
 constexpr int gemm_min_waves(int bm, int bn, int bk, int mf, bool wpack = false) {
-    return (wpack || (mf == 16 && bm == 64 && bn == 64 && bk == 16)) ? 5 : 1;
+    return (wpack && bm == 128) ? LAMP_PACKED_128_WAVES : (wpack || (mf == 16 && bm == 64 && bn == 64 && bk == 16)) ? 5 : 1;
 }
 
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MF = 32, bool WPACK = false>
@@ -85,7 +92,10 @@ struct GemmTile {
     // Measured on the decoder Q/K/V launch (2160 tiles): 37.6 us at five per CU against 40.6 / 40.3 / 40.6 at seven / seven (by
     // LDS) / six and 38.6 at four; the other launches (720 and 2416 tiles) do not care, 16.5-16.6 and 41.5-41.9 us throughout
     // (profiles/gemm_packed_w_ab.txt).
-    static constexpr size_t LDS_LAUNCH_BYTES = WPACK ? size_t(2) * (BM + BN) * LDS_STRIDE * sizeof(float) : LDS_BYTES;
+    // The tall packed tiles ask for their carve alone: 20 KiB for 64x64x32 -- registers then hold five workgroups per CU, and five
+    // measured fastest (encoder FFN 43.5 / 42.8 us against 46-47 at four, 44 at three or two; K / V projection 146.7 at five and four,
+    // 152.6 at three) -- and 40 KiB for 128x64x32, four per CU by LDS and by registers (three or fewer: 3-4 % slower).
+    static constexpr size_t LDS_LAUNCH_BYTES = (WPACK && BM == 32) ? size_t(2) * (BM + BN) * LDS_STRIDE * sizeof(float) : LDS_BYTES;
     // Waves per SIMD the register allocator must leave room for.  The 64x64x16 tile serves launches of ~1200 tiles
     // (encoder FFN at batch 32: 1208): five workgroups per CU hold them all at once, four leave a second, mostly empty
     // round (44 -> 51 us when the 16-byte epilogue operands pushed the kernel from 92 to 100 registers).
@@ -622,12 +632,18 @@ static int launch_cfg(const GemmParams& p, hipStream_t s) {
     return launch_cfg2<BM, BN, BK, WAVES_M, WAVES_N, false, MF, false>(p, s);
 }
 
-// The packed-W instantiations: the 32x64x32 tile (1x4 waves) with the 16-byte epilogue, whole k-tiles; with and without the
-// gathered residual.  Everything else a launch may ask for stays on the LDS-staged kernels (gemm_packed_ok).
+// The packed-W instantiations: the 32x64x32 and 64x64x32 tiles (1x4 waves) with the 16-byte epilogue, whole k-tiles; with and
+// without the gathered residual.  Everything else a launch may ask for stays on the LDS-staged kernels (gemm_packed_ok).
+template <int BM = 32>
 static int launch_packed(const GemmParams& p, hipStream_t s) {
-    if (p.rg_tok) return launch_cfg2<32, 64, 32, 1, 4, false, 16, true, true, true>(p, s);
-    return launch_cfg2<32, 64, 32, 1, 4, false, 16, true, false, true>(p, s);
+    if (p.rg_tok) return launch_cfg2<BM, 64, 32, 1, 4, false, 16, true, true, true>(p, s);
+    return launch_cfg2<BM, 64, 32, 1, 4, false, 16, true, false, true>(p, s);
 }
+
+#ifdef LAMP_TUNING
+// 128x64x32, ungathered only; tuning build only (see launch_gemm)
+static int launch_packed_128(const GemmParams& p, hipStream_t s) { return launch_cfg2<128, 64, 32, 1, 4, false, 16, true, false, true>(p, s); }
+#endif
 
 // What the pack can express: every segment has one (format 0: N a multiple of 16, K of 32), in-pack byte offsets fit 31 bits,
 // and the launch takes the 16-byte epilogue.  Anything else takes the staged kernel, silently, with the same bits.
@@ -697,7 +713,7 @@ int launch_gemm(const GemmParams& p_in, hipStream_t s) {
         case 6: return launch_cfg<64, 64, 16, 2, 2>(p, s);
         case 7: return launch_cfg<128, 64, 16, 2, 2>(p, s);
         case 8: return launch_cfg<256, 128, 16, 4, 2>(p, s);
-        case 9: return gemm_packed_ok(p) ? launch_packed(p, s) : launch_cfg<32, 64, 32, 1, 4, 16>(p, s);   // waves 32x16 (2 blocks of 16x16)
+        case 9: return gemm_packed_ok(p) ? launch_packed<32>(p, s) : launch_cfg<32, 64, 32, 1, 4, 16>(p, s);   // waves 32x16 (2 blocks of 16x16)
         case 10: return launch_cfg<64, 32, 32, 4, 1, 16>(p, s);  // waves 16x32
         case 11: return launch_cfg<64, 64, 16, 2, 2, 16>(p, s);
         case 12: return launch_cfg<64, 64, 32, 2, 2, 16>(p, s);  // waves 32x32 as 2x2 blocks of 16x16
@@ -707,6 +723,9 @@ int launch_gemm(const GemmParams& p_in, hipStream_t s) {
         case 16: return launch_cfg<128, 64, 32, 2, 2, 16>(p, s);
         case 17: return launch_cfg<64, 128, 32, 2, 2, 16>(p, s);
         case 18: return launch_cfg<128, 64, 16, 2, 2, 16>(p, s);
+        // the tall packed tiles; a launch the pack cannot express takes the heuristic's staged kernel (as it would unforced)
+        case 19: if (gemm_packed_ok(p)) return launch_packed<64>(p, s); break;    // waves 64x16 (4 blocks of 16x16)
+        case 20: if (gemm_packed_ok(p)) return p.rg_tok ? launch_packed<64>(p, s) : launch_packed_128(p, s); break;   // waves 128x16 (8 blocks)
         default: break;
     }
 #endif
@@ -722,17 +741,45 @@ int launch_gemm(const GemmParams& p_in, hipStream_t s) {
     // also ahead of the best 32x32x2 tile (128x128x32: 128-139).  The 32x32x2 tiles exist in the tuning build only.
     auto tiles = [&](int bm, int bn) { return ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * p.nseg; };
     const int64_t t64 = tiles(64, 64);
+    const bool packed = gemm_packed_ok(p);
+    // The tall packed tile, 64x64x32 with one wave row: a launch with packs and at least 2048 tiles that fill whole rounds of the
+    // residency.  Against the 32-row tile it moves a third less operand data from L2 into the CUs -- tiles x (BM + BN) x K x 4 bytes
+    // -- and every W fragment held in registers feeds four MFMAs instead of two; what it costs is grain.  It runs five workgroups
+    // per CU, 1280 at once, and is taken when the launch fills at least four fifths of its rounds.  Measured
+    // (profiles/gemm_packed_tall_ab.txt; tiles, share of their rounds filled): the reuters K / V projection (4832, 0.94) 156.9 ->
+    // 148.0 us and -6 ... -8 us in the forward's kernel trace; one layer's K / V (2416, 0.94) and delicious' encoder W1 (3200, 0.83)
+    // -3 and -4 %.  Not moved:
+    //  - 1200-2047 tiles (encoder FFN at batch 32: 1208).  Launch by launch they gain 1.5 % (K = 512) to 9 % (5088x1024x512), but
+    //    the FFN pair's line of the forward's kernel trace stays inside its noise (84.4 us against 83.4-85.1); 1600 tiles at
+    //    K = 2048 (0.63 of two rounds) lose 3.5 %, 1920 (0.75) tie.  LAMP_PACKED_TALL_MIN_TILES=1200 moves them (the A/B's third arm).
+    //  - the gathered residual (encoder layer 0's W2, 1208 tiles): 47.4-47.5 us in the trace against 46.5-47.6.
+    //  - 4096 or more 128x64 tiles (delicious / synthetic4096 FFN and Q/K/V): the 64-row tile is -2.2 ... +0.9 % around the staged
+    //    128x64x16 there, shape by shape.  128x64x32 with one wave row is 1-2.4 % ahead on all five of those shapes (and loses on
+    //    the reuters K / V projection, 154 us), but only at four waves per SIMD, where the product build spills 20 bytes per
+    //    lane; at three it is 3-4 % slower.
+    // The gathered 64-row instantiation and 128x64x32 are forced tiles of the tuning build only (19, 20).
+    // LAMP_PACKED_TALL_TILE=0 compiles the rule out: the A/B's other arm.
+#ifndef LAMP_PACKED_TALL_TILE
+#define LAMP_PACKED_TALL_TILE 1
+#endif
+#ifndef LAMP_PACKED_TALL_MIN_TILES
+#define LAMP_PACKED_TALL_MIN_TILES 2048
+#endif
+    if (LAMP_PACKED_TALL_TILE && packed && !p.rg_tok && t64 >= LAMP_PACKED_TALL_MIN_TILES && tiles(128, 64) < 4096) {
+        const int64_t rounds = (t64 + 1279) / 1280;
+        if (5 * t64 >= 4 * rounds * 1280) return launch_cfg2<64, 64, 32, 1, 4, false, 16, true, false, true>(p, s);
+    }
     if (tiles(128, 64) >= 2048 && p.K >= 512) return launch_cfg<128, 64, 16, 2, 2, 16>(p, s);  // short K: fewer, deeper steps
     if (t64 >= 2048) return launch_cfg<64, 64, 32, 2, 2, 16>(p, s);
-    // Weight packs (GemmParams::Wp): the 32x64x32 tile reads its W fragments straight from them.  The 2x2-wave tiles above gain
-    // nothing from packs (two waves would fetch every fragment).  LAMP_PACKED_FFN_TILE: launches of 1200-2047 64x64 tiles -- the
-    // encoder FFN at batch 32 -- move from 64x64x16 to the packed 32x64x32 tile as well (profiles/gemm_packed_w_ab.txt).
+    // Weight packs (GemmParams::Wp): the 32x64x32 tile reads its W fragments straight from them, like the tall tiles above.  The
+    // 2x2-wave tiles gain nothing from packs (two waves would fetch every fragment).  LAMP_PACKED_FFN_TILE: launches of 1200-2047
+    // 64x64 tiles -- the encoder FFN at batch 32 -- move from 64x64x16 to the packed 32x64x32 tile as well
+    // (profiles/gemm_packed_w_ab.txt).
 #ifndef LAMP_PACKED_FFN_TILE
 #define LAMP_PACKED_FFN_TILE 1
 #endif
-    const bool packed = gemm_packed_ok(p);
     if (t64 >= 1200 && !(LAMP_PACKED_FFN_TILE && packed)) return launch_cfg<64, 64, 16, 2, 2, 16>(p, s);
-    if (packed) return launch_packed(p, s);
+    if (packed) return launch_packed<32>(p, s);
     return launch_cfg<32, 64, 32, 1, 4, 16>(p, s);  // 4 waves of 32x16 (2 blocks each)
 }
 

@@ -20,6 +20,7 @@ TILES = {0: 'heuristic', 1: '128x128x32', 2: '64x64x32', 3: '128x64x32', 4: '64x
          6: '64x64x16', 7: '128x64x16', 8: '256x128x16(8w)', 9: 'm16:32x64x32',
          10: 'm16:64x32x32', 11: 'm16:64x64x16', 12: 'm16:64x64x32', 13: 'm16:32x128x32',
          14: 'm16:128x128x32', 15: 'm16:128x128x16', 16: 'm16:128x64x32', 17: 'm16:64x128x32', 18: 'm16:128x64x16'}
+# 19 / 20: the tall packed tiles (64x64x32, 128x64x32; one wave row) -- they need packs: `gemm_packed` below
 
 def time_fn(fn, iters=30, warm=5):
     for _ in range(warm):
@@ -139,8 +140,12 @@ def lib_ab(rounds=9):
 def gemm_packed(rounds=9):
     """Packed-W tile (csrc/gemm.hip, GemmParams::Wp: W fragments straight from a lamp_pack_weight format-0 copy) against the
     LDS-staged kernels on the launches of the reuters forward at batch 32, round-robin medians in one process.  Columns: the
-    heuristic's staged choice, the forced staged 32x64x32 and 64x64x16 tiles, the packed 32x64x32 tile, and what the heuristic
-    picks when it is handed the packs; every packed result is compared bit for bit with the staged one first."""
+    heuristic's staged choice, the forced staged 32x64x32 and 64x64x16 tiles, the packed 32x64x32 tile, the tall packed tiles
+    (64x64x32 and 128x64x32, one wave row each), and what the heuristic picks when it is handed the packs; every packed result is
+    compared bit for bit with the staged one first.  Below the reuters rows: the launches of the other workloads with at least
+    1200 64x64 tiles, which the tall-tile rule of launch_gemm can reach once they have packs.  (The gathered-residual encoder
+    launch has no entry point of its own: its instantiation is its own line of the forward's kernel trace.)
+    argv[2] (optional): comma-separated substrings, only rows whose name holds one of them."""
     import statistics
     lib = N.lib()
     force = lib.lamp_debug_force_gemm_tile
@@ -150,10 +155,19 @@ def gemm_packed(rounds=9):
     # name, M, N, K, segments, relu, residual
     shapes = [('dec 2880x512x512', 2880, 512, 512, 1, 0, 0), ('decQKV 2880x(3x512)x512', 2880, 512, 512, 3, 0, 0),
               ('encFFN1 9664x512x512 +b relu', 9664, 512, 512, 1, 1, 0), ('encFFN2 9664x512x512 +b +R', 9664, 512, 512, 1, 0, 1),
-              ('encKV 9664x(4x512)x512', 9664, 512, 512, 4, 0, 0)]
+              ('encKV 9664x(4x512)x512', 9664, 512, 512, 4, 0, 0),
+              ('encKV1 9664x(2x512)x512', 9664, 512, 512, 2, 0, 0),                       # the layer-by-layer K / V route
+              ('bib decQKV 5088x(3x512)x512', 5088, 512, 512, 3, 0, 0), ('ffn1 5088x1024x512 +b relu', 5088, 1024, 512, 1, 1, 0),
+              ('d256 9664x512x256 +b relu', 9664, 512, 256, 1, 1, 0),
+              ('delic enc 6400x2048x1024 +b relu', 6400, 2048, 1024, 1, 1, 0), ('delic enc 6400x1024x2048 +b +R', 6400, 1024, 2048, 1, 0, 1),
+              ('delic ffn1 31456x2048x1024 +b relu', 31456, 2048, 1024, 1, 1, 0), ('delic ffn2 31456x1024x2048 +b +R', 31456, 1024, 2048, 1, 0, 1),
+              ('delic qkv 31456x(3x1024)x1024', 31456, 1024, 1024, 3, 0, 0),
+              ('syn ffn1 65536x2048x1024 +b relu', 65536, 2048, 1024, 1, 1, 0), ('syn ffn2 65536x1024x2048 +b +R', 65536, 1024, 2048, 1, 0, 1)]
+    if len(sys.argv) > 2:
+        shapes = [sh for sh in shapes if any(k in sh[0] for k in sys.argv[2].split(','))]
     cols = [('staged heur', 0, False), ('staged 32x64x32', 9, False), ('staged 64x64x16', 11, False), ('packed 32x64x32', 9, True),
-            ('packed heur', 0, True)]
-    print('%-30s' % 'shape (median us)' + ''.join('%18s' % c[0] for c in cols))
+            ('packed 64x64x32', 19, True), ('packed 128x64x32', 20, True), ('packed heur', 0, True)]
+    print('%-36s' % 'shape (median us)' + ''.join('%18s' % c[0] for c in cols))
     for name, M, Nn, K, nseg, relu, res in shapes:
         x = torch.randn(M, K, device=dev)
         ws = [torch.randn(Nn, K, device=dev) / K ** 0.5 for _ in range(nseg)]
@@ -178,9 +192,49 @@ def gemm_packed(rounds=9):
                 def fn():
                     N.check(lib.lamp_linear_packed_fwd(x.data_ptr(), M, K, K, aw, ap if pk else None, nseg, Nn, K, ab, N.ptr(r), Nn, relu,
                                                        ac, Nn, None, N.stream()), 'linear_packed')
-                samples[i].append(time_fn(fn, iters=20, warm=2))
+                samples[i].append(time_fn(fn, iters=5 if M * Nn * nseg * K > 2e10 else 20, warm=2))
         force(0)
-        print('%-30s' % name + ''.join('%18.1f' % statistics.median(v) for v in samples))
+        print('%-36s' % name + ''.join('%18.1f' % statistics.median(v) for v in samples), flush=True)
+
+
+def gemm_packed_residency(rounds=7):
+    """Workgroups per CU of the tall packed tiles (forced tiles 19 / 20), limited by extra LDS asked for at launch
+    (lamp_debug_set_gemm_extra_lds: carve + extra), on the 9664-row launches of the reuters forward; round-robin medians."""
+    import statistics
+    lib = N.lib()
+    force, hook = lib.lamp_debug_force_gemm_tile, lib.lamp_debug_set_gemm_extra_lds
+    for f in (force, hook):
+        f.argtypes, f.restype = [ctypes.c_int], None
+    dev = torch.device('cuda:0')
+    shapes = [('encFFN1 9664x512x512 +b relu', 9664, 512, 512, 1, 1, 0), ('encFFN2 9664x512x512 +b +R', 9664, 512, 512, 1, 0, 1),
+              ('encKV 9664x(4x512)x512', 9664, 512, 512, 4, 0, 0)]
+    extras = (0, 13, 20, 33, 40, 60)   # KiB on top of the carve
+    for tile, carve, regs in ((19, 20, 5), (20, 40, 4)):
+        print('tile %d: carve %d KiB, %d workgroups per CU by registers; by LDS (160 KiB): ' % (tile, carve, regs) +
+              ', '.join('+%dK -> %d' % (e, min(regs, 160 // (carve + e))) for e in extras))
+        print('%-36s' % 'shape (median us)' + ''.join('%12s' % ('+%dK' % e) for e in extras))
+        for name, M, Nn, K, nseg, relu, res in shapes:
+            x = torch.randn(M, K, device=dev)
+            ws = [torch.randn(Nn, K, device=dev) / K ** 0.5 for _ in range(nseg)]
+            packs = [N.weight_pack(w, 0) for w in ws]
+            bs = [torch.randn(Nn, device=dev) for _ in range(nseg)] if (relu or res) else None
+            r = torch.randn(M, Nn, device=dev) if res else None
+            keep = [torch.empty(M, Nn, device=dev) for _ in range(nseg)]
+            arr = lambda ts: (ctypes.c_void_p * nseg)(*[N.ptr(t) for t in ts])
+            aw, ap, ab, ac = arr(ws), arr(packs), arr(bs) if bs else None, arr(keep)
+
+            def fn():
+                N.check(lib.lamp_linear_packed_fwd(x.data_ptr(), M, K, K, aw, ap, nseg, Nn, K, ab, N.ptr(r), Nn, relu, ac, Nn, None,
+                                                   N.stream()), 'linear_packed')
+            force(tile)
+            samples = {e: [] for e in extras}
+            for _ in range(rounds):
+                for e in extras:
+                    hook(e * 1024)
+                    samples[e].append(time_fn(fn, iters=20, warm=2))
+            hook(0)
+            force(0)
+            print('%-36s' % name + ''.join('%12.1f' % statistics.median(samples[e]) for e in extras), flush=True)
 
 
 WALK_SHAPES = [('delic ffn1 31456x2048x1024', 31456, 2048, 1024, 1, 1, 0), ('delic ffn2 31456x1024x2048', 31456, 1024, 2048, 1, 0, 1),
@@ -921,4 +975,5 @@ def gemm_clock():
 if __name__ == '__main__':
     which = sys.argv[1] if len(sys.argv) > 1 else 'gemm'
     {'gemm': gemm, 'gemm_ab': gemm_ab, 'lib_ab': lib_ab, 'walk': walk, 'walk_pmc': walk_pmc, 'gemm_gen': gemm_gen, 'attn': attn, 'steady': steady, 'sparse': sparse, 'sparse_rows': sparse_rows,
-     'gemm_trace': gemm_trace, 'gemm_clock': gemm_clock, 'attn_lib_ab': attn_lib_ab, 'attn_tile': attn_tile, 'chain': chain, 'ln': ln, 'attn_one': attn_one, 'attn_maps': attn_maps, 'attn_trace': attn_trace, 'residency': residency, 'slab': slab, 'gemm_packed': gemm_packed}[which]()
+     'gemm_trace': gemm_trace, 'gemm_clock': gemm_clock, 'attn_lib_ab': attn_lib_ab, 'attn_tile': attn_tile, 'chain': chain, 'ln': ln, 'attn_one': attn_one, 'attn_maps': attn_maps, 'attn_trace': attn_trace, 'residency': residency, 'slab': slab, 'gemm_packed': gemm_packed,
+     'gemm_packed_residency': gemm_packed_residency}[which]()
