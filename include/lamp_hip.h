@@ -812,6 +812,48 @@ int lamp_threshold_counts(const float* probs, int64_t ld_probs, const float* tar
                           int32_t* sample_tp, int32_t* sample_pred, int32_t* sample_gold, int32_t* sample_mismatch,
                           lamp_stream_t stream);
 
+/* ---- decision thresholds fitted per label (csrc/thresholds.hip) -------------------------------------------------------
+ * lamp_tune_thresholds chooses, per label column, the threshold that is best under `criterion` on the given rows -- what
+ * the reference's Find_Optimal_Cutoff (utils/evals.py:301-313, its use commented out at :335-336) set out to do.  Same inputs
+ * and the same sort as lamp_ranking_metrics.  With the column sorted by score descending, equal scores collapsed into groups
+ * k = 1..G (-0.0 counts as +0.0), tp_k / fp_k the cumulative positives / negatives through group k, P = tp_G, N = fp_G and
+ * cnt_k = tp_k + fp_k, the candidates are c = 0..G:
+ *   c = 0   predicts nothing: threshold +inf, tp_0 = fp_0 = cnt_0 = 0;
+ *   c = k   threshold = the score of group k, the very bits; by the rule of lamp_threshold_counts (score >= threshold) it
+ *           predicts groups 1..k: tp_k true and fp_k false positives.
+ * The criteria are decided by exact integer comparison; no floating point takes part in the choice:
+ *   LAMP_TUNE_F1       maximise F1 = 2 tp / (2 tp + fp + fn) = 2 tp_c / (cnt_c + P): a beats b iff
+ *                      tp_a (cnt_b + P) > tp_b (cnt_a + P)   (unsigned 64-bit; n_rows < 2^31)
+ *   LAMP_TUNE_YOUDEN   maximise tp_c N - fp_c P   (signed 64-bit): tpr - fpr scaled by P N
+ *   LAMP_TUNE_BALANCE  minimise |tp_c N + fp_c P - P N|: |tpr - (1 - fpr)| scaled by P N, the quantity Find_Optimal_Cutoff
+ *                      minimises.  The reference's own answer can differ: sklearn's roc_curve drops collinear points by default
+ *                      (drop_intermediate=True), so some candidates never reach its argsort, and that argsort leaves ties open.
+ * A tie goes to the smallest c: the highest threshold, the fewest predictions.  Hence with P == 0 all three criteria choose
+ * c = 0 (every candidate has tp = 0), and LAMP_TUNE_YOUDEN / LAMP_TUNE_BALANCE with N == 0 tie everywhere and give c = 0.
+ * Outputs, [L] each:  threshold (+inf for c = 0);  tp, fp = tp_c, fp_c of the chosen candidate;  n_pos, n_neg = P, N;
+ * tuned = 1 (nullable).  A column that lamp_ranking_metrics cannot rank (a NaN score, a score outside [0, 1], a target other
+ * than 0 / 1) gets threshold = fallback, 0 in the four counts and tuned = 0; the other columns are unaffected.
+ * Deterministic: the same bits from run to run and under any permutation of the rows.  Nothing is allocated, synchronised or
+ * read back, the inputs are not written, everything is enqueued on `stream`.  The workspace needs no alignment.  Validation
+ * before any launch, in this order: LAMP_E_DIMS (a non-positive size, ld < L), LAMP_E_NULL (any pointer but tuned),
+ * LAMP_E_UNSUPPORTED (an unknown criterion, n_rows >= 2^31, a shape the sort does not serve), LAMP_E_WORKSPACE.
+ * lamp_tune_thresholds_workspace_bytes is 0 for a shape that is not served.
+ *
+ * lamp_threshold_counts_vec is lamp_threshold_counts with one threshold per label: thresholds fp32 [L], device-resident.
+ * prediction = (score, NaN read as 0) >= thresholds[label].  A +inf threshold predicts nothing (scores are <= 1), and so
+ * does a NaN threshold (the comparison is false).  With every entry equal to t it writes what lamp_threshold_counts(t)
+ * writes.  LAMP_E_DIMS, LAMP_E_NULL, LAMP_E_UNSUPPORTED in that order before any launch. */
+enum lamp_tune_criterion { LAMP_TUNE_F1 = 0, LAMP_TUNE_YOUDEN = 1, LAMP_TUNE_BALANCE = 2 };
+size_t lamp_tune_thresholds_workspace_bytes(int64_t n_rows, int32_t L);
+int lamp_tune_thresholds(const float* probs, int64_t ld_probs, const float* targets, int64_t ld_targets, int64_t n_rows,
+                         int32_t L, int32_t criterion, float fallback, float* threshold, int32_t* tp, int32_t* fp,
+                         int32_t* n_pos, int32_t* n_neg, int32_t* tuned, void* workspace, size_t workspace_bytes,
+                         lamp_stream_t stream);
+int lamp_threshold_counts_vec(const float* probs, int64_t ld_probs, const float* targets, int64_t ld_targets, int64_t n_rows,
+                              int32_t L, const float* thresholds, int32_t* label_tp, int32_t* label_fp, int32_t* label_fn,
+                              int32_t* sample_tp, int32_t* sample_pred, int32_t* sample_gold, int32_t* sample_mismatch,
+                              lamp_stream_t stream);
+
 /* ---- ranking the labels of one sample: top-k predictions, precision / nDCG / recall at k (csrc/rank_at_k.hip) ---------
  * THE ORDER.  In a row of scores, element a at column i ranks before element b at column j when one of these holds:
  *   1. a is a number and b is NaN;

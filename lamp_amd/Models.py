@@ -594,6 +594,30 @@ class LAMP(nn.Module):
             if was_training:
                 self.train(True)
 
+    def predict_labels(self, src, thresholds=0.5, adj=None):
+        """The predicted label set of every sample: an eval forward under no_grad, then the rule of lamp_threshold_counts --
+        sigmoid(logit), a NaN read as 0, >= threshold.  `thresholds` is a float for all labels or a tensor of length L (one per
+        label, e.g. metrics.tune_thresholds(...)['threshold'] fitted on the validation split; +inf or NaN predicts nothing).
+        -> bool (B, L).  Works on the fused and on the module-by-module route; there is no CPU path."""
+        if not src[0].is_cuda:
+            N.require_device(src[0])   # raises: HIP device only
+        was_training = self.training
+        if was_training:
+            self.eval()
+        try:
+            with torch.no_grad(), torch.cuda.device(src[0].device):
+                probs = torch.nan_to_num(torch.sigmoid(self.forward(src, adj, None, None)[0]), nan=0.0)
+                if torch.is_tensor(thresholds):
+                    thresholds = thresholds.detach().to(device=probs.device, dtype=torch.float32)
+                    if thresholds.dim() != 1 or thresholds.numel() != probs.size(1):
+                        raise ValueError('thresholds: expected a tensor of length %d, got shape %s' %
+                                         (probs.size(1), tuple(thresholds.shape)))
+                    return probs >= thresholds.unsqueeze(0)
+                return probs >= torch.tensor(float(thresholds), dtype=torch.float32, device=probs.device)   # rounded as the C ABI's float
+        finally:
+            if was_training:
+                self.train(True)
+
     # Upper bound on the scratch a forward may claim; larger batches are processed in micro-batches
     # inside lamp_forward.  8 GiB of 288 GB keeps even the 4096-label configuration at >= 64 samples.
     workspace_limit_bytes = 8 << 30

@@ -225,6 +225,9 @@ PROTOTYPES = {
     'lamp_ranking_metrics_workspace_bytes': (_sz, [_i64, _i32]),
     'lamp_ranking_metrics': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'lamp_threshold_counts': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _f] + [_vp] * 7 + [_vp]),
+    'lamp_tune_thresholds_workspace_bytes': (_sz, [_i64, _i32]),
+    'lamp_tune_thresholds': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _f] + [_vp] * 6 + [_vp, _sz, _vp]),
+    'lamp_threshold_counts_vec': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp] + [_vp] * 7 + [_vp]),
     'lamp_topk_labels': (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
     'lamp_rank_at_k_workspace_bytes': (_sz, [_i64, _i32]),
     'lamp_rank_at_k': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp, _vp,
@@ -250,7 +253,8 @@ PROTOTYPES = {
 # entry points added without an ABI bump (no struct changed): a library of the same ABI version built before them lacks the
 # symbols -- same-box A/B runs against the previous build (LAMP_HIP_LIBRARY) -- and their callers ask with getattr
 LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs', 'lamp_forward_packs_kv', 'lamp_attn_bias_bwd_workspace_bytes', 'lamp_attn_bias_bwd',
-                     'lamp_label_bias_fold', 'lamp_topk_labels', 'lamp_rank_at_k_workspace_bytes', 'lamp_rank_at_k')
+                     'lamp_label_bias_fold', 'lamp_topk_labels', 'lamp_rank_at_k_workspace_bytes', 'lamp_rank_at_k',
+                     'lamp_tune_thresholds_workspace_bytes', 'lamp_tune_thresholds', 'lamp_threshold_counts_vec')
 
 _lib = None
 _lock = threading.Lock()

@@ -30,7 +30,7 @@ LIB = os.path.join(HERE, 'liblamp_hip.so')
 LIB_TUNING = os.path.join(HERE, 'liblamp_hip_tuning.so')
 SOURCES = ['gemm.hip', 'gemm_split.hip', 'gemm_gen.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_general.hip', 'attention_sparse.hip',
            'attention_ragged.hip', 'attention_sigmoid.hip', 'attention_bias.hip', 'pointwise.hip',
-           'backward.hip', 'chain.hip', 'conv.hip', 'metrics.hip', 'rank_at_k.hip', 'train_step.hip', 'api.hip']
+           'backward.hip', 'chain.hip', 'conv.hip', 'metrics.hip', 'thresholds.hip', 'rank_at_k.hip', 'train_step.hip', 'api.hip']
 TUNING_SOURCES = {'gemm.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_sparse.hip', 'chain.hip'}
 TUNING_ONLY = ['experiments/slab.hip']   # experiments kept bit-identical and benchmarkable, never part of the product library
 HEADERS = [os.path.join(CSRC, 'lamp_kernels.h'), os.path.join(CSRC, 'lamp_asm.h'), os.path.join(HERE, '..', 'include', 'lamp_hip.h')]
@@ -123,7 +123,7 @@ def built_toolchain():
 
 
 GUARD_KERNELS = ('chain', 'slab', 'attn_tile')   # kernels with inline-assembly loads: registers must stay where the loads land
-LEAN_UNITS = ('train_step.hip', 'attention_ragged.hip', 'rank_at_k.hip')   # units whose kernels must use neither scratch nor AGPRs (checked at every build)
+LEAN_UNITS = ('train_step.hip', 'attention_ragged.hip', 'rank_at_k.hip', 'thresholds.hip')   # units whose kernels must use neither scratch nor AGPRs (checked at every build)
 
 
 def _resource_problems(source, tuning):

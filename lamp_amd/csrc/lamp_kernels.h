@@ -414,4 +414,15 @@ struct AttrOnce {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// metrics.hip: the label-major key build and per-column sort behind lamp_ranking_metrics, shared with thresholds.hip.
+// keys[l * n + i], ascending in i: key = (bits(score, -0.0 read as +0.0) << 1) | target for a rankable column; invalid[l] != 0
+// marks a column that cannot be ranked (NaN / out-of-range score, target other than 0 / 1).  Both point into the workspace.
+struct RankSorted {
+    const uint32_t* keys;
+    const uint32_t* invalid;
+};
+size_t rank_sort_workspace_bytes(int64_t n, int32_t L);   // 0 = the shape is not served
+int rank_sort_columns(const float* probs, int64_t ld_probs, const float* targets, int64_t ld_targets, int64_t n, int32_t L,
+                      void* workspace, size_t workspace_bytes, lamp_stream_t stream, RankSorted* out);
+
 }  // namespace lamp

@@ -382,18 +382,18 @@ AttrOnce g_sort_lds_attr;
 
 using namespace lamp;
 
-size_t lamp_ranking_metrics_workspace_bytes(int64_t n_rows, int32_t L) {
+// The sequence lamp_ranking_metrics and lamp_tune_thresholds (thresholds.hip) share: the workspace layout, the key build, the
+// LDS or radix sort of every label column and the per-label `invalid` flags.  The caller has checked dimensions and pointers;
+// LAMP_E_UNSUPPORTED / LAMP_E_WORKSPACE come back before anything is launched.
+size_t lamp::rank_sort_workspace_bytes(int64_t n, int32_t L) {
     RankLayout g;
-    return rank_layout(n_rows, L, &g) ? g.total : 0;
+    return rank_layout(n, L, &g) ? g.total : 0;
 }
 
-int lamp_ranking_metrics(const float* probs, int64_t ld_probs, const float* targets, int64_t ld_targets, int64_t n_rows, int32_t L,
-                         double fdr_cutoff, double* auc, double* aupr, double* fdr_recall, int64_t* n_pos, int64_t* n_neg,
-                         void* workspace, size_t workspace_bytes, lamp_stream_t stream) {
-    if (n_rows <= 0 || L <= 0 || ld_probs < L || ld_targets < L) return LAMP_E_DIMS;
-    if (!probs || !targets || !auc || !aupr || !fdr_recall || !workspace) return LAMP_E_NULL;
+int lamp::rank_sort_columns(const float* probs, int64_t ld_probs, const float* targets, int64_t ld_targets, int64_t n, int32_t L,
+                            void* workspace, size_t workspace_bytes, lamp_stream_t stream, RankSorted* out) {
     RankLayout g;
-    if (!rank_layout(n_rows, L, &g)) return LAMP_E_UNSUPPORTED;
+    if (!rank_layout(n, L, &g)) return LAMP_E_UNSUPPORTED;
     char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
     if (workspace_bytes < g.total) return LAMP_E_WORKSPACE;   // (g.total holds the 255 bytes `base` may have moved)
     hipStream_t s = hipStream_t(stream);
@@ -402,34 +402,53 @@ int lamp_ranking_metrics(const float* probs, int64_t ld_probs, const float* targ
     uint32_t* hist = reinterpret_cast<uint32_t*>(base + g.hist);
     uint32_t* invalid = reinterpret_cast<uint32_t*>(base + g.invalid);
     if (hipError_t e = hipMemsetAsync(invalid, 0, size_t(L) * sizeof(uint32_t), s)) return int(e);
-    const int64_t row_tiles = (n_rows + 63) / 64;
+    const int64_t row_tiles = (n + 63) / 64;
     const int label_tiles = (L + 63) / 64;
     if (label_tiles > 65535) return LAMP_E_UNSUPPORTED;
     hipLaunchKernelGGL(metric_keys_kernel, dim3(unsigned(row_tiles), unsigned(label_tiles)), dim3(256), 0, s, probs, ld_probs,
-                       targets, ld_targets, n_rows, L, keys_a, invalid);
+                       targets, ld_targets, n, L, keys_a, invalid);
     const uint32_t* sorted = keys_a;
     if (!g.global_route) {
         int npow2 = 1;
-        while (npow2 < n_rows) npow2 <<= 1;
+        while (npow2 < n) npow2 <<= 1;
         const size_t lds = size_t(npow2) * sizeof(uint32_t);
         if (lds > 48 * 1024)
             if (int e = g_sort_lds_attr.set(reinterpret_cast<const void*>(sort_lds_kernel), size_t(SORT_LDS_MAX) * sizeof(uint32_t)))
                 return e;
-        hipLaunchKernelGGL(sort_lds_kernel, dim3(unsigned(L)), dim3(SORT_LDS_THREADS), lds, s, keys_a, n_rows, npow2);
+        hipLaunchKernelGGL(sort_lds_kernel, dim3(unsigned(L)), dim3(SORT_LDS_THREADS), lds, s, keys_a, n, npow2);
     } else {
         const unsigned blocks = unsigned(int64_t(g.chunks) * L);
         uint32_t* src = keys_a;
         uint32_t* dst = keys_b;
         for (int pass = 0; pass < 4; ++pass) {   // keys have 31 significant bits
-            hipLaunchKernelGGL(radix_hist_kernel, dim3(blocks), dim3(256), 0, s, src, n_rows, g.chunks, 8 * pass, hist);
+            hipLaunchKernelGGL(radix_hist_kernel, dim3(blocks), dim3(256), 0, s, src, n, g.chunks, 8 * pass, hist);
             hipLaunchKernelGGL(radix_scan_kernel, dim3(unsigned(L)), dim3(256), 0, s, hist, g.chunks);
-            hipLaunchKernelGGL(radix_scatter_kernel, dim3(blocks), dim3(256), 0, s, src, dst, n_rows, g.chunks, 8 * pass, hist);
+            hipLaunchKernelGGL(radix_scatter_kernel, dim3(blocks), dim3(256), 0, s, src, dst, n, g.chunks, 8 * pass, hist);
             uint32_t* t = src;
             src = dst;
             dst = t;
         }
         sorted = src;   // an even number of passes: keys_a again
     }
+    out->keys = sorted;
+    out->invalid = invalid;
+    return 0;
+}
+
+size_t lamp_ranking_metrics_workspace_bytes(int64_t n_rows, int32_t L) {
+    return rank_sort_workspace_bytes(n_rows, L);
+}
+
+int lamp_ranking_metrics(const float* probs, int64_t ld_probs, const float* targets, int64_t ld_targets, int64_t n_rows, int32_t L,
+                         double fdr_cutoff, double* auc, double* aupr, double* fdr_recall, int64_t* n_pos, int64_t* n_neg,
+                         void* workspace, size_t workspace_bytes, lamp_stream_t stream) {
+    if (n_rows <= 0 || L <= 0 || ld_probs < L || ld_targets < L) return LAMP_E_DIMS;
+    if (!probs || !targets || !auc || !aupr || !fdr_recall || !workspace) return LAMP_E_NULL;
+    RankSorted r;
+    if (int e = rank_sort_columns(probs, ld_probs, targets, ld_targets, n_rows, L, workspace, workspace_bytes, stream, &r)) return e;
+    hipStream_t s = hipStream_t(stream);
+    const uint32_t* sorted = r.keys;
+    const uint32_t* invalid = r.invalid;
     hipLaunchKernelGGL(curve_walk_kernel, dim3(unsigned(L)), dim3(256), 0, s, sorted, n_rows, invalid, fdr_cutoff, auc, aupr,
                        fdr_recall, n_pos, n_neg);
     return int(hipGetLastError());

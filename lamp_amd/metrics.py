@@ -18,6 +18,11 @@ of every row in the order include/lamp_hip.h defines (a number before a NaN, the
 tie), rank_at_k and compute_metrics(at_k=...) the precision, nDCG and recall at those ranks from integer hit counts and
 fixed-order fp64 sums (lamp_rank_at_k), a sample without a gold label adding 0 as sklearn's ndcg_score(ignore_ties=True) has it.
 
+Fitted decision thresholds (csrc/thresholds.hip) are opt-in too: tune_thresholds walks the same sorted
+columns once more and picks, per label, the candidate threshold that is best under F1, Youden's J or the reference's
+Find_Optimal_Cutoff balance, compared in integers with ties to the highest threshold (lamp_tune_thresholds); threshold_counts
+and compute_metrics(thresholds=...) then take one threshold per label (lamp_threshold_counts_vec).
+
 There is no CPU path: without a HIP device compute_metrics raises (N.require_device).
 """
 import ctypes as C
@@ -70,8 +75,17 @@ def ranking_metrics(probs, targets, fdr_cutoff=0.5):
     return out[0], out[1], out[2], counts[0], counts[1]
 
 
+def _threshold_vector(thresholds, L, device):
+    """A length-L tensor of thresholds -> contiguous float32 on `device` (uploaded when it is a host tensor)."""
+    thr = thresholds.detach().to(device=device, dtype=torch.float32).contiguous()
+    if thr.dim() != 1 or thr.numel() != L:
+        raise ValueError('thresholds: expected a tensor of length %d, got shape %s' % (L, tuple(thresholds.shape)))
+    return thr
+
+
 def _counts_buffer(probs, targets, threshold):
-    """-> int32 device buffer: the (3, L) label counts, then the (4, n) sample counts."""
+    """-> int32 device buffer: the (3, L) label counts, then the (4, n) sample counts.  `threshold`: a python float, or a
+    float32 tensor of length L (one threshold per label)."""
     N.require_device(probs, targets)
     p, ldp = _matrix(probs)
     t, ldt = _matrix(targets)
@@ -80,6 +94,12 @@ def _counts_buffer(probs, targets, threshold):
     n, L = p.shape
     buf = torch.empty(3 * L + 4 * n, dtype=torch.int32, device=p.device)
     lab, ex = buf[:3 * L].view(3, L), buf[3 * L:].view(4, n)
+    if torch.is_tensor(threshold):
+        thr = _threshold_vector(threshold, L, p.device)
+        N.check(N.lib().lamp_threshold_counts_vec(N.ptr(p), ldp, N.ptr(t), ldt, n, L, N.ptr(thr), N.ptr(lab[0]), N.ptr(lab[1]),
+                                                  N.ptr(lab[2]), N.ptr(ex[0]), N.ptr(ex[1]), N.ptr(ex[2]), N.ptr(ex[3]),
+                                                  N.stream()), 'lamp_threshold_counts_vec')
+        return buf
     N.check(N.lib().lamp_threshold_counts(N.ptr(p), ldp, N.ptr(t), ldt, n, L, float(threshold), N.ptr(lab[0]), N.ptr(lab[1]),
                                           N.ptr(lab[2]), N.ptr(ex[0]), N.ptr(ex[1]), N.ptr(ex[2]), N.ptr(ex[3]), N.stream()),
             'lamp_threshold_counts')
@@ -87,7 +107,8 @@ def _counts_buffer(probs, targets, threshold):
 
 
 def threshold_counts(probs, targets, threshold):
-    """-> (label counts int32 (3, L): tp, fp, fn;  sample counts int32 (4, n): tp, predicted, gold, mismatches) on the device."""
+    """-> (label counts int32 (3, L): tp, fp, fn;  sample counts int32 (4, n): tp, predicted, gold, mismatches) on the device.
+    `threshold` is a python float for all labels or a float32 tensor of length L."""
     n, L = probs.shape
     buf = _counts_buffer(probs, targets, threshold)
     return buf[:3 * L].view(3, L), buf[3 * L:].view(4, n)
@@ -123,6 +144,73 @@ def aggregate(values):
     if v.size == 0:
         return float('nan'), float('nan'), float('nan')
     return float(np.mean(v)), float(np.median(v)), float(np.var(v))
+
+
+TUNE_CRITERIA = {'f1': 0, 'youden': 1, 'balance': 2}   # include/lamp_hip.h: enum lamp_tune_criterion
+
+
+def tune_thresholds(probs, targets, criterion='f1', fallback=0.5, scope='label'):
+    """The decision threshold per label that is best under `criterion` on these rows (include/lamp_hip.h: lamp_tune_thresholds;
+    'f1', 'youden' = tpr - fpr, 'balance' = the reference's Find_Optimal_Cutoff quantity |tpr - (1 - fpr)|; ties to the highest
+    threshold).  -> a dict of device tensors of length L: 'threshold' float32 (+inf: predict nothing), 'tp', 'fp', 'n_pos',
+    'n_neg' int32 (the counts at the chosen threshold and the column's positives / negatives) and 'tuned' bool (False for a
+    column that cannot be ranked: its threshold is `fallback`, its counts 0).  Nothing is synchronised.
+    scope='global' tunes ONE threshold on the flattened matrix (under 'f1' the micro-F1-optimal cutoff; n L < 2^31): every
+    entry of the result is that single column's, broadcast to length L."""
+    if criterion not in TUNE_CRITERIA:
+        raise ValueError("criterion must be one of 'f1', 'youden', 'balance'; got %r" % (criterion,))
+    if scope not in ('label', 'global'):
+        raise ValueError("scope must be 'label' or 'global'; got %r" % (scope,))
+    N.require_device(probs, targets)
+    p, ldp = _matrix(probs)
+    t, ldt = _matrix(targets)
+    if p.shape != t.shape:
+        raise ValueError('predictions %s and targets %s differ in shape' % (tuple(p.shape), tuple(t.shape)))
+    n_labels = p.size(1)
+    if scope == 'global':
+        if p.numel() >= 1 << 31:
+            raise ValueError("tune_thresholds(scope='global'): n L = %d is not below 2^31" % p.numel())
+        p, t = p.contiguous().view(-1, 1), t.contiguous().view(-1, 1)
+        ldp = ldt = 1
+    n, L = p.shape
+    lib = N.lib()
+    nbytes = lib.lamp_tune_thresholds_workspace_bytes(n, L)
+    if nbytes == 0:
+        raise ValueError('tune_thresholds: unsupported shape (%d, %d)' % (n, L))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    out = torch.empty((6, L), dtype=torch.int32, device=p.device)   # row 0 holds the float32 thresholds
+    thr = out[0].view(torch.float32)
+    N.check(lib.lamp_tune_thresholds(N.ptr(p), ldp, N.ptr(t), ldt, n, L, TUNE_CRITERIA[criterion], float(fallback), N.ptr(thr),
+                                     N.ptr(out[1]), N.ptr(out[2]), N.ptr(out[3]), N.ptr(out[4]), N.ptr(out[5]), N.ptr(ws), nbytes,
+                                     N.stream()), 'lamp_tune_thresholds')
+    res = {'threshold': thr, 'tp': out[1], 'fp': out[2], 'n_pos': out[3], 'n_neg': out[4], 'tuned': out[5] != 0}
+    if scope == 'global':
+        res = {k: v.expand(n_labels) for k, v in res.items()}
+    return res
+
+
+def tuned_values(result, criterion):
+    """The criterion's value at the chosen threshold of every label, in fp64 from the integers of a tune_thresholds result
+    (copied to the host here): 'f1' 2 tp / (tp + fp + n_pos), 'youden' tp / n_pos - fp / n_neg, 'balance'
+    |tp / n_pos - (1 - fp / n_neg)|, each as ONE division of exact integers.  NaN where the value is undefined: a label that
+    was not tuned, 'f1' with nothing predicted and no positive, 'youden' / 'balance' without a positive or without a negative."""
+    if criterion not in TUNE_CRITERIA:
+        raise ValueError("criterion must be one of 'f1', 'youden', 'balance'; got %r" % (criterion,))
+    host = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in result.items()}
+    out = np.full(len(host['tp']), np.nan, dtype=np.float64)
+    for l in range(len(out)):
+        if not host['tuned'][l]:
+            continue
+        tp, fp, P, Nn = (int(host[k][l]) for k in ('tp', 'fp', 'n_pos', 'n_neg'))
+        if criterion == 'f1':
+            num, den = 2 * tp, tp + fp + P
+        elif criterion == 'youden':
+            num, den = tp * Nn - fp * P, P * Nn
+        else:
+            num, den = abs(tp * Nn + fp * P - P * Nn), P * Nn
+        if den > 0:
+            out[l] = num / den
+    return out
 
 
 TOPK_MAX_K, TOPK_MAX_L = 64, 32768   # include/lamp_hip.h: lamp_topk_labels
@@ -202,13 +290,15 @@ def rank_at_k(scores, targets, ks=(1, 3, 5)):
 
 
 def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapsed=0.0, all_metrics=True, device=None,
-                    fdr_cutoff=0.5, at_k=None):
+                    fdr_cutoff=0.5, at_k=None, thresholds=None):
     """utils/evals.py:316-407 for the binary-relevance decoders: a dict with the reference's keys -- ACC, HA, ebF1, miF1, maF1,
     meanAUC, medianAUC, meanAUPR, medianAUPR, allAUC, allAUPR, meanFDR, medianFDR, loss, time.  allAUC / allAUPR are float64
     arrays of length L (NaN for a label that cannot be ranked); all_metrics=False gives 0 for the ranking entries, as the
     reference does.  (n, L) tensors of probabilities in [0, 1] and 0 / 1 targets, on the CPU (uploaded once, to `device` or the
     current HIP device) or on the device; the inputs are not modified.  at_k=(1, 3, 5) adds the keys of rank_at_k for those k
-    (P@k, nDCG@k, R@k, n_with_gold); with the default the dict is what it was."""
+    (P@k, nDCG@k, R@k, n_with_gold); with the default the dict is what it was.  thresholds = a float32 tensor of length L (as
+    tune_thresholds fitted it, on another split) makes the five thresholded figures use one threshold per label instead of
+    br_threshold; with None not one more launch happens."""
     if not all_predictions.is_cuda:
         if not torch.cuda.is_available():
             N.require_device(all_predictions)      # raises: HIP device only
@@ -218,7 +308,8 @@ def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapse
         all_targets = all_targets.to(all_predictions.device)
     with torch.cuda.device(all_predictions.device):
         n, L = all_predictions.shape
-        counts_d = _counts_buffer(all_predictions, all_targets, br_threshold)
+        counts_d = _counts_buffer(all_predictions, all_targets, br_threshold if thresholds is None else
+                                   torch.as_tensor(thresholds, dtype=torch.float32))
         ranked_d = _ranking_buffer(all_predictions, all_targets, fdr_cutoff) if all_metrics else None
         if at_k is not None:
             ks = _check_ks(at_k, L)

@@ -4,7 +4,7 @@ on the MI355X path.
     python -m lamp_amd.run_eval -data data/reuters/train_valid_test.pt -dataset reuters \
            -d_model 512 -d_inner_hid 512 -n_layers_enc 2 -n_head 4 -label_mask prior \
            [-checkpoint results/.../model.chkpt] [-split test] [-batch_size 32] [-streams 2] [-gpus N] [-all_metrics]
-           [-at_k 1,3,5]
+           [-at_k 1,3,5] [-tune_thresholds f1|youden|balance|checkpoint [-tune_split valid] [-tune_scope label|global]]
 
 -gpus N starts one process per GPU (rendezvous on 127.0.0.1; "nccl" = RCCL for the final gather only); every rank
 evaluates its contiguous share of the batches -- the forward path needs no collective (lamp_amd/sharding.py).
@@ -20,6 +20,12 @@ reference's conventions for empty samples / labels); with -all_metrics also the 
 all_metrics=True (:208-298: mean / median AUC, AUPR and recall at FDR <= 0.5 over the labels, and the per-label arrays), on the
 device (lamp_amd/metrics.py); with -at_k 1,3,5 precision, nDCG and recall at those ranks, each sample's labels ranked on
 the device in the order include/lamp_hip.h defines (the figures are printed on stderr and join the JSON result line).
+With -tune_thresholds f1|youden|balance the -tune_split (valid) is evaluated first and one decision threshold per label is
+fitted on it on the device (lamp_amd/metrics.py: tune_thresholds), then -split is evaluated as always and
+the five thresholded figures at the fitted thresholds join the JSON line as tuned_ACC, tuned_HA, tuned_ebF1, tuned_miF1 and
+tuned_maF1, with tune_criterion, tune_split, n_labels_tuned, thresholds (a list; Infinity = the label is never predicted) and
+tune_seconds; the figures at -br_threshold stay.  -tune_thresholds checkpoint takes the thresholds run_train -tune_thresholds
+stored in the checkpoint.
 """
 import argparse
 import json
@@ -88,6 +94,14 @@ def parse(argv=None):
                     help='comma-separated ranks, e.g. 1,3,5: also report precision (P@k), nDCG@k and recall (R@k) at those k, each '
                          "sample's labels ranked on the device (lamp_amd/metrics.py: rank_at_k; every k <= min(n_labels, 64)); "
                          'independent of -all_metrics; with -gpus N by rank 0 after the combine')
+    ap.add_argument('-tune_thresholds', type=str, choices=['f1', 'youden', 'balance', 'checkpoint'], default=None,
+                    help='fit one decision threshold per label on -tune_split under this criterion (lamp_amd/metrics.py: '
+                         "tune_thresholds) and also report the thresholded figures of -split at them (tuned_*); 'checkpoint' takes "
+                         'the thresholds run_train -tune_thresholds stored in -checkpoint; with -gpus N rank 0 tunes on what it '
+                         'gathered')
+    ap.add_argument('-tune_split', default='valid', choices=['train', 'valid', 'test'], help='the split the thresholds are fitted on')
+    ap.add_argument('-tune_scope', default='label', choices=['label', 'global'],
+                    help='label = one threshold per label; global = one threshold for all labels, fitted on the flattened matrix')
     ap.add_argument('-seed', type=int, default=0, help='weight init seed when no checkpoint is given')
     ap.add_argument('-gpus', type=int, default=1, help='processes (one per GPU) the batches are sharded over')
     opt = ap.parse_args(argv)
@@ -274,7 +288,12 @@ def main(argv=None):
     geometry = dict(n_head2=opt.n_head2, d_k=opt.d_k, d_v=opt.d_v)
     geometry.update(load_checkpoint_head_geometry(ckpt))   # the checkpoint's settings override the flags
     learn = load_checkpoint_learn_label_bias(ckpt)
+    stored_thresholds = ckpt.get('label_thresholds') if isinstance(ckpt, dict) and 'model' in ckpt else None
+    stored_criterion = ckpt.get('tune_criterion') if isinstance(ckpt, dict) and 'model' in ckpt else None
     del ckpt
+    if opt.tune_thresholds == 'checkpoint' and stored_thresholds is None:
+        raise SystemExit('-tune_thresholds checkpoint: %s holds no label_thresholds (run_train -tune_thresholds f1|youden|balance '
+                         'stores them)' % (opt.checkpoint or 'no -checkpoint was given, and a run without one'))
     if stored is not None:   # the checkpoint's settings override the flags
         bias_kind, bias_scale = stored
     # a trained label graph is among the weights (decoder.label_bias): nothing to rebuild but the mask above
@@ -290,10 +309,34 @@ def main(argv=None):
         model.load_state_dict(state)
     model = model.to(device).eval()
     model.matmul_precision = opt.matmul_precision
+    tuned = None
+    if opt.tune_thresholds == 'checkpoint':
+        thresholds = torch.as_tensor(stored_thresholds, dtype=torch.float32).reshape(-1)
+        if thresholds.numel() != n_labels:
+            raise SystemExit('-tune_thresholds checkpoint: %d stored thresholds for %d labels' % (thresholds.numel(), n_labels))
+        tuned = {'thresholds': thresholds.to(device), 'tune_criterion': stored_criterion, 'tune_split': None,
+                 'n_labels_tuned': None, 'tune_seconds': 0.0}
+    elif opt.tune_thresholds:
+        from .metrics import tune_thresholds
+        t1 = time.perf_counter()
+        tune_batches = D.EvalBatcher(data[opt.tune_split]['src'], data[opt.tune_split]['tgt'], opt.batch_size)
+        tune_dev = {} if world == 1 else None
+        tune_preds, tune_targets, _ = test_epoch(model, tune_batches, n_labels, opt.batch_size, device, streams=opt.streams,
+                                                 prefetch=opt.prefetch, merge_stage=opt.merge_stages, world_size=world,
+                                                 rank=rank, group=plane.group, device_results=tune_dev)
+        if rank == 0:
+            fit = (tune_thresholds(tune_dev['probs'], tune_dev['targets'], opt.tune_thresholds, opt.br_threshold, opt.tune_scope)
+                   if tune_dev else tune_thresholds(tune_preds.to(device), tune_targets.to(device), opt.tune_thresholds,
+                                                    opt.br_threshold, opt.tune_scope))
+            tuned = {'thresholds': fit['threshold'].contiguous(), 'tune_criterion': opt.tune_thresholds,
+                     'tune_split': opt.tune_split, 'n_labels_tuned': int(fit['tuned'].sum()),
+                     'tune_seconds': time.perf_counter() - t1}
+        del tune_preds, tune_targets, tune_dev
     split = data[opt.split]
     batches = D.EvalBatcher(split['src'], split['tgt'], opt.batch_size)
     torch.cuda.synchronize()
-    on_device = {} if (opt.all_metrics or opt.at_k) and world == 1 else None   # one rank holds the whole split: nothing goes back up
+    # one rank holds the whole split: nothing goes back up
+    on_device = {} if (opt.all_metrics or opt.at_k or opt.tune_thresholds) and world == 1 else None
     t0 = time.perf_counter()
     preds, targets, bce_total = test_epoch(model, batches, n_labels, opt.batch_size, device, streams=opt.streams,
                                            prefetch=opt.prefetch, merge_stage=opt.merge_stages,
@@ -321,6 +364,19 @@ def main(argv=None):
         out['at_k_seconds'] = time.perf_counter() - t1
         print('  '.join('%s %.6f' % (key, at_k[key]) for key in at_k if key != 'n_with_gold') +
               '  n_with_gold %d' % at_k['n_with_gold'], file=sys.stderr, flush=True)
+    if tuned is not None and rank == 0:
+        from .metrics import compute_metrics
+        t1 = time.perf_counter()
+        m = (compute_metrics(on_device['probs'], on_device['targets'], bce_total, opt.br_threshold, all_metrics=False,
+                             thresholds=tuned['thresholds']) if on_device else
+             compute_metrics(preds, targets, bce_total, opt.br_threshold, all_metrics=False, device=device,
+                             thresholds=tuned['thresholds']))
+        out.update({'tuned_' + k: m[k] for k in ('ACC', 'HA', 'ebF1', 'miF1', 'maF1')})
+        out.update(tune_criterion=tuned['tune_criterion'], tune_split=tuned['tune_split'],
+                   n_labels_tuned=tuned['n_labels_tuned'], thresholds=tuned['thresholds'].cpu().tolist(),
+                   tune_seconds=tuned['tune_seconds'] + time.perf_counter() - t1)
+        print('  '.join('tuned_%s %.6f' % (k, out['tuned_' + k]) for k in ('ACC', 'HA', 'ebF1', 'miF1', 'maF1')),
+              file=sys.stderr, flush=True)
     if rank == 0:
         print(json.dumps(out), flush=True)
     plane.close()

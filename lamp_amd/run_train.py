@@ -4,6 +4,7 @@ decoder=graph, on the MI355X path.
     python -m lamp_amd.run_train -data data/reuters/train_valid_test.pt -dataset reuters -batch_size 32 \
            -d_model 512 -n_layers_enc 2 -n_head 4 -label_mask prior -epoch 50 -dropout 0.1 -lr 0.0002 [-int_preds] \
            [-enc_self_att] [-attn_type sigmoid] [-lr_decay 0.9 -lr_step_size 10] [-save_mode best] [-load_pretrained] [-name run1] [-results_dir results/]
+           [-tune_thresholds f1|youden|balance]
 
 Flag names and derived defaults are config_args.py's for everything on this path (n_layers_dec = n_layers_enc :87-88,
 test_batch_size = batch_size :93-94, d_k = d_v = d_model / n_head :96-99, dec_dropout = dropout :101-102, no position
@@ -21,6 +22,12 @@ rule's `valid_loss >= min(valid_losses)` is kept as written: the list already ho
 rewrites model.chkpt after EVERY epoch -- the reference's behaviour, not a selection of the best epoch.  As in the reference
 (runner.py:85) nothing is saved when the results directory's name contains 'test'.  The file loads in
 `run_eval -checkpoint` and in the reference's `main.py -load_pretrained`.
+
+-tune_thresholds f1|youden|balance fits one decision threshold per label on every epoch's validation predictions, still on the
+device (lamp_amd/metrics.py: tune_thresholds), reports the test epoch's thresholded figures at them as
+tuned_ACC .. tuned_maF1 next to the fixed ones in that epoch's record, stores `label_thresholds` (a CPU float32 tensor) and
+`tune_criterion` in the checkpoint beside model / settings / epoch (run_eval -tune_thresholds checkpoint reads them) and adds
+.thr_<criterion> to the results name.
 """
 import argparse
 import json
@@ -87,6 +94,10 @@ def parse(argv=None):
                     help="train the label graph: the score bias is a parameter (LAMP(learn_label_bias=True)), initialised from "
                          "-label_bias adj|logp or from zeros with none; -label_mask still decides which edges exist at all; "
                          "stored in the checkpoint's settings (and the bias in its weights) for run_eval")
+    ap.add_argument('-tune_thresholds', type=str, choices=['f1', 'youden', 'balance'], default=None,
+                    help="after each validation epoch fit one decision threshold per label on the valid predictions (lamp_amd/"
+                         "metrics.py: tune_thresholds), report the test epoch's tuned_* figures and store label_thresholds / "
+                         "tune_criterion in the checkpoint for run_eval -tune_thresholds checkpoint")
     ap.add_argument('-optim_impl', choices=['lamp', 'torch'], default=DEFAULT_OPTIM_IMPL,
                     help='lamp = lamp_amd.optim (one lamp_optim_step launch per step); torch = torch.optim (fused=True for adam)')
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4], help='batches in flight in the valid / test epochs')
@@ -167,6 +178,9 @@ def derive(opt):
     opt.learn_label_bias = bool(getattr(opt, 'learn_label_bias', False))
     if opt.learn_label_bias:
         name += '.lbias_learn'
+    opt.tune_thresholds = getattr(opt, 'tune_thresholds', None) or None
+    if opt.tune_thresholds:
+        name += '.thr_' + opt.tune_thresholds
     if opt.name:
         name += '.' + str(opt.name)
     opt.model_name = os.path.join(opt.results_dir, opt.dataset, name)
@@ -220,14 +234,19 @@ def build_optimizer(model, opt):
 
 def checkpoint_settings(opt):
     """The Namespace that travels in the checkpoint: plain values only, so that it unpickles anywhere.  `learn_label_bias`
-    travels only when it is set: without the flag the settings are what they were before it existed."""
+    and `tune_thresholds` travel only when they are set: without the flags the settings are what they were before they
+    existed."""
     return argparse.Namespace(**{k: v for k, v in vars(opt).items() if isinstance(v, (bool, int, float, str, type(None)))
-                                 and (k != 'learn_label_bias' or v)})
+                                 and (k not in ('learn_label_bias', 'tune_thresholds') or v)})
 
 
-def save_model(opt, epoch_i, model, valid_loss, valid_losses):
-    """utils/utils.py:228-241, `>=` included (see the module docstring).  -> the path written, or None."""
+def save_model(opt, epoch_i, model, valid_loss, valid_losses, label_thresholds=None):
+    """utils/utils.py:228-241, `>=` included (see the module docstring).  -> the path written, or None.  With
+    -tune_thresholds the epoch's fitted thresholds travel beside the weights."""
     checkpoint = {'model': model.state_dict(), 'settings': checkpoint_settings(opt), 'epoch': epoch_i}
+    if label_thresholds is not None:
+        checkpoint['label_thresholds'] = label_thresholds.detach().to('cpu', torch.float32).contiguous()
+        checkpoint['tune_criterion'] = opt.tune_thresholds
     if opt.save_mode == 'all':
         path = opt.model_name + '/accu_{accu:3.3f}.chkpt'.format(accu=100 * valid_loss)
         torch.save(checkpoint, path)
@@ -251,7 +270,7 @@ def main(argv=None):
         raise SystemExit('lamp_amd.run_train needs an MI355X: no HIP device visible (there is no CPU path)')
     from . import hostcpu
     from .evaluate import test_epoch
-    from .metrics import compute_metrics
+    from .metrics import compute_metrics, tune_thresholds
     from .train import TrainBatcher, train_epoch
     hostcpu.fit_intra_op_threads()
     device = torch.device('cuda', torch.cuda.current_device())
@@ -292,6 +311,7 @@ def main(argv=None):
             out.update(train_loss=train_loss, train_seconds=dt,
                        train_samples_per_s=sum(real for _, real in on_dev['batches']) / dt)
             losses = {}
+            label_thresholds = None
             for split, batches in (('valid', valid_data), ('test', test_data)):
                 t0 = time.perf_counter()
                 on_dev = {}
@@ -301,13 +321,22 @@ def main(argv=None):
                 dt = time.perf_counter() - t0
                 losses[split] = loss / batches.n_insts
                 metrics[split] = compute_metrics(on_dev['probs'], on_dev['targets'], losses[split], opt.br_threshold, dt / 60)
+                if opt.tune_thresholds and split == 'valid':   # (valid comes first: the test epoch below uses them)
+                    fit = tune_thresholds(on_dev['probs'], on_dev['targets'], opt.tune_thresholds, opt.br_threshold)
+                    label_thresholds = fit['threshold']
+                    out['n_labels_tuned'] = int(fit['tuned'].sum())
+                    out['tune_criterion'] = opt.tune_thresholds
+                if label_thresholds is not None and split == 'test':
+                    tuned = compute_metrics(on_dev['probs'], on_dev['targets'], losses[split], opt.br_threshold, dt / 60,
+                                            all_metrics=False, thresholds=label_thresholds)
+                    metrics[split].update({'tuned_' + k: tuned[k] for k in ('ACC', 'HA', 'ebF1', 'miF1', 'maF1')})
                 out['%s_loss' % split] = losses[split]
                 out['%s_samples_per_s' % split] = batches.n_insts / dt
             valid_losses.append(losses['valid'])
             out['metrics'] = {k: _json_metrics(v) for k, v in metrics.items()}
             out['checkpoint'] = None
             if 'test' not in opt.model_name:   # runner.py:85
-                out['checkpoint'] = save_model(opt, epoch_i, model, losses['valid'], valid_losses)
+                out['checkpoint'] = save_model(opt, epoch_i, model, losses['valid'], valid_losses, label_thresholds)
             loss_file.write('%d,%s,%s,%s\n' % (epoch_i + 1, train_loss, losses['valid'], losses['test']))
             loss_file.flush()
             history.append(out)
