@@ -910,6 +910,40 @@ int lamp_bce_logits_train(const float* const* logits, const float* weights, floa
                           const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
                           int64_t ld_row_loss, lamp_stream_t stream);
 
+/* lamp_bce_logits_train with an objective for imbalanced label sets: per-label positive weights, focal loss (Lin et al. 2017)
+ * and asymmetric loss (Ridnik et al. 2021) are members of one family.  For logit x, target t, s = sigmoid(x), ns = sigmoid(-x),
+ * label column j, g+ = gamma_pos, g- = gamma_neg, m = clip, w_j = pos_weight[j] (1 without pos_weight):
+ *   l+(x)  = - ns^g+ log s                                   (positives)
+ *   p      = max(s - m, 0)
+ *   l-(x)  = - p^g- log(1 - p)                               (negatives; 1 - p = ns + m where s > m)
+ *   loss   = t w_j l+  +  (1 - t) l-
+ *   dl+/dx = - ns^g+ (ns - g+ s log s)
+ *   dl-/dx =   s ns (p^g- / (1 - p) - g- p^(g- - 1) log(1 - p))   where s > m, else 0
+ * with x^0 = 1, 0^0 included.  g+ = g- = 0, m = 0, no pos_weight: the BCE above.  g+ = g- = gamma, m = 0: focal loss, its
+ * alpha through w = alpha / (1 - alpha).  The published asymmetric setting is g+ = 0, g- = 4, m = 0.05.  A target inside
+ * (0, 1) mixes the two branches as written.
+ *   probs[r * ld_probs + i]            = sigmoid(logits[0][r, i])            (the same bits as lamp_bce_logits_train gives)
+ *   dlogits[k][r, i]                   = weights[k] * d loss / dx / (n_rows * L)
+ *   row_loss[k * ld_row_loss + r]      = sum_i loss(logits[k][r, i], targets[r, i])
+ * Same arguments, geometry and order of summation as lamp_bce_logits_train: a row's numbers do not depend on its batch.
+ * log s and log ns are taken from x (min(x, 0) - log1p(exp(-|x|)), -max(x, 0) - log1p(exp(-|x|))), so ns log ns is 0, not
+ * NaN, where ns underflows at a large finite x; the powers are exp(g log .); with m > 0, log(1 - p) = log1p(-p).
+ * opts == NULL, or gamma_pos = gamma_neg = clip = 0 with pos_weight NULL, IS lamp_bce_logits_train: the same kernel, the same
+ * bits.  Validated before any launch, in this order: LAMP_E_DIMS and LAMP_E_NULL as lamp_bce_logits_train, then
+ * LAMP_E_UNSUPPORTED: an exponent outside {0} u [1, 16] (between 0 and 1 the gradient is unbounded at p = 0), a non-finite
+ * parameter, clip outside [0, 1), reserved != 0, n_mats > 8.
+ * A NaN logit makes its own gradient element and its row's loss NaN, and nothing else.  A +-inf logit may give inf or NaN in
+ * its own element and row only.  The values of pos_weight are the caller's responsibility (a NaN or inf weight reaches every
+ * row's loss through its column). */
+typedef struct lamp_loss_options {
+    float gamma_pos, gamma_neg, clip;
+    int32_t reserved;          /* 0 */
+    const float* pos_weight;   /* L floats on the device, or NULL */
+} lamp_loss_options;
+int lamp_multilabel_loss_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
+                               const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
+                               int64_t ld_row_loss, const lamp_loss_options* opts, lamp_stream_t stream);
+
 /* lamp_embed_bwd with a fixed summation order, for a training epoch that must be reproducible bit for bit (the embedding
  * gradient feeds optimizer.step(), train.py:47-48): d_emb[src_seq[t], :] += dout[t, :], the rows of a repeated token added in
  * ascending position order by ONE writer per table row -- no atomics.  Same arguments and contract as lamp_embed_bwd; the

@@ -142,6 +142,11 @@ class OptimEntry(C.Structure):  # include/lamp_hip.h: lamp_optim_entry
     _fields_ = [('param', _vp), ('grad', _vp), ('exp_avg', _vp), ('exp_avg_sq', _vp), ('numel', C.c_int64)]
 
 
+class LossOptions(C.Structure):  # include/lamp_hip.h: lamp_loss_options
+    _fields_ = [('gamma_pos', C.c_float), ('gamma_neg', C.c_float), ('clip', C.c_float), ('reserved', C.c_int32),
+                ('pos_weight', _vp)]
+
+
 LAMP_OPTIM_ADAM, LAMP_OPTIM_SGD = 0, 1
 BCE_TRAIN_MAX_MATS = 8
 
@@ -234,6 +239,8 @@ PROTOTYPES = {
                                  _vp, _vp, _sz, _vp]),
     'lamp_embed_bwd_ordered': (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i64, _vp, _vp]),
     'lamp_bce_logits_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
+    'lamp_multilabel_loss_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64,
+                                             C.POINTER(LossOptions), _vp]),
     'lamp_optim_step': (C.c_int, [C.POINTER(OptimEntry), _i32, _i32, _i64] + [C.c_double] * 4 + [_vp]),
     'lamp_sdpa_act_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _i32,
                                     C.POINTER(Mask), C.POINTER(AttnLayout), _vp]),
@@ -254,7 +261,8 @@ PROTOTYPES = {
 # symbols -- same-box A/B runs against the previous build (LAMP_HIP_LIBRARY) -- and their callers ask with getattr
 LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs', 'lamp_forward_packs_kv', 'lamp_attn_bias_bwd_workspace_bytes', 'lamp_attn_bias_bwd',
                      'lamp_label_bias_fold', 'lamp_topk_labels', 'lamp_rank_at_k_workspace_bytes', 'lamp_rank_at_k',
-                     'lamp_tune_thresholds_workspace_bytes', 'lamp_tune_thresholds', 'lamp_threshold_counts_vec')
+                     'lamp_tune_thresholds_workspace_bytes', 'lamp_tune_thresholds', 'lamp_threshold_counts_vec',
+                     'lamp_multilabel_loss_train')
 
 _lib = None
 _lock = threading.Lock()
@@ -1113,37 +1121,81 @@ def sigmoid_bce(logits, targets=None, probs_out=None, row_loss_out=None):
     return probs, row_loss
 
 
+def _loss_train_call(who, logits, weights, targets, probs_out, row_loss_out, want_grads, want_probs):
+    """The arguments lamp_bce_logits_train and lamp_multilabel_loss_train share, validated -> (argument tuple up to
+    ld_row_loss, probs, grads, row_loss, keep-alive)."""
+    n = len(logits)
+    if not 1 <= n <= BCE_TRAIN_MAX_MATS or len(weights) != n:
+        raise ValueError('%s takes 1..%d logit matrices and one weight each' % (who, BCE_TRAIN_MAX_MATS))
+    require_device(targets, probs_out, row_loss_out, *logits)
+    B, L = logits[0].shape
+    xs = [f32c(x.detach()) for x in logits]
+    z = f32c(targets)
+    if any(tuple(x.shape) != (B, L) for x in xs) or tuple(z.shape) != (B, L):
+        raise ValueError('%s: every logit matrix and the targets must be (%d, %d)' % (who, B, L))
+    dev = xs[0].device
+    probs = probs_out if probs_out is not None else torch.empty((B, L), dtype=torch.float32, device=dev) if want_probs else None
+    row_loss = row_loss_out if row_loss_out is not None else torch.empty((n, B), dtype=torch.float32, device=dev)
+    if probs is not None and (tuple(probs.shape) != (B, L) or probs.dtype != torch.float32 or (L > 1 and probs.stride(1) != 1) or
+            (B > 1 and probs.stride(0) < L)):
+        raise ValueError('%s: probs_out must be a (%d, %d) fp32 view with unit column stride' % (who, B, L))
+    if (tuple(row_loss.shape) != (n, B) or row_loss.dtype != torch.float32 or (B > 1 and row_loss.stride(1) != 1) or
+            (n > 1 and row_loss.stride(0) < B)):
+        raise ValueError('%s: row_loss_out must be a (%d, %d) fp32 view with unit column stride' % (who, n, B))
+    grads = [torch.empty_like(x) for x in xs] if want_grads else None
+    xp = (_vp * n)(*[x.data_ptr() for x in xs])
+    gp = (_vp * n)(*[g.data_ptr() for g in grads]) if want_grads else None
+    wp = (C.c_float * n)(*[float(w) for w in weights])
+    args = (xp, wp, gp, n, z.data_ptr(), B, L, ptr(probs), probs.stride(0) if probs is not None and B > 1 else L,
+            row_loss.data_ptr(), row_loss.stride(0) if n > 1 else B)
+    return args, probs, grads, row_loss, (xs, z)
+
+
 def bce_logits_train(logits, weights, targets, probs_out=None, row_loss_out=None, want_grads=True, want_probs=True):
     """lamp_bce_logits_train (train.py:37-44 forward and backward in one launch).  logits: the final prediction followed by
     the int_preds intermediates, each (B, L); weights: their loss weights; targets (B, L).
     -> (probs (B, L) = sigmoid(logits[0]) or None, [dlogits_k] or None, row_loss (len(logits), B)).
     probs_out: a (B, L) fp32 view with unit column stride (its row stride may be wider: a block of rows of an epoch-wide
     matrix); row_loss_out: a (len(logits), B) fp32 view with unit column stride."""
-    n = len(logits)
-    if not 1 <= n <= BCE_TRAIN_MAX_MATS or len(weights) != n:
-        raise ValueError('bce_logits_train takes 1..%d logit matrices and one weight each' % BCE_TRAIN_MAX_MATS)
-    require_device(targets, probs_out, row_loss_out, *logits)
-    B, L = logits[0].shape
-    xs = [f32c(x.detach()) for x in logits]
-    z = f32c(targets)
-    if any(tuple(x.shape) != (B, L) for x in xs) or tuple(z.shape) != (B, L):
-        raise ValueError('bce_logits_train: every logit matrix and the targets must be (%d, %d)' % (B, L))
-    dev = xs[0].device
-    probs = probs_out if probs_out is not None else torch.empty((B, L), dtype=torch.float32, device=dev) if want_probs else None
-    row_loss = row_loss_out if row_loss_out is not None else torch.empty((n, B), dtype=torch.float32, device=dev)
-    if probs is not None and (tuple(probs.shape) != (B, L) or probs.dtype != torch.float32 or (L > 1 and probs.stride(1) != 1) or
-            (B > 1 and probs.stride(0) < L)):
-        raise ValueError('bce_logits_train: probs_out must be a (%d, %d) fp32 view with unit column stride' % (B, L))
-    if (tuple(row_loss.shape) != (n, B) or row_loss.dtype != torch.float32 or (B > 1 and row_loss.stride(1) != 1) or
-            (n > 1 and row_loss.stride(0) < B)):
-        raise ValueError('bce_logits_train: row_loss_out must be a (%d, %d) fp32 view with unit column stride' % (n, B))
-    grads = [torch.empty_like(x) for x in xs] if want_grads else None
-    xp = (_vp * n)(*[x.data_ptr() for x in xs])
-    gp = (_vp * n)(*[g.data_ptr() for g in grads]) if want_grads else None
-    wp = (C.c_float * n)(*[float(w) for w in weights])
-    check(lib().lamp_bce_logits_train(xp, wp, gp, n, z.data_ptr(), B, L, ptr(probs), probs.stride(0) if probs is not None and B > 1 else L,
-                                      row_loss.data_ptr(), row_loss.stride(0) if n > 1 else B, stream()),
-          'lamp_bce_logits_train')
+    args, probs, grads, row_loss, _keep = _loss_train_call('bce_logits_train', logits, weights, targets, probs_out, row_loss_out,
+                                                           want_grads, want_probs)
+    check(lib().lamp_bce_logits_train(*args, stream()), 'lamp_bce_logits_train')
+    return probs, grads, row_loss
+
+
+def check_loss_options(gamma_pos=0., gamma_neg=0., clip=0.):
+    """The parameter rules of lamp_multilabel_loss_train (include/lamp_hip.h) as ValueErrors -> the three as Python floats."""
+    out = []
+    for name, g in (('gamma_pos', gamma_pos), ('gamma_neg', gamma_neg)):
+        g = float(g)
+        if not (g == 0.0 or 1.0 <= g <= 16.0):      # (NaN and inf fail both)
+            raise ValueError('%s = %r: a focusing exponent is 0 or lies in [1, 16] (between 0 and 1 the gradient is unbounded '
+                             'at p = 0)' % (name, g))
+        out.append(g)
+    clip = float(clip)
+    if not 0.0 <= clip < 1.0:
+        raise ValueError('clip = %r: the probability margin lies in [0, 1)' % (clip,))
+    return out[0], out[1], clip
+
+
+def multilabel_loss_train(logits, weights, targets, gamma_pos=0., gamma_neg=0., clip=0., pos_weight=None, probs_out=None,
+                          row_loss_out=None, want_grads=True, want_probs=True):
+    """lamp_multilabel_loss_train: bce_logits_train with the objectives of imbalanced label sets (include/lamp_hip.h has the
+    definition): gamma_pos / gamma_neg the focusing exponents (0 or in [1, 16]), clip the probability margin in [0, 1),
+    pos_weight a contiguous fp32 (L,) tensor on the logits' device or None.  Same arguments otherwise, same tuple back; at the
+    defaults the same bits.  A parameter that is not served is a ValueError before the library is called."""
+    gamma_pos, gamma_neg, clip = check_loss_options(gamma_pos, gamma_neg, clip)
+    if pos_weight is not None:
+        L = logits[0].shape[1] if len(logits) else -1
+        if (not torch.is_tensor(pos_weight) or pos_weight.dtype != torch.float32 or tuple(pos_weight.shape) != (L,) or
+                not pos_weight.is_contiguous()):
+            raise ValueError('multilabel_loss_train: pos_weight must be a contiguous fp32 (%d,) tensor' % L)
+        if pos_weight.device != logits[0].device:
+            raise ValueError("multilabel_loss_train: pos_weight must live on the logits' device")
+    args, probs, grads, row_loss, _keep = _loss_train_call('multilabel_loss_train', logits, weights, targets, probs_out,
+                                                           row_loss_out, want_grads, want_probs)
+    opts = LossOptions(gamma_pos, gamma_neg, clip, 0, ptr(pos_weight))
+    check(lib().lamp_multilabel_loss_train(*args, C.byref(opts), stream()), 'lamp_multilabel_loss_train')
     return probs, grads, row_loss
 
 

@@ -6,6 +6,8 @@
 //               loss sum.  One wave per (matrix, row); a lane walks the row in steps of 64 and the 64 partial sums are folded
 //               by wave64_sum, so the order of every sum is a function of L alone: a row's numbers do not depend on the batch
 //               it travels in.  No atomics, no scratch.
+//   multilabel_loss_train  the same launch for the objectives of imbalanced label sets: per-label positive weights, focal
+//               and asymmetric loss, specialised at compile time on "has an exponent" and "has a margin".
 //   optim_step  Adam (torch.optim.Adam's single-tensor arithmetic, no weight decay, no amsgrad) or plain SGD over EVERY
 //               parameter of the model in one launch.  The table of (param, grad, exp_avg, exp_avg_sq, numel) travels in the
 //               kernel arguments (OPTIM_TABLE entries per launch); a workgroup owns one OPTIM_CHUNK-element chunk of one
@@ -59,6 +61,110 @@ __global__ __launch_bounds__(256) void bce_train_kernel(const BceTrainParams p) 
     }
     loss = wave64_sum(loss);
     if (lane == 0 && p.row_loss) p.row_loss[int64_t(k) * p.ld_loss + row] = loss;
+}
+
+// bce_train_kernel's geometry with the loss family of lamp_multilabel_loss_train (include/lamp_hip.h):
+//   l+ = -ns^g+ log s,   l- = -p^g- log(1 - p),  p = max(s - m, 0),   loss = t w l+ + (1 - t) l-.
+// FOCUS: an exponent is set; MARGIN: m > 0.  Neither: per-label positive weights alone, which cost no transcendental beyond
+// BCE's own exp and log1p.  log s and log ns come from x, never from s or ns: finite wherever x is, so that ns log ns is 0
+// where ns has underflowed.  The powers are exp(g log .); with a margin, p has no logarithm at hand and p^g- is
+// p exp((g- - 1) log p), which also is the p^(g- - 1) of the gradient.
+struct LossTrainParams {
+    BceTrainParams b;
+    const float* pos_weight;             // L floats or nullptr
+    float gamma_pos, gamma_neg, clip;
+};
+
+// wave64_sum's pairing on doubles: the same four DPP steps on both halves of the value, then the four row totals.
+template <int CTRL>
+__device__ __forceinline__ double dpp_move_f64(double v) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = unsigned(__builtin_amdgcn_update_dpp(0, int(unsigned(u)), CTRL, 0xF, 0xF, true));
+    const unsigned hi = unsigned(__builtin_amdgcn_update_dpp(0, int(unsigned(u >> 32)), CTRL, 0xF, 0xF, true));
+    return __builtin_bit_cast(double, (unsigned long long)(hi) << 32 | lo);
+}
+__device__ __forceinline__ double readlane_f64(double v, int src) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = unsigned(__builtin_amdgcn_readlane(int(unsigned(u)), src));
+    const unsigned hi = unsigned(__builtin_amdgcn_readlane(int(unsigned(u >> 32)), src));
+    return __builtin_bit_cast(double, (unsigned long long)(hi) << 32 | lo);
+}
+__device__ __forceinline__ double wave64_sum_f64(double v) {
+    v += dpp_move_f64<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += dpp_move_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+    v += dpp_move_f64<0x141>(v);  // row_half_mirror
+    v += dpp_move_f64<0x140>(v);  // row_mirror
+    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+
+template <bool FOCUS, bool MARGIN>
+__global__ __launch_bounds__(256) void multilabel_loss_train_kernel(const LossTrainParams q) {
+    const BceTrainParams& p = q.b;
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t row = int64_t(blockIdx.x) * 4 + (int(threadIdx.x) >> 6);
+    const int k = int(blockIdx.y);
+    if (row >= p.n_rows) return;
+    const float* __restrict__ x_row = p.logits[k] + row * p.L;
+    const float* __restrict__ t_row = p.targets + row * p.L;
+    const float* __restrict__ w_col = q.pos_weight;
+    float* __restrict__ d_row = p.dlogits[k] ? p.dlogits[k] + row * p.L : nullptr;
+    float* __restrict__ p_row = (k == 0 && p.probs) ? p.probs + row * p.ld_probs : nullptr;
+    const float coef = p.coef[k];
+    const float gp = q.gamma_pos, gn = q.gamma_neg, m = q.clip;
+    double loss = 0.0;
+    for (int i = lane; i < p.L; i += 64) {
+        const float x = x_row[i], t = t_row[i];
+        const float w = w_col ? w_col[i] : 1.0f;
+        const float e = expf(-fabsf(x));             // (as bce_train_kernel: the probabilities are its bits)
+        const float r = 1.0f / (1.0f + e);
+        const float small = e * r;
+        if (p_row) p_row[i] = x >= 0.f ? r : small;
+        // the gradient's own larger half: 1 - small carries half an ulp of its own, r the rounding of 1 + e as well.  It
+        // shows next to 1, where the gradient is largest and the tolerance an ulp of it
+        const float big = 1.0f - small;
+        const float s = x >= 0.f ? big : small;
+        const float ns = x >= 0.f ? small : big;
+        const float l1p = log1pf(e);
+        const float ls = fminf(x, 0.f) - l1p;        // log s; a NaN logit is NaN in e, hence in both logs and in l+ below
+        const float lns = -fmaxf(x, 0.f) - l1p;      // log ns
+        float lpos, dpos, lneg, dneg;                // l+, dl+/dx, l-, dl-/dx
+        if (FOCUS) {
+            const float f = gp > 0.f ? expf(gp * lns) : 1.0f;         // ns^g+
+            lpos = -f * ls;
+            dpos = -f * (ns - gp * s * ls);
+        } else {
+            lpos = -ls;
+            dpos = -ns;
+        }
+        if (MARGIN) {
+            const bool on = s > m;                   // off: p = 0, the element is discarded (l- = 0 for every g-)
+            const float pm = s - m;
+            const float omp = ns + m;                // 1 - p
+            const float l1 = log1pf(-pm);            // log(1 - p)
+            float pg = 1.0f, dpg = 0.f;              // p^g-, g- p^(g- - 1)
+            if (FOCUS && gn > 0.f) {
+                const float pgm1 = expf((gn - 1.0f) * logf(pm));
+                pg = pgm1 * pm;
+                dpg = gn * pgm1;
+            }
+            lneg = on ? -pg * l1 : 0.f;
+            dneg = on ? s * ns * (pg / omp - dpg * l1) : 0.f;
+        } else if (FOCUS) {
+            const float g = gn > 0.f ? expf(gn * ls) : 1.0f;          // s^g-
+            lneg = -g * lns;
+            dneg = g * (s - gn * ns * lns);          // s ns (s^g- / ns - g- s^(g- - 1) log ns) without the division by ns
+        } else {
+            lneg = -lns;
+            dneg = s;
+        }
+        // the two branches are mixed, scaled and summed in double and rounded once: t w, the products and (where one branch
+        // is off) the sum are then exact, and a row's sum carries the roundings of its elements, not those of its additions
+        const double tw = double(t) * double(w), nt = 1.0 - double(t);
+        if (d_row) d_row[i] = float(double(coef) * (tw * double(dpos) + nt * double(dneg)));
+        loss += tw * double(lpos) + nt * double(lneg);
+    }
+    loss = wave64_sum_f64(loss);
+    if (lane == 0 && p.row_loss) p.row_loss[int64_t(k) * p.ld_loss + row] = float(loss);
 }
 
 struct OptimEntry {
@@ -227,6 +333,57 @@ int lamp_bce_logits_train(const float* const* logits, const float* weights, floa
     p.L = L;
     p.n_mats = n_mats;
     hipLaunchKernelGGL(bce_train_kernel, dim3(unsigned(blocks), unsigned(n_mats)), dim3(256), 0, hipStream_t(stream), p);
+    return int(hipGetLastError());
+}
+
+static bool loss_exponent_served(float g) { return g == 0.f || (g >= 1.f && g <= 16.f); }   // (false for NaN and inf)
+
+int lamp_multilabel_loss_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
+                               const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
+                               int64_t ld_row_loss, const lamp_loss_options* opts, lamp_stream_t stream) {
+    if (n_rows <= 0 || L <= 0 || n_mats <= 0) return LAMP_E_DIMS;
+    if ((probs && ld_probs < L) || (row_loss && n_mats > 1 && ld_row_loss < n_rows)) return LAMP_E_DIMS;
+    if (!logits || !weights || !targets) return LAMP_E_NULL;
+    for (int k = 0; k < n_mats; ++k)
+        if (!logits[k]) return LAMP_E_NULL;
+    if (n_mats > BCE_MAX_MATS) return LAMP_E_UNSUPPORTED;
+    const int64_t blocks = (n_rows + 3) / 4;
+    if (blocks >= (int64_t(1) << 31)) return LAMP_E_UNSUPPORTED;
+    if (opts) {
+        if (!loss_exponent_served(opts->gamma_pos) || !loss_exponent_served(opts->gamma_neg) ||
+            !(opts->clip >= 0.f && opts->clip < 1.f) || opts->reserved != 0)
+            return LAMP_E_UNSUPPORTED;
+    }
+    const bool focus = opts && (opts->gamma_pos != 0.f || opts->gamma_neg != 0.f);
+    const bool margin = opts && opts->clip != 0.f;
+    if (!focus && !margin && !(opts && opts->pos_weight))      // plain BCE: the kernel it has always been, the same bits
+        return lamp_bce_logits_train(logits, weights, dlogits, n_mats, targets, n_rows, L, probs, ld_probs, row_loss, ld_row_loss,
+                                     stream);
+    LossTrainParams q{};
+    BceTrainParams& p = q.b;
+    const double n_mean = double(n_rows) * double(L);
+    for (int k = 0; k < n_mats; ++k) {
+        p.logits[k] = logits[k];
+        p.dlogits[k] = dlogits ? dlogits[k] : nullptr;
+        p.coef[k] = float(double(weights[k]) / n_mean);
+    }
+    p.targets = targets;
+    p.probs = probs;
+    p.row_loss = row_loss;
+    p.n_rows = n_rows;
+    p.ld_probs = ld_probs;
+    p.ld_loss = ld_row_loss;
+    p.L = L;
+    p.n_mats = n_mats;
+    q.pos_weight = opts->pos_weight;
+    q.gamma_pos = opts->gamma_pos;
+    q.gamma_neg = opts->gamma_neg;
+    q.clip = opts->clip;
+    const dim3 grid = dim3(unsigned(blocks), unsigned(n_mats)), block = dim3(256);
+    if (focus && margin) hipLaunchKernelGGL((multilabel_loss_train_kernel<true, true>), grid, block, 0, hipStream_t(stream), q);
+    else if (focus) hipLaunchKernelGGL((multilabel_loss_train_kernel<true, false>), grid, block, 0, hipStream_t(stream), q);
+    else if (margin) hipLaunchKernelGGL((multilabel_loss_train_kernel<false, true>), grid, block, 0, hipStream_t(stream), q);
+    else hipLaunchKernelGGL((multilabel_loss_train_kernel<false, false>), grid, block, 0, hipStream_t(stream), q);
     return int(hipGetLastError());
 }
 

@@ -116,6 +116,30 @@ def build_label_bias(data, kind, scale, device):
     return label_bias_from_counts(counts, kind, scale).cpu()
 
 
+def label_pos_weight(train_tgt, n_tgt_dict, device, kind='inv', cap=100.0):
+    """The per-label positive weights of -pos_weight (lamp_multilabel_loss_train's pos_weight): a contiguous fp32 (L,) tensor on
+    `device`.  With n train samples and c_j of them carrying label j (a label repeated inside a sample counts once):
+    'inv':      w_j = min(cap, (n - c_j) / max(c_j, 1)), negatives over positives, torch.nn.BCEWithLogitsLoss's documented recipe;
+    'sqrt_inv': w_j = min(cap, sqrt((n - c_j) / max(c_j, 1))).
+    A label without a positive gets `cap`.  Host-side counting, once per run."""
+    if kind not in ('inv', 'sqrt_inv'):
+        raise ValueError("pos_weight kind %r: 'inv' or 'sqrt_inv'" % (kind,))
+    cap = float(cap)
+    if not cap > 0.0 or cap == float('inf'):
+        raise ValueError('pos_weight cap %r: a positive finite number' % (cap,))
+    L = n_tgt_dict - 4
+    n = len(train_tgt)
+    ids, offsets = _label_csr(train_tgt)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(offsets))
+    pairs = np.unique(rows * L + ids) if ids.size else ids       # (sample, label) once each
+    c = np.bincount(pairs % L, minlength=L).astype(np.float64)
+    w = (n - c) / np.maximum(c, 1.0)
+    if kind == 'sqrt_inv':
+        w = np.sqrt(w)
+    w = np.where(c > 0, np.minimum(w, cap), cap)
+    return torch.from_numpy(w.astype(np.float32)).to(device).contiguous()
+
+
 def pad_to_longest(insts):
     """-> (ids int64 (B, T), positions int64 (B, T)); T = longest instance of the batch, PAD = 0, position
     = 1-based index on non-PAD tokens and 0 on PAD (utils/data_loader.py:261-279)."""

@@ -28,6 +28,13 @@ device (lamp_amd/metrics.py: tune_thresholds), reports th
 tuned_ACC .. tuned_maF1 next to the fixed ones in that epoch's record, stores `label_thresholds` (a CPU float32 tensor) and
 `tune_criterion` in the checkpoint beside model / settings / epoch (run_eval -tune_thresholds checkpoint reads them) and adds
 .thr_<criterion> to the results name.
+
+-loss_fn focal|asl and -pos_weight inv|sqrt_inv change the TRAINED objective (focal loss, asymmetric loss, per-label positive
+weights from the train split's counts), still in the one loss launch per batch.  The train column of
+losses.csv and train_loss are then that objective; the valid and test losses stay plain BCE, so -save_mode best and runs with
+different objectives stay comparable.  They add .lossfn_<kind>_<parameters> / .posw_<kind>_<cap> to the results name and
+their flags to the checkpoint's settings, and nothing when they are not given.  (-loss is the reference's flag, parsed and,
+as there, unused.)
 """
 import argparse
 import json
@@ -98,6 +105,21 @@ def parse(argv=None):
                     help="after each validation epoch fit one decision threshold per label on the valid predictions (lamp_amd/"
                          "metrics.py: tune_thresholds), report the test epoch's tuned_* figures and store label_thresholds / "
                          "tune_criterion in the checkpoint for run_eval -tune_thresholds checkpoint")
+    ap.add_argument('-loss_fn', type=str, choices=['bce', 'focal', 'asl'], default='bce',
+                    help="the TRAINED objective (lamp_multilabel_loss_train, DESIGN.md section 8.10): focal = -focal_gamma on both "
+                         "branches, asl = the asymmetric loss of -asl_gamma_pos / -asl_gamma_neg / -asl_clip.  Only the training "
+                         "loss changes: the valid and test losses stay plain BCE, so -save_mode best and runs with different "
+                         "objectives stay comparable; the train column of losses.csv is the trained loss")
+    ap.add_argument('-focal_gamma', type=float, default=2.0, help='focal loss: the focusing exponent (0, or 1 .. 16)')
+    ap.add_argument('-asl_gamma_pos', type=float, default=0.0, help='asymmetric loss: the exponent of the positives')
+    ap.add_argument('-asl_gamma_neg', type=float, default=4.0, help='asymmetric loss: the exponent of the negatives')
+    ap.add_argument('-asl_clip', type=float, default=0.05,
+                    help='asymmetric loss: the probability margin in [0, 1); a negative predicted below it is discarded')
+    ap.add_argument('-pos_weight', type=str, choices=['none', 'inv', 'sqrt_inv'], default='none',
+                    help="per-label weights of the positives in the TRAINED loss, from the train split's label counts "
+                         "(lamp_amd/data.py: label_pos_weight): inv = negatives / positives, sqrt_inv = its square root; "
+                         "combines with every -loss_fn; the valid and test losses stay plain BCE")
+    ap.add_argument('-pos_weight_cap', type=float, default=100.0, help='the largest weight, also given to a label without a positive')
     ap.add_argument('-optim_impl', choices=['lamp', 'torch'], default=DEFAULT_OPTIM_IMPL,
                     help='lamp = lamp_amd.optim (one lamp_optim_step launch per step); torch = torch.optim (fused=True for adam)')
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4], help='batches in flight in the valid / test epochs')
@@ -111,6 +133,32 @@ def parse(argv=None):
 # torch's fused Adam: lamp_optim_step has not been shown to beat it same-box (nothing is measured yet; tools/bench_train_epoch.py
 # is the tool that would), and without a measured win the default stays torch's
 DEFAULT_OPTIM_IMPL = 'torch'
+
+
+# -loss_fn -> the flags that parameterise it (they enter the results name and the checkpoint's settings only with it)
+LOSS_FN_FLAGS = {'bce': (), 'focal': ('focal_gamma',), 'asl': ('asl_gamma_pos', 'asl_gamma_neg', 'asl_clip')}
+
+
+def loss_parameters(opt):
+    """-loss_fn and its flags -> (gamma_pos, gamma_neg, clip) of lamp_multilabel_loss_train; ValueError for what it refuses."""
+    from . import _native as N
+    if opt.loss_fn == 'focal':
+        return N.check_loss_options(opt.focal_gamma, opt.focal_gamma, 0.0)
+    if opt.loss_fn == 'asl':
+        return N.check_loss_options(opt.asl_gamma_pos, opt.asl_gamma_neg, opt.asl_clip)
+    return N.check_loss_options()
+
+
+def build_loss_options(opt, data, device):
+    """-> the train.LossOptions of -loss_fn / -pos_weight (the weights from the TRAIN split's label counts), or None for plain
+    BCE: train_batch then makes the call it has always made."""
+    if opt.loss_fn == 'bce' and opt.pos_weight == 'none':
+        return None
+    from .train import LossOptions
+    w = None
+    if opt.pos_weight != 'none':
+        w = D.label_pos_weight(data['train']['tgt'], len(data['dict']['tgt']), device, opt.pos_weight, opt.pos_weight_cap)
+    return LossOptions(*loss_parameters(opt), pos_weight=w)
 
 
 def derive(opt):
@@ -181,6 +229,22 @@ def derive(opt):
     opt.tune_thresholds = getattr(opt, 'tune_thresholds', None) or None
     if opt.tune_thresholds:
         name += '.thr_' + opt.tune_thresholds
+    opt.loss_fn = getattr(opt, 'loss_fn', None) or 'bce'
+    if opt.loss_fn not in LOSS_FN_FLAGS:
+        raise ValueError("-loss_fn %r: one of %s" % (opt.loss_fn, ', '.join(sorted(LOSS_FN_FLAGS))))
+    for flag, default in (('focal_gamma', 2.0), ('asl_gamma_pos', 0.0), ('asl_gamma_neg', 4.0), ('asl_clip', 0.05),
+                          ('pos_weight_cap', 100.0)):
+        setattr(opt, flag, float(getattr(opt, flag, default)))
+    opt.pos_weight = getattr(opt, 'pos_weight', None) or 'none'
+    if opt.pos_weight not in ('none', 'inv', 'sqrt_inv'):
+        raise ValueError("-pos_weight %r: none, inv or sqrt_inv" % (opt.pos_weight,))
+    if opt.loss_fn != 'bce':
+        loss_parameters(opt)    # (refuses what the kernel does not serve, here and not in the first batch)
+        name += '.lossfn_%s_%s' % (opt.loss_fn, '_'.join(str(getattr(opt, f)) for f in LOSS_FN_FLAGS[opt.loss_fn]))
+    if opt.pos_weight != 'none':
+        if not 0.0 < opt.pos_weight_cap < float('inf'):
+            raise ValueError('-pos_weight_cap %r: a positive finite number' % (opt.pos_weight_cap,))
+        name += '.posw_%s_%s' % (opt.pos_weight, opt.pos_weight_cap)
     if opt.name:
         name += '.' + str(opt.name)
     opt.model_name = os.path.join(opt.results_dir, opt.dataset, name)
@@ -235,9 +299,18 @@ def build_optimizer(model, opt):
 def checkpoint_settings(opt):
     """The Namespace that travels in the checkpoint: plain values only, so that it unpickles anywhere.  `learn_label_bias`
     and `tune_thresholds` travel only when they are set: without the flags the settings are what they were before they
-    existed."""
+    existed.  Likewise `loss_fn` with the flags of the chosen objective, and `pos_weight` with its cap."""
+    drop = {'loss_options'}      # (the run's device-side object, None for plain BCE: never a setting)
+    loss_fn = getattr(opt, 'loss_fn', 'bce')
+    if loss_fn == 'bce':
+        drop.add('loss_fn')
+    for fn, flags in LOSS_FN_FLAGS.items():
+        if fn != loss_fn:
+            drop.update(flags)
+    if getattr(opt, 'pos_weight', 'none') == 'none':
+        drop.update(('pos_weight', 'pos_weight_cap'))
     return argparse.Namespace(**{k: v for k, v in vars(opt).items() if isinstance(v, (bool, int, float, str, type(None)))
-                                 and (k not in ('learn_label_bias', 'tune_thresholds') or v)})
+                                 and (k not in ('learn_label_bias', 'tune_thresholds') or v) and k not in drop})
 
 
 def save_model(opt, epoch_i, model, valid_loss, valid_losses, label_thresholds=None):
@@ -280,6 +353,7 @@ def main(argv=None):
     opt.total_num_parameters = int(sum(p.numel() for p in model.parameters() if p.requires_grad))
     model = model.to(device)       # (before the optimizer: torch's fused Adam wants device parameters at construction)
     optimizer = build_optimizer(model, opt)
+    opt.loss_options = build_loss_options(opt, data, device)      # (None for plain BCE; never part of the checkpoint's settings)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=opt.lr_step_size, gamma=opt.lr_decay, last_epoch=-1)

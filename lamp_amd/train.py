@@ -7,7 +7,9 @@ twice as many with -int_preds), and torch's multi-tensor Adam (:48).  Here, symm
     pinned ring while the device trains on the previous stage; a stage goes up with one asynchronous copy per buffer;
   * per batch: zero_grad, `model.train()` forward (lamp_amd/training.py), ONE lamp_bce_logits_train launch -- the batch's rows
     of the epoch's device prediction matrix, d loss / d logits of the final prediction and of every int_preds intermediate,
-    and the per-row loss sums -- then torch.autograd.backward from those gradients and optimizer.step();
+    and the per-row loss sums -- then torch.autograd.backward from those gradients and optimizer.step(); with
+    `opt.loss_options` (LossOptions: per-label positive weights, focal or asymmetric loss) that launch is
+    lamp_multilabel_loss_train, still one;
   * the embedding gradient takes lamp_embed_bwd_ordered (one writer per table row instead of the atomic scatter-add; switched
     on for the epoch through training.ORDERED_EMBED_GRAD), so an epoch is reproducible bit for bit;
   * nothing comes back to the host inside the loop: no `.item()`, no copy, no synchronize.  Predictions and row sums come
@@ -100,13 +102,26 @@ class TrainBatcher(object):
             self.shuffle()
 
 
+class LossOptions(object):
+    """`opt.loss_options`: the trained objective when it is not plain BCE (lamp_multilabel_loss_train):
+    the focusing exponents, the probability margin and the per-label positive weights (a contiguous fp32 (L,) DEVICE tensor or
+    None).  Focal loss is gamma_pos = gamma_neg; the published asymmetric loss is (0, 4, 0.05).  Parameters that are not
+    served are refused here, not in the first batch."""
+
+    def __init__(self, gamma_pos=0.0, gamma_neg=0.0, clip=0.0, pos_weight=None):
+        self.gamma_pos, self.gamma_neg, self.clip = N.check_loss_options(gamma_pos, gamma_neg, clip)
+        self.pos_weight = pos_weight
+
+
 def _loss_weights(n_mats, int_pred_weight):
     return [1.0] + [float(int_pred_weight)] * (n_mats - 1)
 
 
 def train_batch(model, optimizer, opt, src, adj, gold_d, probs_rows, loss_rows):
     """The loop body (train.py:35-48) for one batch already on the device.  probs_rows (real, L) / loss_rows (n_mats, real):
-    this batch's rows of the epoch's prediction matrix and loss-sum matrix.  Nothing here waits for the device."""
+    this batch's rows of the epoch's prediction matrix and loss-sum matrix.  `opt.loss_options` (a LossOptions, or absent / None
+    for the reference's BCE) picks the trained objective: the loss launch is then lamp_multilabel_loss_train and the row sums
+    are that loss.  Nothing here waits for the device."""
     optimizer.zero_grad()
     pred, enc_output, *results = model(src, adj, None, gold_d, return_attns=opt.attns_loss, int_preds=opt.int_preds)
     mats = [pred]
@@ -118,9 +133,16 @@ def train_batch(model, optimizer, opt, src, adj, gold_d, probs_rows, loss_rows):
     weights = _loss_weights(len(mats), getattr(opt, 'int_pred_weight', 0.2))
     grads = []
     M = N.BCE_TRAIN_MAX_MATS
+    lo = getattr(opt, 'loss_options', None)
     for k in range(0, len(mats), M):   # (more than 8 matrices: 5+ decoder layers with -int_preds)
-        _, g, _ = N.bce_logits_train(mats[k:k + M], weights[k:k + M], gold_d, probs_out=probs_rows if k == 0 else None,
-                                     row_loss_out=loss_rows[k:k + M], want_probs=k == 0)
+        if lo is None:
+            _, g, _ = N.bce_logits_train(mats[k:k + M], weights[k:k + M], gold_d, probs_out=probs_rows if k == 0 else None,
+                                         row_loss_out=loss_rows[k:k + M], want_probs=k == 0)
+        else:
+            _, g, _ = N.multilabel_loss_train(mats[k:k + M], weights[k:k + M], gold_d, gamma_pos=lo.gamma_pos,
+                                              gamma_neg=lo.gamma_neg, clip=lo.clip, pos_weight=lo.pos_weight,
+                                              probs_out=probs_rows if k == 0 else None, row_loss_out=loss_rows[k:k + M],
+                                              want_probs=k == 0)
         grads += g
     torch.autograd.backward(mats, grads)
     optimizer.step()
@@ -138,7 +160,8 @@ def train_epoch(model, train_data, optimizer, opt, device=None, prefetch=8, stre
 
     `train_data` yields ((src_seq, src_pos), adj, tgt) batches of at most `train_data._batch_size` rows (TrainBatcher, or any
     iterable with `n_insts`, `__len__` and `_batch_size`); `opt` carries what the reference's loop reads: tgt_vocab_size,
-    binary_relevance, int_preds, int_pred_weight, attns_loss (only changes return_attns, as in the reference), decoder.
+    binary_relevance, int_preds, int_pred_weight, attns_loss (only changes return_attns, as in the reference), decoder, and
+    optionally `loss_options` (LossOptions): the third return value and 'row_loss' are then the TRAINED loss, not BCE.
     `prefetch` = batches per stage of the producer thread (evaluate.py); `streams=2` issues the stage uploads on a stream of
     their own instead of in front of the stage's first forward.  Every batch's numbers are the same in every mode, bit for bit.
     `timeline` / `device_results` as in evaluate.test_epoch: 'probs' and 'targets' (n, L) stay on the device for
