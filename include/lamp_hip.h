@@ -971,6 +971,61 @@ typedef struct lamp_optim_entry {
 int lamp_optim_step(const lamp_optim_entry* entries, int32_t n, int32_t kind, int64_t step, double lr, double beta1,
                     double beta2, double eps, lamp_stream_t stream);
 
+/* The global L2 norm of every gradient of a table (entries[i].grad / .numel; the other members are not read), for gradient
+ * clipping and for the decision "is this batch's gradient finite" taken on the device.  Deterministic, no atomics:
+ *   stage 1  one workgroup per 4096-element chunk of an entry (lamp_optim_step's chunking).  Every element is squared and
+ *            added in fp64 -- the square of an fp32 number is exact there, nothing overflows below |g| = 3.4e38 and nothing
+ *            underflows -- lanes and waves are folded in a fixed order, and the workgroup writes one double into `workspace`.
+ *            72 entries per launch; a longer table takes several launches.
+ *   stage 2  ONE workgroup, whatever the table's length: lane t adds partials t, t + 256, ... in ascending order, lanes and
+ *            waves fold as in stage 1, and one lane writes the 4-float DEVICE record
+ *              grad_state = { norm, scale, finite, 0 }:   norm = float(sqrt(sum));
+ *              scale = min(1, max_norm * (1 / (norm + 1e-6))) in fp32, torch.nn.utils.clip_grad_norm_'s own expression
+ *                      (its `max_norm / tensor` is reciprocal().mul()); 1 when max_norm < 0 (LAMP_GRAD_NORM_NO_CLIP); a NaN
+ *                      norm gives a NaN scale, an infinite one 0, as in torch;
+ *              finite = 1.0f when norm is finite, else 0.0f.
+ *            skipped (device int32, may be NULL): incremented by one when finite == 0.
+ * The record is bit-identical from run to run on the same table; it depends on the order of the entries and on their
+ * alignment (16-byte aligned gradients are read four at a time) in the last bits of the fp64 sum, far below one fp32 ulp.
+ * Zero-numel entries are skipped; gradients are 4-byte aligned.  lamp_grad_norm_workspace_bytes() is exact: 8 bytes per
+ * chunk (0 for a table it refuses).  Validated before any launch: LAMP_E_DIMS (n < 0, a negative numel), LAMP_E_NULL
+ * (entries, grad_state, a gradient, the workspace), LAMP_E_UNSUPPORTED (a NaN max_norm, 2^31 chunks), LAMP_E_ALIGN,
+ * LAMP_E_WORKSPACE (a workspace smaller than the query's answer). */
+#define LAMP_GRAD_NORM_NO_CLIP (-1.0)
+size_t lamp_grad_norm_workspace_bytes(const lamp_optim_entry* entries, int32_t n);
+int lamp_grad_norm(const lamp_optim_entry* entries, int32_t n, double max_norm, void* workspace, size_t workspace_bytes,
+                   float* grad_state, int32_t* skipped, lamp_stream_t stream);
+
+/* lamp_optim_step with the training-loop controls of a Transformer-style model, still one launch per 72 entries.  ext NULL,
+ * or an ext that asks for nothing, IS lamp_optim_step (the same kernel, the same bits).  Per element, in this order:
+ *   grad_state (DEVICE, the record of lamp_grad_norm; NULL = no clipping): g = g * scale, rounded as torch's in-place mul_
+ *     (no contraction).  The gradient buffer is read once and NOT rewritten.
+ *   entry_weight_decay (HOST array of n floats >= 0, NULL = 0 everywhere; it travels in the kernel arguments):
+ *     flag unset: g = g + wd * w, before the moments (torch's weight_decay);  LAMP_OPTIM_DECOUPLED_DECAY (Adam only):
+ *     w = w * (1 - lr * wd) before the update, the factor taken in double on the host (torch.optim.AdamW).  An entry with
+ *     decay 0 takes exactly lamp_optim_step's arithmetic (an infinite weight stays what it is), so biases, LayerNorm
+ *     parameters and a label bias with -inf entries share the launch.
+ *   momentum (LAMP_OPTIM_SGD only, in [0, 1)): buf = momentum * buf + g; w = w - lr * buf, the buffer in the entry's exp_avg
+ *     slot.  A zero buffer on the first step is torch's "first step copies the gradient".  No nesterov, no dampening.
+ *   LAMP_OPTIM_SKIP_NONFINITE (needs grad_state): when the record's finite is 0 the launch writes NOTHING -- parameters and
+ *     moments keep their bits.  Without the flag a non-finite norm does what torch's arithmetic does: the scale is NaN (or 0
+ *     against an infinite gradient) and NaN spreads into every parameter and moment of the table.
+ * `step` is the caller's count; a skipped launch does not know it was skipped.  Refused before any launch: LAMP_E_DIMS
+ * (n < 0, numel < 0, Adam with step < 1), LAMP_E_UNSUPPORTED (unknown kind or flag bits, reserved != 0, momentum outside
+ * [0, 1) or with Adam, decoupled decay with SGD, a skip without grad_state, a negative or non-finite decay), LAMP_E_NULL,
+ * LAMP_E_ALIGN. */
+#define LAMP_OPTIM_DECOUPLED_DECAY 1
+#define LAMP_OPTIM_SKIP_NONFINITE 2
+typedef struct lamp_optim_ext {
+    const float* entry_weight_decay;   /* HOST, n floats, or NULL */
+    const float* grad_state;           /* DEVICE, 4 floats, or NULL */
+    double momentum;
+    int32_t flags;
+    int32_t reserved;                  /* 0 */
+} lamp_optim_ext;
+int lamp_optim_step_ext(const lamp_optim_entry* entries, int32_t n, int32_t kind, int64_t step, double lr, double beta1,
+                        double beta2, double eps, const lamp_optim_ext* ext, lamp_stream_t stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline) ------ */
 enum lamp_kernel_class {
     LAMP_K_EMBED = 0, LAMP_K_GEMM = 1, LAMP_K_ATTN = 2, LAMP_K_LAYERNORM = 3, LAMP_K_DIAG = 4,

@@ -142,12 +142,19 @@ class OptimEntry(C.Structure):  # include/lamp_hip.h: lamp_optim_entry
     _fields_ = [('param', _vp), ('grad', _vp), ('exp_avg', _vp), ('exp_avg_sq', _vp), ('numel', C.c_int64)]
 
 
+class OptimExt(C.Structure):  # include/lamp_hip.h: lamp_optim_ext
+    _fields_ = [('entry_weight_decay', C.POINTER(C.c_float)), ('grad_state', _vp), ('momentum', C.c_double),
+                ('flags', C.c_int32), ('reserved', C.c_int32)]
+
+
 class LossOptions(C.Structure):  # include/lamp_hip.h: lamp_loss_options
     _fields_ = [('gamma_pos', C.c_float), ('gamma_neg', C.c_float), ('clip', C.c_float), ('reserved', C.c_int32),
                 ('pos_weight', _vp)]
 
 
 LAMP_OPTIM_ADAM, LAMP_OPTIM_SGD = 0, 1
+LAMP_OPTIM_DECOUPLED_DECAY, LAMP_OPTIM_SKIP_NONFINITE = 1, 2   # lamp_optim_ext.flags
+LAMP_GRAD_NORM_NO_CLIP = -1.0
 BCE_TRAIN_MAX_MATS = 8
 
 
@@ -242,6 +249,9 @@ PROTOTYPES = {
     'lamp_multilabel_loss_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64,
                                              C.POINTER(LossOptions), _vp]),
     'lamp_optim_step': (C.c_int, [C.POINTER(OptimEntry), _i32, _i32, _i64] + [C.c_double] * 4 + [_vp]),
+    'lamp_grad_norm_workspace_bytes': (_sz, [C.POINTER(OptimEntry), _i32]),
+    'lamp_grad_norm': (C.c_int, [C.POINTER(OptimEntry), _i32, C.c_double, _vp, _sz, _vp, _vp, _vp]),
+    'lamp_optim_step_ext': (C.c_int, [C.POINTER(OptimEntry), _i32, _i32, _i64] + [C.c_double] * 4 + [C.POINTER(OptimExt), _vp]),
     'lamp_sdpa_act_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _i32,
                                     C.POINTER(Mask), C.POINTER(AttnLayout), _vp]),
     'lamp_mha_act_fwd': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(MhaWeights), _i32,
@@ -262,7 +272,7 @@ PROTOTYPES = {
 LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs', 'lamp_forward_packs_kv', 'lamp_attn_bias_bwd_workspace_bytes', 'lamp_attn_bias_bwd',
                      'lamp_label_bias_fold', 'lamp_topk_labels', 'lamp_rank_at_k_workspace_bytes', 'lamp_rank_at_k',
                      'lamp_tune_thresholds_workspace_bytes', 'lamp_tune_thresholds', 'lamp_threshold_counts_vec',
-                     'lamp_multilabel_loss_train')
+                     'lamp_multilabel_loss_train', 'lamp_grad_norm_workspace_bytes', 'lamp_grad_norm', 'lamp_optim_step_ext')
 
 _lib = None
 _lock = threading.Lock()
@@ -1213,6 +1223,70 @@ def optim_step(entries, kind, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
             e.exp_avg, e.exp_avg_sq = m.data_ptr(), v.data_ptr()
     check(lib().lamp_optim_step(arr, n, int(kind), int(step), float(lr), float(beta1), float(beta2), float(eps), stream()),
           'lamp_optim_step')
+
+
+def _optim_table(entries):
+    n = len(entries)
+    arr = (OptimEntry * n)()
+    for i, (p, g, m, v) in enumerate(entries):
+        e = arr[i]
+        e.param, e.grad, e.numel = ptr(p), g.data_ptr(), g.numel()
+        if m is not None:
+            e.exp_avg = m.data_ptr()
+        if v is not None:
+            e.exp_avg_sq = v.data_ptr()
+    return arr
+
+
+_norm_ws = {}    # device index -> the stage-1 partials of lamp_grad_norm (uint8; regrown only when the size query grows)
+
+
+def grad_norm_workspace(nbytes, device):
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    buf = _norm_ws.get(idx)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+        _norm_ws[idx] = buf
+    return buf
+
+
+def grad_norm(entries, max_norm, grad_state, skipped=None):
+    """lamp_grad_norm over [(param or None, grad, ...)] (optim_step's table; only the gradients are read): the global L2 norm
+    of every gradient, accumulated in fp64, as the device record grad_state = (norm, scale, finite, 0), a contiguous fp32 (4,)
+    tensor on the gradients' device.  max_norm None: scale = 1.  skipped: an int32 device tensor that is incremented when the
+    norm is not finite, or None.  The partials live in one cached buffer per device; nothing is allocated per call and nothing
+    is read back."""
+    if (grad_state.dtype != torch.float32 or grad_state.numel() != 4 or not grad_state.is_contiguous() or
+            (skipped is not None and (skipped.dtype != torch.int32 or skipped.numel() != 1))):
+        raise ValueError('grad_norm: grad_state is a contiguous fp32 (4,) tensor, skipped an int32 tensor of one element')
+    require_device(grad_state, skipped)
+    n = len(entries)
+    arr = _optim_table(entries)
+    L = lib()
+    nbytes = L.lamp_grad_norm_workspace_bytes(arr, n)
+    ws = grad_norm_workspace(nbytes, grad_state.device)
+    check(L.lamp_grad_norm(arr, n, LAMP_GRAD_NORM_NO_CLIP if max_norm is None else float(max_norm), ptr(ws), ws.numel(),
+                           ptr(grad_state), ptr(skipped), stream()), 'lamp_grad_norm')
+    return grad_state
+
+
+def optim_step_ext(entries, kind, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=None, decoupled=False,
+                   momentum=0.0, grad_state=None, skip_nonfinite=False):
+    """lamp_optim_step_ext: optim_step with weight_decay (one float per entry, or None), decoupled (AdamW's form of it),
+    momentum (SGD; the buffer is the entry's third tensor), grad_state (the device record of grad_norm: the gradients are
+    used as g * scale) and skip_nonfinite (write nothing when the record says the norm is not finite).  With nothing asked
+    for it is optim_step, bit for bit."""
+    n = len(entries)
+    if n == 0:
+        return
+    if weight_decay is not None and len(weight_decay) != n:
+        raise ValueError('optim_step_ext: one weight decay per entry')
+    arr = _optim_table(entries)
+    wd = (C.c_float * n)(*[float(w) for w in weight_decay]) if weight_decay is not None else None
+    ext = OptimExt(wd, ptr(grad_state), float(momentum), (LAMP_OPTIM_DECOUPLED_DECAY if decoupled else 0) |
+                   (LAMP_OPTIM_SKIP_NONFINITE if skip_nonfinite else 0), 0)
+    check(lib().lamp_optim_step_ext(arr, n, int(kind), int(step), float(lr), float(beta1), float(beta2), float(eps),
+                                    C.byref(ext), stream()), 'lamp_optim_step_ext')
 
 
 # ------------------------------------------------------------------ profiling

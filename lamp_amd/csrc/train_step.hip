@@ -13,6 +13,10 @@
 //               kernel arguments (OPTIM_TABLE entries per launch); a workgroup owns one OPTIM_CHUNK-element chunk of one
 //               tensor, found by a binary search over the table's running chunk counts.  16-byte accesses when all four
 //               pointers allow it, the chunk's last numel % 4 elements by single lanes; 4-byte accesses otherwise.
+//   grad_norm   the global L2 norm of a table's gradients in fp64, one partial per chunk and one closing workgroup: the device
+//               record {norm, scale, finite, 0} that optim_step_ext reads.  No atomics.
+//   optim_step_ext  optim_step behind gradient clipping (the record's scale, applied in registers), per-entry weight decay
+//               (L2 or decoupled), SGD momentum, and "write nothing when the norm is not finite".  optim_step is untouched.
 //   embed_bwd_ordered  the embedding scatter-add without atomics (see the kernel), so that an epoch is reproducible.
 // All are enqueued on the caller's stream; neither allocates, synchronises or reads anything back.
 #include "lamp_kernels.h"
@@ -302,6 +306,189 @@ __global__ __launch_bounds__(256) void embed_bwd_ordered_kernel(const int64_t* _
     }
 }
 
+// ---- lamp_grad_norm: the global L2 norm of every gradient of a table, in two stages, without atomics ----
+// Stage 1 has optim_step_kernel's geometry: one workgroup per OPTIM_CHUNK of one entry.  A lane squares its elements in
+// double (the square of an fp32 number is exact there: no overflow below 3.4e38, no underflow) and adds them in the order
+// it walks them; the 64 lanes of a wave fold by wave64_sum_f64, the four waves as (w0 + w1) + (w2 + w3); one double per
+// workgroup goes to partial[blockIdx.x].
+struct NormParams {
+    const float* grad[OPTIM_TABLE];
+    int64_t numel[OPTIM_TABLE];
+    int32_t chunk_start[OPTIM_TABLE + 1];
+    int32_t n;
+    double* partial;     // this launch's first partial
+};
+
+__device__ __forceinline__ double block256_sum_f64(double acc, double* red) {
+    acc = wave64_sum_f64(acc);
+    const int tid = int(threadIdx.x);
+    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const NormParams p) {
+    __shared__ double red[4];
+    const int b = int(blockIdx.x);
+    int lo = 0, hi = p.n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (p.chunk_start[mid] <= b) lo = mid; else hi = mid;
+    }
+    const int64_t off = int64_t(b - p.chunk_start[lo]) * OPTIM_CHUNK;
+    const int64_t left = p.numel[lo] - off;
+    const int n = left < OPTIM_CHUNK ? int(left) : OPTIM_CHUNK;
+    const float* __restrict__ g = p.grad[lo] + off;
+    const int tid = int(threadIdx.x);
+    double acc = 0.0;
+    if ((reinterpret_cast<uintptr_t>(g) & 15u) == 0) {
+        const int nq = n >> 2;
+        for (int q = tid; q < nq; q += 256) {
+            const float4 g4 = reinterpret_cast<const float4*>(g)[q];
+            acc += double(g4.x) * double(g4.x);
+            acc += double(g4.y) * double(g4.y);
+            acc += double(g4.z) * double(g4.z);
+            acc += double(g4.w) * double(g4.w);
+        }
+        const int i = (nq << 2) + tid;
+        if (i < n) acc += double(g[i]) * double(g[i]);
+    } else {
+        for (int i = tid; i < n; i += 256) acc += double(g[i]) * double(g[i]);
+    }
+    const double total = block256_sum_f64(acc, red);
+    if (tid == 0) p.partial[b] = total;
+}
+
+// Stage 2, one workgroup: lane t adds partials t, t + 256, ... in ascending order, lanes and waves fold as in stage 1, and
+// lane 0 writes the record {norm, scale, finite, 0}.  scale is clip_grad_norm_'s own fp32 expression,
+// clamp(max_norm * reciprocal(norm + 1e-6), max=1) -- `max_norm / tensor` is reciprocal().mul() in torch -- and keeps a NaN.
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const double* __restrict__ partial, int64_t n_partials,
+                                                              float max_norm, int clip, float* __restrict__ grad_state,
+                                                              int32_t* __restrict__ skipped) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    const int tid = int(threadIdx.x);
+    double acc = 0.0;
+    for (int64_t i = tid; i < n_partials; i += 256) acc += partial[i];
+    const double total = block256_sum_f64(acc, red);
+    if (tid == 0) {
+        const float norm = float(sqrt(total));
+        float scale = 1.0f;
+        if (clip) {
+            const float coef = (1.0f / (norm + 1e-6f)) * max_norm;
+            scale = coef > 1.0f ? 1.0f : coef;
+        }
+        const bool finite = fabsf(norm) <= 3.402823466e38f;      // (false for inf and NaN)
+        grad_state[0] = norm;
+        grad_state[1] = scale;
+        grad_state[2] = finite ? 1.0f : 0.0f;
+        grad_state[3] = 0.0f;
+        if (skipped && !finite) skipped[0] = skipped[0] + 1;
+    }
+}
+
+// ---- lamp_optim_step_ext: optim_step_kernel's geometry and arithmetic behind the clip factor, weight decay and momentum ----
+enum { OPT_ADAM = 0, OPT_SGD = 1, OPT_SGD_MOMENTUM = 2 };
+enum { DECAY_NONE = 0, DECAY_L2 = 1, DECAY_DECOUPLED = 2 };
+
+struct OptimExtParams {
+    OptimParams o;
+    float decay[OPTIM_TABLE];     // per entry: weight_decay (L2 form) or float(1 - lr * weight_decay) (decoupled form)
+    const float* grad_state;      // {norm, scale, finite, 0} of lamp_grad_norm, or nullptr
+    float momentum;
+    int32_t decay_mode;           // DECAY_L2 / DECAY_DECOUPLED: what `decay` holds (an entry with weight_decay 0 takes neither)
+    int32_t skip_nonfinite;
+};
+
+struct OptimExtStep {             // what is uniform over a workgroup
+    float scale, decay, momentum;
+    bool clip;
+    int decay_mode;
+};
+
+template <int KIND>
+__device__ __forceinline__ void optim_update_ext(float& w, float g, float& m, float& v, const OptimParams& p, const OptimExtStep& s) {
+#pragma clang fp contract(off)
+    if (s.clip) g = g * s.scale;                             // clip_grad_norm_'s grad.mul_(clip_coef), kept in a register
+    if (s.decay_mode == DECAY_L2) g = g + s.decay * w;       // grad.add(param, alpha=weight_decay)
+    else if (s.decay_mode == DECAY_DECOUPLED) w = w * s.decay;   // param.mul_(1 - lr * weight_decay)
+    if (KIND == OPT_SGD_MOMENTUM) {
+        m = s.momentum * m + g;                              // buf.mul_(momentum).add_(grad)
+        w = w - p.lr * m;                                    // param.add_(buf, alpha=-lr)
+    } else {
+        optim_update<KIND == OPT_ADAM>(w, g, m, v, p);
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_step_ext_kernel(const OptimExtParams x) {
+    constexpr bool HAS_M = KIND != OPT_SGD, HAS_V = KIND == OPT_ADAM;
+    const OptimParams& p = x.o;
+    OptimExtStep s;
+    s.clip = x.grad_state != nullptr;
+    s.scale = 1.0f;
+    if (s.clip) {
+        if (x.skip_nonfinite && x.grad_state[2] == 0.0f) return;     // a non-finite norm: this launch writes nothing
+        s.scale = x.grad_state[1];
+    }
+    s.momentum = x.momentum;
+    const int b = int(blockIdx.x);
+    int lo = 0, hi = p.n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (p.chunk_start[mid] <= b) lo = mid; else hi = mid;
+    }
+    const OptimEntry& t = p.e[lo];
+    s.decay = x.decay[lo];
+    // an entry without decay takes exactly optim_step_kernel's arithmetic: 0 * w would turn an infinite weight into NaN
+    s.decay_mode = (x.decay_mode == DECAY_L2 && s.decay != 0.0f) || (x.decay_mode == DECAY_DECOUPLED && s.decay != 1.0f)
+                       ? x.decay_mode : DECAY_NONE;
+    const int64_t off = int64_t(b - p.chunk_start[lo]) * OPTIM_CHUNK;
+    const int64_t left = t.numel - off;
+    const int n = left < OPTIM_CHUNK ? int(left) : OPTIM_CHUNK;
+    float* __restrict__ w = t.param + off;
+    const float* __restrict__ g = t.grad + off;
+    float* __restrict__ m = HAS_M ? t.exp_avg + off : nullptr;
+    float* __restrict__ v = HAS_V ? t.exp_avg_sq + off : nullptr;
+    const int tid = int(threadIdx.x);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) |
+                           (HAS_M ? reinterpret_cast<uintptr_t>(m) : uintptr_t(0)) |
+                           (HAS_V ? reinterpret_cast<uintptr_t>(v) : uintptr_t(0));
+    if ((bits & 15u) == 0) {
+        const int nq = n >> 2;
+        for (int q = tid; q < nq; q += 256) {
+            float4 w4 = reinterpret_cast<float4*>(w)[q];
+            const float4 g4 = reinterpret_cast<const float4*>(g)[q];
+            float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), v4 = m4;
+            if (HAS_M) m4 = reinterpret_cast<float4*>(m)[q];
+            if (HAS_V) v4 = reinterpret_cast<float4*>(v)[q];
+            optim_update_ext<KIND>(w4.x, g4.x, m4.x, v4.x, p, s);
+            optim_update_ext<KIND>(w4.y, g4.y, m4.y, v4.y, p, s);
+            optim_update_ext<KIND>(w4.z, g4.z, m4.z, v4.z, p, s);
+            optim_update_ext<KIND>(w4.w, g4.w, m4.w, v4.w, p, s);
+            reinterpret_cast<float4*>(w)[q] = w4;
+            if (HAS_M) reinterpret_cast<float4*>(m)[q] = m4;
+            if (HAS_V) reinterpret_cast<float4*>(v)[q] = v4;
+        }
+        const int i = (nq << 2) + tid;      // the tail: at most three single lanes
+        if (i < n) {
+            float wi = w[i], mi = HAS_M ? m[i] : 0.f, vi = HAS_V ? v[i] : 0.f;
+            optim_update_ext<KIND>(wi, g[i], mi, vi, p, s);
+            w[i] = wi;
+            if (HAS_M) m[i] = mi;
+            if (HAS_V) v[i] = vi;
+        }
+    } else {
+        for (int i = tid; i < n; i += 256) {
+            float wi = w[i], mi = HAS_M ? m[i] : 0.f, vi = HAS_V ? v[i] : 0.f;
+            optim_update_ext<KIND>(wi, g[i], mi, vi, p, s);
+            w[i] = wi;
+            if (HAS_M) m[i] = mi;
+            if (HAS_V) v[i] = vi;
+        }
+    }
+}
+
 }  // namespace
 }  // namespace lamp
 
@@ -455,6 +642,163 @@ int lamp_optim_step(const lamp_optim_entry* entries, int32_t n, int32_t kind, in
             hipLaunchKernelGGL(optim_step_kernel<true>, dim3(unsigned(chunks)), dim3(256), 0, s, p);
         else
             hipLaunchKernelGGL(optim_step_kernel<false>, dim3(unsigned(chunks)), dim3(256), 0, s, p);
+        if (hipError_t e = hipGetLastError()) return int(e);
+    }
+    return LAMP_OK;
+}
+
+// The chunk count of a table, or -1 when an entry's numel is negative / the count leaves int32 (the partials are indexed by it).
+static int64_t grad_norm_chunks(const lamp_optim_entry* entries, int32_t n) {
+    int64_t chunks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (entries[i].numel < 0) return -1;
+        chunks += (entries[i].numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
+        if (chunks >= (int64_t(1) << 31)) return -1;
+    }
+    return chunks;
+}
+
+size_t lamp_grad_norm_workspace_bytes(const lamp_optim_entry* entries, int32_t n) {
+    if (n <= 0 || !entries) return 0;
+    const int64_t chunks = grad_norm_chunks(entries, n);
+    return chunks < 0 ? 0 : size_t(chunks) * sizeof(double);
+}
+
+int lamp_grad_norm(const lamp_optim_entry* entries, int32_t n, double max_norm, void* workspace, size_t workspace_bytes,
+                   float* grad_state, int32_t* skipped, lamp_stream_t stream) {
+    static_assert(sizeof(NormParams) <= 4096, "kernel arguments");
+    if (n < 0) return LAMP_E_DIMS;
+    if (n > 0 && !entries) return LAMP_E_NULL;
+    if (!grad_state) return LAMP_E_NULL;
+    if (max_norm != max_norm) return LAMP_E_UNSUPPORTED;
+    for (int i = 0; i < n; ++i)
+        if (entries[i].numel < 0) return LAMP_E_DIMS;
+    const int64_t total = grad_norm_chunks(entries, n);
+    if (total < 0) return LAMP_E_UNSUPPORTED;      // 2^31 chunks or more
+    for (int i = 0; i < n; ++i) {
+        if (entries[i].numel == 0) continue;
+        if (!entries[i].grad) return LAMP_E_NULL;
+        if (reinterpret_cast<uintptr_t>(entries[i].grad) & 3u) return LAMP_E_ALIGN;
+    }
+    if ((reinterpret_cast<uintptr_t>(grad_state) & 3u) || (reinterpret_cast<uintptr_t>(skipped) & 3u) ||
+        (reinterpret_cast<uintptr_t>(workspace) & 7u))
+        return LAMP_E_ALIGN;
+    if (total > 0 && !workspace) return LAMP_E_NULL;
+    if (workspace_bytes < size_t(total) * sizeof(double)) return LAMP_E_WORKSPACE;
+    hipStream_t s = hipStream_t(stream);
+    NormParams p{};
+    int64_t done = 0;
+    int i = 0;
+    while (i < n) {
+        int cnt = 0;
+        int64_t chunks = 0;
+        for (; i < n && cnt < OPTIM_TABLE; ++i) {
+            const lamp_optim_entry& e = entries[i];
+            if (e.numel == 0) continue;
+            p.grad[cnt] = e.grad;
+            p.numel[cnt] = e.numel;
+            p.chunk_start[cnt] = int32_t(chunks);
+            chunks += (e.numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
+            ++cnt;
+        }
+        if (cnt == 0) break;
+        p.chunk_start[cnt] = int32_t(chunks);
+        p.n = cnt;
+        p.partial = static_cast<double*>(workspace) + done;
+        hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(unsigned(chunks)), dim3(256), 0, s, p);
+        if (hipError_t e = hipGetLastError()) return int(e);
+        done += chunks;
+    }
+    const bool clip = max_norm >= 0.0;
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, s, static_cast<const double*>(workspace), done,
+                       clip ? float(max_norm) : 0.0f, clip ? 1 : 0, grad_state, skipped);
+    return int(hipGetLastError());
+}
+
+int lamp_optim_step_ext(const lamp_optim_entry* entries, int32_t n, int32_t kind, int64_t step, double lr, double beta1,
+                        double beta2, double eps, const lamp_optim_ext* ext, lamp_stream_t stream) {
+    static_assert(sizeof(OptimExtParams) <= 4096, "kernel arguments");
+    if (!ext) return lamp_optim_step(entries, n, kind, step, lr, beta1, beta2, eps, stream);
+    if (n < 0) return LAMP_E_DIMS;
+    if (kind != LAMP_OPTIM_ADAM && kind != LAMP_OPTIM_SGD) return LAMP_E_UNSUPPORTED;
+    if ((ext->flags & ~(LAMP_OPTIM_DECOUPLED_DECAY | LAMP_OPTIM_SKIP_NONFINITE)) || ext->reserved != 0) return LAMP_E_UNSUPPORTED;
+    if (!(ext->momentum >= 0.0 && ext->momentum < 1.0)) return LAMP_E_UNSUPPORTED;       // (NaN fails both)
+    if (ext->momentum != 0.0 && kind != LAMP_OPTIM_SGD) return LAMP_E_UNSUPPORTED;
+    const bool decoupled = (ext->flags & LAMP_OPTIM_DECOUPLED_DECAY) != 0;
+    const bool skip = (ext->flags & LAMP_OPTIM_SKIP_NONFINITE) != 0;
+    if (decoupled && kind != LAMP_OPTIM_ADAM) return LAMP_E_UNSUPPORTED;
+    if (skip && !ext->grad_state) return LAMP_E_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(ext->grad_state) & 3u) return LAMP_E_ALIGN;
+    if (n == 0) return LAMP_OK;
+    if (!entries) return LAMP_E_NULL;
+    bool any_decay = false;
+    if (ext->entry_weight_decay)
+        for (int i = 0; i < n; ++i) {
+            const float wd = ext->entry_weight_decay[i];
+            if (!(wd >= 0.f && wd <= 3.402823466e38f)) return LAMP_E_UNSUPPORTED;      // negative, infinite or NaN
+            any_decay |= wd != 0.f;
+        }
+    const bool mom = ext->momentum != 0.0;
+    if (!any_decay && !mom && !ext->grad_state)      // nothing asked for: the kernel it has always been, the same bits
+        return lamp_optim_step(entries, n, kind, step, lr, beta1, beta2, eps, stream);
+    if (kind == LAMP_OPTIM_ADAM && step < 1) return LAMP_E_DIMS;
+    const bool needs_m = kind == LAMP_OPTIM_ADAM || mom;
+    for (int i = 0; i < n; ++i) {
+        const lamp_optim_entry& e = entries[i];
+        if (e.numel < 0) return LAMP_E_DIMS;
+        if (e.numel == 0) continue;
+        if (!e.param || !e.grad || (needs_m && !e.exp_avg) || (kind == LAMP_OPTIM_ADAM && !e.exp_avg_sq)) return LAMP_E_NULL;
+        if ((reinterpret_cast<uintptr_t>(e.param) | reinterpret_cast<uintptr_t>(e.grad) |
+             reinterpret_cast<uintptr_t>(e.exp_avg) | reinterpret_cast<uintptr_t>(e.exp_avg_sq)) & 3u)
+            return LAMP_E_ALIGN;
+    }
+    OptimExtParams x{};
+    OptimParams& p = x.o;
+    p.beta2 = float(beta2);
+    p.omb1 = float(1.0 - beta1);
+    p.omb2 = float(1.0 - beta2);
+    p.eps = float(eps);
+    if (kind == LAMP_OPTIM_ADAM) {
+        const double bc1 = 1.0 - pow(beta1, double(step));
+        const double bc2 = 1.0 - pow(beta2, double(step));
+        p.lr = float(lr / bc1);
+        p.inv_bc2_sqrt = float(1.0 / sqrt(bc2));
+    } else {
+        p.lr = float(lr);
+        p.inv_bc2_sqrt = 1.f;
+    }
+    x.grad_state = ext->grad_state;
+    x.momentum = float(ext->momentum);
+    x.decay_mode = !any_decay ? DECAY_NONE : decoupled ? DECAY_DECOUPLED : DECAY_L2;
+    x.skip_nonfinite = skip ? 1 : 0;
+    hipStream_t s = hipStream_t(stream);
+    int i = 0;
+    while (i < n) {
+        int cnt = 0;
+        int64_t chunks = 0;
+        for (; i < n && cnt < OPTIM_TABLE; ++i) {
+            const lamp_optim_entry& e = entries[i];
+            if (e.numel == 0) continue;
+            const int64_t c = (e.numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
+            if (chunks + c >= (int64_t(1) << 31)) {
+                if (cnt == 0) return LAMP_E_UNSUPPORTED;
+                break;
+            }
+            p.e[cnt] = OptimEntry{e.param, e.grad, e.exp_avg, e.exp_avg_sq, e.numel};
+            const float wd = any_decay ? ext->entry_weight_decay[i] : 0.f;
+            // AdamW's factor is taken in double on the host and rounded once, as torch passes it to param.mul_
+            x.decay[cnt] = x.decay_mode == DECAY_DECOUPLED ? float(1.0 - lr * double(wd)) : wd;
+            p.chunk_start[cnt] = int32_t(chunks);
+            chunks += c;
+            ++cnt;
+        }
+        if (cnt == 0) break;
+        p.chunk_start[cnt] = int32_t(chunks);
+        p.n = cnt;
+        const dim3 grid = dim3(unsigned(chunks)), block = dim3(256);
+        if (kind == LAMP_OPTIM_ADAM) hipLaunchKernelGGL(optim_step_ext_kernel<OPT_ADAM>, grid, block, 0, s, x);
+        else if (mom) hipLaunchKernelGGL(optim_step_ext_kernel<OPT_SGD_MOMENTUM>, grid, block, 0, s, x);
+        else hipLaunchKernelGGL(optim_step_ext_kernel<OPT_SGD>, grid, block, 0, s, x);
         if (hipError_t e = hipGetLastError()) return int(e);
     }
     return LAMP_OK;

@@ -35,6 +35,14 @@ losses.csv and train_loss are then that objective; the valid and test losses sta
 different objectives stay comparable.  They add .lossfn_<kind>_<parameters> / .posw_<kind>_<cap> to the results name and
 their flags to the checkpoint's settings, and nothing when they are not given.  (-loss is the reference's flag, parsed and,
 as there, unused.)
+
+-max_grad_norm F, -weight_decay F, -optim adamw, -momentum F (sgd) and -skip_nonfinite are the training-loop controls of
+DESIGN.md section 8.11.  With any of them the optimizer is built over two param groups: parameters with ndim >= 2 decay, 1-D
+parameters and decoder.label_bias (whose -inf entries must never meet weight_decay * w) do not.  Both -optim_impl values serve
+the first four (torch: clip_grad_norm_ in front of every step, torch.optim.AdamW / Adam(weight_decay=) / SGD(momentum=));
+-skip_nonfinite exists with -optim_impl lamp only and adds steps_skipped to each epoch's record, read where the loop already
+synchronises.  Each adds .clip_<v> / .wd_<v> / .mom_<v> / .skipnf to the results name and its flag to the checkpoint's settings,
+and nothing when it is not given.
 """
 import argparse
 import json
@@ -65,7 +73,7 @@ def parse(argv=None):
     ap.add_argument('-n_head2', type=int, default=0)
     ap.add_argument('-n_layers_enc', type=int, default=5)
     ap.add_argument('-n_layers_dec', type=int, default=None)
-    ap.add_argument('-optim', type=str, choices=['adam', 'sgd'], default='adam')
+    ap.add_argument('-optim', type=str, choices=['adam', 'sgd', 'adamw'], default='adam')
     ap.add_argument('-lr', type=float, default=0.0002)
     ap.add_argument('-lr_step_size', type=int, default=1)
     ap.add_argument('-lr_decay', type=float, default=0)
@@ -120,6 +128,16 @@ def parse(argv=None):
                          "(lamp_amd/data.py: label_pos_weight): inv = negatives / positives, sqrt_inv = its square root; "
                          "combines with every -loss_fn; the valid and test losses stay plain BCE")
     ap.add_argument('-pos_weight_cap', type=float, default=100.0, help='the largest weight, also given to a label without a positive')
+    ap.add_argument('-max_grad_norm', type=float, default=None,
+                    help='clip the gradient to this GLOBAL L2 norm before every update (DESIGN.md section 8.11): lamp = one '
+                         'lamp_grad_norm launch, the factor applied inside the optimizer launch; torch = clip_grad_norm_')
+    ap.add_argument('-weight_decay', type=float, default=None,
+                    help='weight decay of every parameter with ndim >= 2 but decoder.label_bias (1-D parameters and the label '
+                         'bias never decay): L2 with -optim adam / sgd, decoupled with -optim adamw (default there: 0.01)')
+    ap.add_argument('-momentum', type=float, default=None, help='-optim sgd only: buf = momentum buf + g; w -= lr buf')
+    ap.add_argument('-skip_nonfinite', action='store_true',
+                    help='-optim_impl lamp only: a batch whose gradient norm is inf or NaN changes no weight and no moment (the '
+                         "decision is taken on the device); the epoch's log line reports steps_skipped")
     ap.add_argument('-optim_impl', choices=['lamp', 'torch'], default=DEFAULT_OPTIM_IMPL,
                     help='lamp = lamp_amd.optim (one lamp_optim_step launch per step); torch = torch.optim (fused=True for adam)')
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4], help='batches in flight in the valid / test epochs')
@@ -131,7 +149,8 @@ def parse(argv=None):
 
 
 # torch's fused Adam: lamp_optim_step has not been shown to beat it same-box (nothing is measured yet; tools/bench_train_epoch.py
-# is the tool that would), and without a measured win the default stays torch's
+# is the tool that would), and without a measured win the default stays torch's.  (With clipping the lamp route is the shorter
+# one -- DESIGN.md section 8.11, tools/bench_optim_ext.py -- which does not decide the plain case.)
 DEFAULT_OPTIM_IMPL = 'torch'
 
 
@@ -159,6 +178,33 @@ def build_loss_options(opt, data, device):
     if opt.pos_weight != 'none':
         w = D.label_pos_weight(data['train']['tgt'], len(data['dict']['tgt']), device, opt.pos_weight, opt.pos_weight_cap)
     return LossOptions(*loss_parameters(opt), pos_weight=w)
+
+
+OPTIM_CONTROL_FLAGS = ('max_grad_norm', 'weight_decay', 'momentum', 'skip_nonfinite')
+
+
+def optimizer_controls(opt):
+    """-max_grad_norm, -weight_decay, -momentum and -skip_nonfinite: normalised on `opt` (None / False = not given), what is
+    not served refused, -> their part of the results name ('' without them)."""
+    name = ''
+    for flag, tag in (('max_grad_norm', 'clip'), ('weight_decay', 'wd'), ('momentum', 'mom')):
+        v = getattr(opt, flag, None)
+        v = None if v is None else float(v)
+        setattr(opt, flag, v)
+        if v is None:
+            continue
+        if not 0.0 <= v < float('inf'):
+            raise ValueError('-%s %r: a finite number >= 0' % (flag, v))
+        name += '.%s_%s' % (tag, v)
+    opt.skip_nonfinite = bool(getattr(opt, 'skip_nonfinite', False))
+    if opt.momentum is not None and (opt.optim != 'sgd' or opt.momentum >= 1.0):
+        raise ValueError('-momentum %r: with -optim sgd only, and in [0, 1)' % (opt.momentum,))
+    if opt.skip_nonfinite:
+        if getattr(opt, 'optim_impl', DEFAULT_OPTIM_IMPL) != 'lamp':
+            raise ValueError('-skip_nonfinite needs -optim_impl lamp: torch.optim has no way to leave a step out without '
+                             'reading the gradient norm back')
+        name += '.skipnf'
+    return name
 
 
 def derive(opt):
@@ -245,6 +291,7 @@ def derive(opt):
         if not 0.0 < opt.pos_weight_cap < float('inf'):
             raise ValueError('-pos_weight_cap %r: a positive finite number' % (opt.pos_weight_cap,))
         name += '.posw_%s_%s' % (opt.pos_weight, opt.pos_weight_cap)
+    name += optimizer_controls(opt)
     if opt.name:
         name += '.' + str(opt.name)
     opt.model_name = os.path.join(opt.results_dir, opt.dataset, name)
@@ -288,12 +335,54 @@ def build_model(opt, data, device):
 def build_optimizer(model, opt):
     """main.py:99 (the reference builds this Adam whatever -optim says; -optim sgd gets the plain update here)."""
     params = list(model.get_trainable_parameters())
+    controls = {f: getattr(opt, f, None) for f in OPTIM_CONTROL_FLAGS}
+    if opt.optim != 'adamw' and all(v is None or v is False for v in controls.values()):
+        # without the new flags: the optimizers this runner has always built, over one flat parameter list
+        if opt.optim_impl == 'lamp':
+            from . import optim
+            return optim.Adam(params, betas=(0.9, 0.98), lr=opt.lr) if opt.optim == 'adam' else optim.SGD(params, lr=opt.lr)
+        if opt.optim == 'adam':
+            return torch.optim.Adam(params, betas=(0.9, 0.98), lr=opt.lr, fused=True)
+        return torch.optim.SGD(params, lr=opt.lr)
+    wd = controls['weight_decay']
+    if wd is None:
+        wd = 1e-2 if opt.optim == 'adamw' else 0.0       # (torch.optim.AdamW's default)
+    groups = decay_param_groups(model, wd)
+    clip, momentum = controls['max_grad_norm'], controls['momentum'] or 0.0
     if opt.optim_impl == 'lamp':
         from . import optim
-        return optim.Adam(params, betas=(0.9, 0.98), lr=opt.lr) if opt.optim == 'adam' else optim.SGD(params, lr=opt.lr)
-    if opt.optim == 'adam':
-        return torch.optim.Adam(params, betas=(0.9, 0.98), lr=opt.lr, fused=True)
-    return torch.optim.SGD(params, lr=opt.lr)
+        extra = dict(max_grad_norm=clip, skip_nonfinite=bool(controls['skip_nonfinite']))
+        if opt.optim == 'sgd':
+            return optim.SGD(groups, lr=opt.lr, momentum=momentum, **extra)
+        return (optim.AdamW if opt.optim == 'adamw' else optim.Adam)(groups, betas=(0.9, 0.98), lr=opt.lr, **extra)
+    if controls['skip_nonfinite']:
+        raise ValueError('-skip_nonfinite needs -optim_impl lamp')
+    if opt.optim == 'sgd':
+        optimizer = torch.optim.SGD(groups, lr=opt.lr, momentum=momentum)
+    else:
+        optimizer = (torch.optim.AdamW if opt.optim == 'adamw' else torch.optim.Adam)(groups, betas=(0.9, 0.98), lr=opt.lr, fused=True)
+    if clip is not None:      # in front of every step(), where the reference's loop would call it (no read-back: foreach, no check)
+        clipped = [p for g in groups for p in g['params']]
+
+        def clip_first(*_):
+            torch.nn.utils.clip_grad_norm_(clipped, clip)
+
+        optimizer.register_step_pre_hook(clip_first)
+    return optimizer
+
+
+def decay_param_groups(model, weight_decay):
+    """-> [decay group, no-decay group] over model.get_trainable_parameters(): parameters with ndim >= 2 decay; 1-D parameters
+    (biases, LayerNorm) and decoder.label_bias do not -- the learnable label graph holds -inf where an edge is blocked, and
+    -inf must never meet weight_decay * w."""
+    trainable = {id(p) for p in model.get_trainable_parameters()}
+    decay, no_decay, seen = [], [], set()
+    for name, p in model.named_parameters():
+        if id(p) not in trainable or id(p) in seen:
+            continue
+        seen.add(id(p))
+        (no_decay if p.ndim < 2 or name.endswith('label_bias') else decay).append(p)
+    return [dict(params=decay, weight_decay=float(weight_decay)), dict(params=no_decay, weight_decay=0.0)]
 
 
 def checkpoint_settings(opt):
@@ -309,6 +398,9 @@ def checkpoint_settings(opt):
             drop.update(flags)
     if getattr(opt, 'pos_weight', 'none') == 'none':
         drop.update(('pos_weight', 'pos_weight_cap'))
+    for f in OPTIM_CONTROL_FLAGS:      # (set flags travel, unset ones never)
+        if getattr(opt, f, None) is None or getattr(opt, f) is False:
+            drop.add(f)
     return argparse.Namespace(**{k: v for k, v in vars(opt).items() if isinstance(v, (bool, int, float, str, type(None)))
                                  and (k not in ('learn_label_bias', 'tune_thresholds') or v) and k not in drop})
 
@@ -366,6 +458,7 @@ def main(argv=None):
     test_data = D.EvalBatcher(data['test']['src'], data['test']['tgt'], opt.test_batch_size)
     n_labels = opt.tgt_vocab_size
     valid_losses, history = [], []
+    skipped_before = 0
     with open(os.path.join(opt.model_name, 'losses.csv'), 'w+') as loss_file:
         for epoch_i in range(opt.epoch):
             if scheduler and opt.lr_decay > 0:   # runner.py:38
@@ -384,6 +477,10 @@ def main(argv=None):
             metrics = {'train': compute_metrics(on_dev['probs'], on_dev['targets'], train_loss, opt.br_threshold, dt / 60)}
             out.update(train_loss=train_loss, train_seconds=dt,
                        train_samples_per_s=sum(real for _, real in on_dev['batches']) / dt)
+            if opt.skip_nonfinite:      # (the loop has synchronised above: the device counter's first and only read-back)
+                skipped = getattr(optimizer, 'skipped_steps', None)
+                total = int(skipped.item()) if skipped is not None else 0
+                out['steps_skipped'], skipped_before = total - skipped_before, total
             losses = {}
             label_thresholds = None
             for split, batches in (('valid', valid_data), ('test', test_data)):
