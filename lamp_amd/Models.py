@@ -539,33 +539,36 @@ class LAMP(nn.Module):
         whole = fixed + (per_sample - fixed) * B + 4096
         budget = max(per_sample + 4096, min(whole, self.workspace_limit_bytes))
         ws = N.workspace(budget, dev)
+        # the grow-only buffer may be larger than this call's budget (an earlier, larger call): hand over the budget, so that
+        # workspace_limit_bytes decides the micro-batch split whatever ran before
+        ws_given = min(ws.numel(), budget)
         if opts is not None and fe is not None:
             N.check(lib.lamp_onehot_forward_opts(C.byref(model), C.byref(fe), C.byref(opts), seq.data_ptr(), pos.data_ptr(), B,
                                                  T_in, logits.data_ptr(), enc_output.data_ptr(),
-                                                 C.byref(aux) if aux is not None else None, ws.data_ptr(), ws.numel(),
+                                                 C.byref(aux) if aux is not None else None, ws.data_ptr(), ws_given,
                                                  N.stream()), 'lamp_onehot_forward_opts')
         elif gp is not None and fe is None and built[9][4] is not None:
             N.check(lib.lamp_forward_packs_kv(C.byref(model), C.byref(opts) if opts is not None else None, C.byref(gp), built[9][4],
                                               seq.data_ptr(), pos.data_ptr(), B, T, logits.data_ptr(), enc_output.data_ptr(),
-                                              C.byref(aux) if aux is not None else None, ws.data_ptr(), ws.numel(), N.stream()),
+                                              C.byref(aux) if aux is not None else None, ws.data_ptr(), ws_given, N.stream()),
                     'lamp_forward_packs_kv')
         elif gp is not None and fe is None:
             N.check(lib.lamp_forward_packs(C.byref(model), C.byref(opts) if opts is not None else None, C.byref(gp), seq.data_ptr(),
                                            pos.data_ptr(), B, T, logits.data_ptr(), enc_output.data_ptr(),
-                                           C.byref(aux) if aux is not None else None, ws.data_ptr(), ws.numel(), N.stream()),
+                                           C.byref(aux) if aux is not None else None, ws.data_ptr(), ws_given, N.stream()),
                     'lamp_forward_packs')
         elif opts is not None:
             N.check(lib.lamp_forward_opts(C.byref(model), C.byref(opts), seq.data_ptr(), pos.data_ptr(), B, T,
                                           logits.data_ptr(), enc_output.data_ptr(), C.byref(aux) if aux is not None else None,
-                                          ws.data_ptr(), ws.numel(), N.stream()), 'lamp_forward_opts')
+                                          ws.data_ptr(), ws_given, N.stream()), 'lamp_forward_opts')
         elif fe is not None:
             N.check(lib.lamp_onehot_forward(C.byref(model), C.byref(fe), seq.data_ptr(), pos.data_ptr(), B, T_in,
                                             logits.data_ptr(), enc_output.data_ptr(), C.byref(aux) if aux is not None else None,
-                                            ws.data_ptr(), ws.numel(), N.stream()), 'lamp_onehot_forward')
+                                            ws.data_ptr(), ws_given, N.stream()), 'lamp_onehot_forward')
         else:
             N.check(lib.lamp_forward(C.byref(model), seq.data_ptr(), pos.data_ptr(), B, T, logits.data_ptr(),
                                      enc_output.data_ptr(), C.byref(aux) if aux is not None else None,
-                                     ws.data_ptr(), ws.numel(), N.stream()), 'lamp_forward')
+                                     ws.data_ptr(), ws_given, N.stream()), 'lamp_forward')
         del keep
         if int_preds:
             return logits, enc_output, ipreds

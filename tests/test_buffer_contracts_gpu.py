@@ -11,7 +11,7 @@ carved out of one allocation, with 64 KiB sentinel red zones around each, worksp
     test_gpu_training.py, test_onehot_gpu.py, test_train_gpu.py, attn_routes_common.py) -- no new tolerances.  Of the
     whole-forward variants only 'default' and 'onehot' are held against the fp64 oracle here; the others (live encoder,
     sigmoid decoder, bf16x3, label bias, enc_mask, no packs) are compared with LAMP.forward bit for bit, and their own files
-    hold that against fp64.
+    hold that against fp64 -- one option at a time; tests/test_combo_gpu.py holds their combinations against fp64.
 
 Every overrun these tests can see lands in memory the arena owns.
 
