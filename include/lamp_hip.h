@@ -231,7 +231,10 @@ const char* lamp_strerror(int status);  /* text for lamp_status / hipError_t val
 
 /* nn.Linear / XavierLinear / Conv1d(k=1) (lamp/SubLayers.py:7-13, 91-93, 110, 127-128):
  *   C[M,N] = act(A[M,K] . W[N,K]^T + bias[N]) + residual[M,N]      (bias, residual may be NULL)
- * lda/ldw/ldc/ldr are leading dimensions in elements; K, lda, ldw must be multiples of 4. */
+ * lda/ldw/ldc/ldr are leading dimensions in elements; K, lda, ldw must be multiples of 4.
+ * Limits (this entry, lamp_linear_prec_fwd and lamp_linear_packed_fwd): M is 64-bit and A, residual and C may be of any
+ * size; inside one tile the byte offsets are 32-bit: max(lda, ldw, ldc) * max(BM, BN) * 4 < 0x7fffffff and ldr * BM * 4 < 0x7fffffff for
+ * the tile the launch picks (BM, BN <= 128: every leading dimension up to 4194300 is served by every tile), else LAMP_E_UNSUPPORTED. */
 int lamp_linear_fwd(const float* A, int64_t M, int32_t K, int64_t lda,
                     const float* W, int32_t N, int64_t ldw, const float* bias,
                     const float* residual, int64_t ldr, int32_t relu,
@@ -265,13 +268,15 @@ int lamp_linear_prec_fwd(const float* A, int64_t M, int32_t K, int64_t lda,
  *     otherwise the packs are ignored.
  *     Same bits either way.
  *   m_dev (nullable): the live row count in device memory; rows at and past min(*m_dev, M) are neither computed nor written
- *     (M then only sizes the launch). */
+ *     (M then only sizes the launch).
+ * A pack is read through one 31-bit descriptor: with (N + 64) * K * 4 >= 0x7fffffff the packs are ignored (same bits). */
 int lamp_linear_packed_fwd(const float* A, int64_t M, int32_t K, int64_t lda, const float* const* W, const float* const* W_pack,
                            int32_t n_seg, int32_t N, int64_t ldw, const float* const* bias, const float* residual, int64_t ldr,
                            int32_t relu, float* const* C, int64_t ldc, const int32_t* m_dev, lamp_stream_t stream);
 
 /* nn.LayerNorm over the last dim, biased variance, eps inside the sqrt (lamp/SubLayers.py:68,130).
- * y may alias x.  d must be a multiple of 4. */
+ * y may alias x.  d must be a multiple of 4, d <= 4096.  Rows are indexed in 64 bits (M * d may pass 2^31 elements); one wave per
+ * row, four rows per workgroup: (M + 3) / 4 > 0x7fffffff is LAMP_E_DIMS (so for every row kernel below that takes a row count). */
 int lamp_layernorm_fwd(const float* x, int64_t M, int32_t d, const float* gamma, const float* beta,
                        float eps, float* y, lamp_stream_t stream);
 
@@ -280,7 +285,10 @@ int lamp_layernorm_fwd(const float* x, int64_t M, int32_t d, const float* gamma,
  * for B samples x H heads.  `attn` (nullable) receives P as (H*B, lq, lk), index head*B + b.
  * A fully blocked row yields NaN in O and P, as in the reference.  d_k, d_v multiples of 4; up to 128 the fused
  * single-kernel path runs, beyond that a general three-launch path (S = QK^T, masked softmax, PV) that keeps its
- * scores in `attn` -- which must then be given (LAMP_E_WORKSPACE otherwise). */
+ * scores in `attn` -- which must then be given (LAMP_E_WORKSPACE otherwise).
+ * Limits (every lamp_sdpa_* / lamp_mha_* entry): B * H and with them Q, K, V, out and attn may be of any size (slice offsets are 64-bit);
+ * inside ONE (sample, head) slice the byte offsets are 32-bit: lq * q_r * 4, lk * k_r * 4, lk * v_r * 4, lq * stride_q + lk bytes of a
+ * u8 mask (x 4 for bit-packed words) and (lq * stride_q + lk + 3) * 4 of a bias must each stay below 0x7fffffff, else LAMP_E_UNSUPPORTED. */
 int lamp_sdpa_fwd(const float* q, const float* k, const float* v, float* out, float* attn,
                   int32_t B, int32_t H, int32_t lq, int32_t lk, int32_t d_k, int32_t d_v,
                   float inv_temperature, const lamp_mask* mask, const lamp_attn_layout* layout,
@@ -344,13 +352,15 @@ int lamp_ffn_fwd(const float* x, int64_t M, int32_t d_model, int32_t d_inner,
                  void* workspace, size_t workspace_bytes, lamp_stream_t stream);
 
 /* GraphEncoder's input stage (lamp/Encoders.py:66,75): out[t,:] = emb[src_seq[t],:] (+ pos[src_pos[t],:]).
- * An index outside its table writes NaN into that row (PyTorch would raise; a kernel cannot). */
+ * An index outside its table writes NaN into that row (PyTorch would raise; a kernel cannot).  n_tokens * d_model may pass 2^32 bytes
+ * (64-bit row offsets; lamp_embed_bwd and lamp_embed_bwd_ordered likewise); (n_tokens + 3) / 4 > 0x7fffffff is LAMP_E_DIMS. */
 int lamp_embed_fwd(const int64_t* src_seq, const int64_t* src_pos, int64_t n_tokens,
                    const float* emb, int32_t n_vocab, const float* pos_table, int32_t n_position,
                    int32_t d_model, float* out, lamp_stream_t stream);
 
 /* Label read-out (lamp/Models.py:124-126): logits[b,i] = <y[b,i,:], w_out[i,:]>, i.e. the diagonal
- * of y . w_out^T without forming the (B, L, L) product. */
+ * of y . w_out^T without forming the (B, L, L) product.  B * L * d_model may pass 2^32 bytes (64-bit row offsets);
+ * (B * L + 3) / 4 > 0x7fffffff is LAMP_E_DIMS. */
 int lamp_diag_logits_fwd(const float* y, const float* w_out, int32_t B, int32_t L, int32_t d_model,
                          float* logits, lamp_stream_t stream);
 
@@ -388,7 +398,11 @@ int lamp_pack_weight(const float* W, int32_t N, int32_t K, int64_t ldw, int32_t 
  * without a transpose copy: dX = dY.W, dW = dY^T.X, dP = dO.V^T, dV = P^T.dO, dQ = dS.K, dK = dS^T.Q.
  * relu_mask (batch 1 only, nullable): result elements whose mask value is not > 0 are zeroed (ReLU backward).
  * accumulate != 0 adds to C.  Workspace (nullable): lamp_gemm_workspace_bytes() lets deep-K / small-output
- * products (weight gradients) split K deterministically. */
+ * products (weight gradients) split K deterministically.
+ * Limits: the batch strides and m * row_stride are 64-bit (an operand may pass 2^32 bytes through M or the batch); inside one 64-row tile
+ * the byte offsets are 32-bit: (64 * ld + K) * 4 for a k-contiguous operand, K * ld * 4 for a k-strided one, 64 * ldc * 4 and
+ * 64 * ld_mask * 4 must each stay below 0x7fffffff, else LAMP_E_UNSUPPORTED; batch0 * batch1 <= 65535, else LAMP_E_DIMS.
+ * lamp_gemm_grouped validates every description before its launch: one description beyond a limit refuses the call, no C is written. */
 typedef struct lamp_gemm_desc {
     const float* A;
     const float* B;
@@ -524,7 +538,8 @@ int lamp_layernorm_bwd(const float* x, const float* residual, int64_t residual_r
                        float* dx, float* dgamma, float* dbeta, float* dbias, void* workspace, size_t workspace_bytes,
                        lamp_stream_t stream);
 
-/* out[n] = sum_m x[m*ldx + n]: bias gradients, and the label-table gradient (sum over the batch). */
+/* out[n] = sum_m x[m*ldx + n]: bias gradients, and the label-table gradient (sum over the batch).  M, N and ldx are 64-bit and x may be
+ * of any size; (N + 255) / 256 > 0x7fffffff is LAMP_E_DIMS (lamp_attn_bias_bwd likewise with N = lq * lk). */
 size_t lamp_colsum_workspace_bytes(int64_t M, int64_t N);
 int lamp_colsum(const float* x, int64_t M, int64_t N, int64_t ldx, float* out, void* workspace,
                 size_t workspace_bytes, lamp_stream_t stream);
@@ -554,10 +569,12 @@ int lamp_label_bias_fold(const float* param, int64_t ld_p, const uint8_t* blocke
 /* nn.Dropout in training mode (lamp/SubLayers.py:40,113,138): y[e] = keep(e, seed) ? x[e] / (1 - p) : 0 with a
  * counter-based generator -- keep(e, seed) = mix32(e, seed) >= p * 2^32 -- so the mask is a pure function of
  * (element index, seed) and is never stored: calling it again on the gradient with the same seed IS the backward
- * pass.  y may alias x.  (The stream of random numbers necessarily differs from torch's Philox stream.) */
+ * pass.  y may alias x.  (The stream of random numbers necessarily differs from torch's Philox stream.)  The element index is 64 bits
+ * wide and both of its words are mixed in: n has no limit, and elements 2^32 .. have a mask of their own. */
 int lamp_dropout(const float* x, int64_t n, float p, uint32_t seed, float* y, lamp_stream_t stream);
 
-/* Softmax backward per row of length lk: dS = scale * P * (dP - sum_k P * dP); dS may alias dP. */
+/* Softmax backward per row of length lk: dS = scale * P * (dP - sum_k P * dP); dS may alias dP.  rows * lk may pass 2^31 elements
+ * (64-bit row offsets); (rows + 3) / 4 > 0x7fffffff is LAMP_E_DIMS. */
 int lamp_softmax_bwd(const float* P, const float* dP, int64_t rows, int32_t lk, float scale, float* dS,
                      lamp_stream_t stream);
 
@@ -565,7 +582,7 @@ int lamp_softmax_bwd(const float* P, const float* dP, int64_t rows, int32_t lk, 
  *   dS = scale * P * (1 - P) * dropout_backward(dP)
  * P = 0 on blocked entries keeps their gradient at exactly 0 (no NaN anywhere).  dropout_p > 0: dP is the gradient of
  * dropout(P) and lamp_dropout's mask for (`seed`, element index = row * lk + column) is applied on load; 0: dP as it is.
- * dS may alias dP. */
+ * dS may alias dP.  rows * lk has no limit (a 64-bit element index, which is also the dropout counter). */
 int lamp_sigmoid_attn_bwd(const float* P, const float* dP, int64_t rows, int32_t lk, float scale, float dropout_p,
                           uint32_t seed, float* dS, lamp_stream_t stream);
 
@@ -806,7 +823,8 @@ int lamp_ranking_metrics(const float* probs, int64_t ld_probs, const float* targ
 /* The integer counts behind the thresholded figures (compute_tp_fp_fn and the per-sample loops of utils/evals.py:347-357),
  * with prediction = (score, NaN read as 0) >= threshold and gold = target != 0:
  *   label_tp / label_fp / label_fn [L];  sample_tp, sample_pred (predicted labels), sample_gold (gold labels) and
- *   sample_mismatch (labels where prediction != gold) [n_rows].  All outputs are written in full. */
+ *   sample_mismatch (labels where prediction != gold) [n_rows].  All outputs are written in full.  n_rows * L may pass 2^32 bytes; the
+ *   per-label counts are int32, so n_rows >= 2^31 is LAMP_E_UNSUPPORTED before any launch (lamp_threshold_counts_vec likewise). */
 int lamp_threshold_counts(const float* probs, int64_t ld_probs, const float* targets, int64_t ld_targets, int64_t n_rows,
                           int32_t L, float threshold, int32_t* label_tp, int32_t* label_fp, int32_t* label_fn,
                           int32_t* sample_tp, int32_t* sample_pred, int32_t* sample_gold, int32_t* sample_mismatch,
@@ -905,7 +923,8 @@ int lamp_rank_at_k(const int32_t* idx, int64_t ld_idx, const float* targets, int
  *   row_loss[k * ld_row_loss + r]      = sum_i max(x,0) - x*t + log1p(exp(-|x|)),  x = logits[k][r, i], t = targets[r, i]
  * The 'mean' of matrix k is sum_r row_loss[k, r] / (n_rows * L), taken by the caller.  Every sum runs in an order fixed by L
  * alone (no atomics): a row's probabilities and loss sums do not depend on the batch it is in, and neither do its gradients
- * up to the 1 / (n_rows * L) factor.  A NaN logit gives NaN in its own row only. */
+ * up to the 1 / (n_rows * L) factor.  A NaN logit gives NaN in its own row only.  n_rows * L may pass 2^32 bytes (64-bit row offsets;
+ * lamp_multilabel_loss_train likewise); (n_rows + 3) / 4 >= 2^31 is LAMP_E_UNSUPPORTED. */
 int lamp_bce_logits_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
                           const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
                           int64_t ld_row_loss, lamp_stream_t stream);
@@ -959,7 +978,8 @@ int lamp_embed_bwd_ordered(const int64_t* src_seq, int64_t n_tokens, const float
  *             w = w - lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
  *   LAMP_OPTIM_SGD:  w = w - lr * g  (exp_avg / exp_avg_sq unused, may be NULL)
  * The hyper-parameters are doubles: 1 - beta and the bias corrections are taken on the host in double, as torch does,
- * and rounded to fp32 once.  Elementwise: bit-identical from run to run. */
+ * and rounded to fp32 once.  Elementwise: bit-identical from run to run.  An entry may pass 2^32 bytes (a workgroup's offset is its
+ * 64-bit chunk index times 4096); 2^31 chunks in one launch's entries is LAMP_E_UNSUPPORTED (lamp_optim_step_ext and lamp_grad_norm likewise). */
 enum lamp_optim_kind { LAMP_OPTIM_ADAM = 0, LAMP_OPTIM_SGD = 1 };
 typedef struct lamp_optim_entry {
     float* param;

@@ -1034,9 +1034,10 @@ def dropout(x, p, seed, out=None):
     return y
 
 
-def dropout_keep_mask(n, p, seed, device='cpu'):
-    """The library's keep mask for elements 0..n-1, restated with torch integer ops (tests / documentation)."""
-    e = torch.arange(n, dtype=torch.int64, device=device)
+def dropout_keep_mask(n, p, seed, device='cpu', start=0):
+    """The library's keep mask for elements start..start+n-1, restated with torch integer ops (tests / documentation).
+    The element index is 64 bits wide: its high word is mixed in, so a window beyond 2^32 has a mask of its own."""
+    e = torch.arange(int(start), int(start) + int(n), dtype=torch.int64, device=device)
     m32 = 0xffffffff
     h = ((e & m32) ^ (((e >> 32) * 0x9E3779B9) & m32) ^ (int(seed) & m32)) & m32
     h = h ^ (h >> 16)

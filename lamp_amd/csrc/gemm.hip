@@ -576,6 +576,10 @@ static int launch_cfg2(const GemmParams& p, hipStream_t s) {
     using T = GemmTile<BM, BN, BK, WAVES_M, WAVES_N, MF, WPACK>;
     constexpr bool RPRE = T::MI * T::NI * (MF == 32 ? 16 : 4) <= 16;
     auto kern = gemm_nt_kernel<BM, BN, BK, WAVES_M, WAVES_N, KTAIL, MF, RPRE, VEC, RGATHER, WPACK>;
+    // 32-bit in-tile byte offsets.  Refused before anything touches the runtime: the status is the same with and without a device
+    const int64_t ldmax = p.lda > p.ldw ? (p.lda > p.ldc ? p.lda : p.ldc) : (p.ldw > p.ldc ? p.ldw : p.ldc);
+    if (ldmax * (BM > BN ? BM : BN) * 4 >= 0x7fffffffLL || (p.R && p.ldr * BM * 4 >= 0x7fffffffLL))
+        return LAMP_E_UNSUPPORTED;
     size_t LDS = T::LDS_LAUNCH_BYTES;
     static AttrOnce once;
 #ifdef LAMP_TUNING
@@ -584,10 +588,6 @@ static int launch_cfg2(const GemmParams& p, hipStream_t s) {
 #else
     if (int e = once.set(reinterpret_cast<const void*>(kern), LDS)) return e;
 #endif
-    // 32-bit in-tile byte offsets
-    const int64_t ldmax = p.lda > p.ldw ? (p.lda > p.ldc ? p.lda : p.ldc) : (p.ldw > p.ldc ? p.ldw : p.ldc);
-    if (ldmax * (BM > BN ? BM : BN) * 4 >= 0x7fffffffLL || (p.R && p.ldr * BM * 4 >= 0x7fffffffLL))
-        return LAMP_E_UNSUPPORTED;
     const int64_t tiles_m = (p.M + BM - 1) / BM;
     const int tiles_n_seg = (p.N + BN - 1) / BN;
     const int tiles_n = tiles_n_seg * p.nseg;

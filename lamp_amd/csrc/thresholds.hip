@@ -235,7 +235,8 @@ int lamp_threshold_counts_vec(const float* probs, int64_t ld_probs, const float*
         return LAMP_E_NULL;
     const int64_t row_blocks = (n_rows + 255) / 256;
     const int slabs = (L + VEC_SLAB - 1) / VEC_SLAB;
-    if (row_blocks >= (int64_t(1) << 31) || slabs > 65535) return LAMP_E_UNSUPPORTED;
+    // the per-label counts are int32: a label of 2^31 rows could not hold its own count
+    if (n_rows >= (int64_t(1) << 31) || slabs > 65535) return LAMP_E_UNSUPPORTED;
     hipStream_t s = hipStream_t(stream);
     for (int32_t* p : {label_tp, label_fp, label_fn})
         if (hipError_t e = hipMemsetAsync(p, 0, size_t(L) * sizeof(int32_t), s)) return int(e);
