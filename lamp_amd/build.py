@@ -33,7 +33,8 @@ SOURCES = ['gemm.hip', 'gemm_split.hip', 'gemm_gen.hip', 'attention.hip', 'atten
            'backward.hip', 'chain.hip', 'conv.hip', 'metrics.hip', 'thresholds.hip', 'rank_at_k.hip', 'train_step.hip', 'api.hip']
 TUNING_SOURCES = {'gemm.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_sparse.hip', 'chain.hip'}
 TUNING_ONLY = ['experiments/slab.hip']   # experiments kept bit-identical and benchmarkable, never part of the product library
-HEADERS = [os.path.join(CSRC, 'lamp_kernels.h'), os.path.join(CSRC, 'lamp_asm.h'), os.path.join(HERE, '..', 'include', 'lamp_hip.h')]
+HEADERS = [os.path.join(CSRC, 'lamp_kernels.h'), os.path.join(CSRC, 'lamp_asm.h'), os.path.join(CSRC, 'attn16_frag.h'),
+           os.path.join(HERE, '..', 'include', 'lamp_hip.h')]
 REMARKS = ['-Rpass-analysis=kernel-resource-usage']   # per-kernel VGPR / AGPR / scratch report, saved beside each object
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden', '-fvisibility-inlines-hidden', '-Wno-unused-result']
 

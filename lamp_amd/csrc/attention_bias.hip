@@ -4,7 +4,8 @@
 // whose entries are all -inf comes out NaN as masked_fill + softmax gives.  One kernel for every shape with
 // d_k, d_v <= 128; heads share the bias, samples share it (stride_b == 0) or bring their own.
 //
-// Work decomposition and operand paths are attention_sigmoid.hip's: a wave owns ONE 16-query block and a share of its 16-key
+// Work decomposition and operand paths are attention_sigmoid.hip's (the code the kernels share is attn16_frag.h): a wave
+// owns ONE 16-query block and a share of its 16-key
 // tiles, a workgroup is four waves = 4 / ksplit query blocks x ksplit key shares (ksplit is a launch argument), both products
 // are TRANSPOSED (query on the lane = lane & 15, register r of S^T = key 4 * (lane >> 4) + r of the tile = B operand of PV step
 // r), the Q block sits in LDS pre-scaled by log2(e) / temperature, K tiles are fetched one tile ahead with range-checked buffer
@@ -23,52 +24,20 @@
 // and, with V, multiplied into O as it is.
 //
 // Bits: the key split is a function of lk alone (never of B), partial results combine in share order through LDS.
-#include "lamp_kernels.h"
+#include "attn16_frag.h"
 
 namespace lamp {
 
 namespace {
 
-constexpr int BS_PAD = 8;     // LDS row padding of the Q block / K tiles (attention_small.hip: conflict-free b128 fragment reads)
 constexpr int BS_WAVES = 4;
 constexpr float BS_LOG2E = 1.4426950408889634f;
-
-// Exchange across the four lane groups of a query (lanes l, l^16, l^32, l^48): attention_small.hip's row swaps (the builtins
-// return their second result equal to the first in hipcc 7.2 -- DESIGN.md 4.4; the wait states around them are spelled out).
-__device__ __forceinline__ void bs_swap16(float& a, float& b) {
-    asm volatile("s_nop 3\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 3" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ void bs_swap32(float& a, float& b) {
-    asm volatile("s_nop 3\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 3" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ float bs_group_max(float v) {
-    float a = v, b = v;
-    bs_swap16(a, b);
-    a = fmaxf(a, b);
-    b = a;
-    bs_swap32(a, b);
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float bs_group_sum(float v) {  // (v[l] + v[l^16]) + (v[l^32] + v[l^48]) in every lane of the four
-    float a = v, b = v;
-    bs_swap16(a, b);
-    a = a + b;
-    b = a;
-    bs_swap32(a, b);
-    return a + b;
-}
-
-// key shares for lk keys: attention_small.hip's measured thresholds on the number of 16-key tiles -- a function of lk alone
-inline int bias_key_shares(int lk) {
-    const int nt = (lk + 15) / 16;
-    return nt >= 12 ? 4 : (nt >= 4 ? 2 : 1);
-}
 
 template <int DP, int PM>
 __global__ __launch_bounds__(BS_WAVES * 64, 2) void attn_bias_kernel(AttnParams p, int ksplit) {
     constexpr int DKC = DP / 16;   // 16-wide k chunks of the QK^T product (one b128 fragment each)
     constexpr int DV8 = DP / 16;   // floats of a V row per lane = number of 16-row blocks of O^T
-    constexpr int QS = DP + BS_PAD;
+    constexpr int QS = DP + ATTN16_PAD;
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x;
@@ -136,52 +105,12 @@ __global__ __launch_bounds__(BS_WAVES * 64, 2) void attn_bias_kernel(AttnParams 
     constexpr int DVW = DV8 == 8 ? 4 : DV8;
     const unsigned v_voff = DVW * l15 < p.dv ? unsigned(4 * g * v_r + DVW * l15) * 4u : OOB;
     const unsigned v_voff2 = 64 + DVW * l15 < p.dv ? unsigned(4 * g * v_r + DVW * l15) * 4u + 256u : OOB;
-    auto load_v = [&](int kt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const unsigned so = unsigned((kt * 16 + r) * v_r) * 4u;
-            if constexpr (DV8 == 8) {
-                const float4 a = bload4(rsV, v_voff, so);
-                const float4 c2 = bload4(rsV, v_voff2, so);
-                vf[r][0] = a.x; vf[r][1] = a.y; vf[r][2] = a.z; vf[r][3] = a.w;
-                vf[r][4] = c2.x; vf[r][5] = c2.y; vf[r][6] = c2.z; vf[r][7] = c2.w;
-            } else if constexpr (DV8 == 4) {
-                const float4 a = bload4(rsV, v_voff, so);
-                vf[r][0] = a.x; vf[r][1] = a.y; vf[r][2] = a.z; vf[r][3] = a.w;
-            } else {
-                const f32x2 a = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsV, v_voff, so, 0));
-                vf[r][0] = a.x; vf[r][1] = a.y;
-            }
-        }
-    };
+    auto load_v = [&](int kt) { attn16_load_v<DP>(vf, rsV, v_voff, v_voff2, kt, v_r); };
     const unsigned b_voff = unsigned(int64_t(qc) * p.m_sq + 4 * g) * 4u;
     auto load_bias = [&](int kt) {   // past the last tile / the row's last group: zeros (those keys are blocked below anyway)
         bg = bload4(rsB, (kt < nt && kt * 16 + 4 * g < p.lk) ? b_voff + unsigned(kt) * 64u : OOB, 0);
     };
-    // S^T = K Q^T for the tile staged in Ks (two accumulator chains, summed: the dependent-issue latency of the 16x16x4 MFMA
-    // is 40 cycles against 32 of issue)
-    auto scores = [&](f32x4& s) {
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-        const float* qp = Qs + l15 * QS + 4 * g;   // lane (query l15, group g): Q[q][16c + 4g + j]
-        const float* kp = Ks + l15 * QS + 4 * g;   // lane (key   l15, group g): K[k][16c + 4g + j]
-#pragma unroll
-        for (int c = 0; c < DKC; c += 2) {
-            const float4 qa = *reinterpret_cast<const float4*>(qp + 16 * c);
-            const float4 qb2 = *reinterpret_cast<const float4*>(qp + 16 * c + 16);
-            const float4 ka = *reinterpret_cast<const float4*>(kp + 16 * c);
-            const float4 kb = *reinterpret_cast<const float4*>(kp + 16 * c + 16);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.x, qa.x, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.x, qb2.x, s1, 0, 0, 0);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.y, qa.y, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.y, qb2.y, s1, 0, 0, 0);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.z, qa.z, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.z, qb2.z, s1, 0, 0, 0);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.w, qa.w, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.w, qb2.w, s1, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[r] = s0[r] + s1[r];
-    };
+    auto scores = [&](f32x4& s) { attn16_scores<DP>(Qs, Ks, l15, g, f32x4{0.f, 0.f, 0.f, 0.f}, s); };
     // the tile's scaled scores plus bias * log2(e), -inf for the keys past lk (bg is consumed: the next tile's may be requested)
     auto add_bias = [&](int kt, f32x4& s) {
         const int kbase = kt * 16 + 4 * g;
@@ -214,7 +143,7 @@ __global__ __launch_bounds__(BS_WAVES * 64, 2) void attn_bias_kernel(AttnParams 
                 load_bias(kt + 1);
                 const float tmax = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
                 if (__any(tmax > m_run)) {
-                    const float m_new = fmaxf(m_run, bs_group_max(tmax));
+                    const float m_new = fmaxf(m_run, group_max(tmax));
                     l_part *= __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
                     m_run = m_new;
                 }
@@ -224,7 +153,7 @@ __global__ __launch_bounds__(BS_WAVES * 64, 2) void attn_bias_kernel(AttnParams 
                 l_part += (s[0] + s[1]) + (s[2] + s[3]);
             }
         }
-        const float inv_l = 1.0f / bs_group_sum(l_part);   // l = 0 (fully blocked row): 0 * inf = NaN, like torch
+        const float inv_l = 1.0f / group_sum(l_part);   // l = 0 (fully blocked row): 0 * inf = NaN, like torch
         const float m_use = (m_run == -INFINITY) ? 0.f : m_run;
         // ---- pass 2: P = exp2(s - m) / l, written once and multiplied into O as it is ----
         if (working) {
@@ -282,7 +211,7 @@ __global__ __launch_bounds__(BS_WAVES * 64, 2) void attn_bias_kernel(AttnParams 
                 }
                 const float tmax = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
                 if (__any(tmax > m_run + RESCALE_THR)) {
-                    const float m_new = fmaxf(m_run, bs_group_max(tmax));
+                    const float m_new = fmaxf(m_run, group_max(tmax));
                     const float alpha = __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
                     l_part *= alpha;
                     m_run = m_new;
@@ -346,7 +275,7 @@ __global__ __launch_bounds__(BS_WAVES * 64, 2) void attn_bias_kernel(AttnParams 
     if (!(wave_active && ks == 0)) return;
     float inv_l = 1.0f;   // PM == 1: O was accumulated from normalised probabilities
     if constexpr (PM != 1) {
-        const float l_run = bs_group_sum(l_part);   // the four lane groups of a query hold disjoint keys
+        const float l_run = group_sum(l_part);   // the four lane groups of a query hold disjoint keys
         if constexpr (PM == 2) {
             // row log2-sum-exp of the biased scores: probabilities = exp2(score - lse).  A fully blocked row has
             // l = 0 -> lse = -inf -> exp2(-inf - -inf) = NaN, as the reference's softmax gives.
@@ -381,20 +310,9 @@ __global__ __launch_bounds__(BS_WAVES * 64, 2) void attn_bias_kernel(AttnParams 
 template <int DP, int PM>
 int launch_bias_pm(const AttnParams& p, int ksplit, hipStream_t s) {
     const int QB = BS_WAVES / ksplit;
-    const size_t lds_qk = size_t(QB + BS_WAVES) * 16 * (DP + BS_PAD) * sizeof(float);   // Q blocks + one K tile per wave
-    const size_t lds_merge = ksplit > 1 ? size_t(BS_WAVES) * (DP / 4 + 4) * 64 * sizeof(float) : 0;
-    const size_t lds = lds_qk > lds_merge ? lds_qk : lds_merge;
-    constexpr size_t lds_max = size_t(2 * BS_WAVES) * 16 * (DP + BS_PAD) * sizeof(float);
-    static_assert(lds_max >= size_t(BS_WAVES) * (DP / 4 + 4) * 64 * sizeof(float), "the merge region fits the largest Q / K region");
-    auto kern = attn_bias_kernel<DP, PM>;
-    if constexpr (lds_max > 65536) {
-        static AttrOnce once;
-        if (int e = once.set(reinterpret_cast<const void*>(kern), lds_max)) return e;
-    }
-    const int64_t nwg = int64_t((p.lq + 16 * QB - 1) / (16 * QB)) * p.H * p.B;
-    if (nwg > 0x7fffffffLL) return LAMP_E_DIMS;
-    hipLaunchKernelGGL(kern, dim3(unsigned(nwg)), dim3(BS_WAVES * 64), lds, s, p, ksplit);
-    return int(hipGetLastError());
+    constexpr int MERGE_F4 = DP / 16 + 1;   // a wave's merge record: its o blocks, then (m, l, -, -)
+    return attn16_launch<attn_bias_kernel<DP, PM>, attn16_lds_bytes(BS_WAVES, BS_WAVES, DP, MERGE_F4)>(
+        p, QB, BS_WAVES, attn16_lds_bytes(QB, BS_WAVES, DP, ksplit > 1 ? MERGE_F4 : 0), s, ksplit);
 }
 
 template <int DP>
@@ -409,7 +327,7 @@ int launch_bias_dp(const AttnParams& p, int ksplit, hipStream_t s) {
 // Called by launch_attn (attention.hip) behind its argument checks, for AttnParams::mask_kind == LAMP_MASK_BIAS_F32 and
 // d_k, d_v <= 128 (softmax, no tile list, no ragged keys).
 int launch_attn_bias(const AttnParams& p, hipStream_t s) {
-    const int ksplit = bias_key_shares(p.lk);
+    const int ksplit = attn16_key_shares((p.lk + 15) / 16);   // a function of lk alone
     const int dmax = p.dk > p.dv ? p.dk : p.dv;
     if (dmax <= 32) return launch_bias_dp<32>(p, ksplit, s);
     if (dmax <= 64) return launch_bias_dp<64>(p, ksplit, s);

@@ -5,7 +5,8 @@
 // No key is coupled to another: no running maximum, no rescale, no log-sum-exp.  A row without one allowed key is 0 (not NaN),
 // a key split is a plain sum, and the maps come out of the same single pass (no lse, no normalising launch).
 //
-// Work decomposition (attention_small.hip's, simplified): a wave owns ONE 16-query block and a share of its 16-key tiles; a
+// Work decomposition (attention_small.hip's, simplified; the code the kernels share is attn16_frag.h): a wave owns ONE
+// 16-query block and a share of its 16-key tiles; a
 // workgroup is always four waves = 4 / ksplit query blocks x ksplit key shares (ksplit is a launch argument, not a template axis:
 // 3 head widths x 4 mask kinds = 12 instantiations).  Both products are TRANSPOSED, so the query sits on the lane (column =
 // lane & 15) in both accumulators and register r of S^T (key 4 * (lane >> 4) + r of the tile) is directly the B operand of PV
@@ -17,23 +18,19 @@
 // Bits: the key split is a function of the sample's own key count (kv_len[b], else lk) -- never of B -- and under
 // LAMP_MASK_SELF_RAGGED without per-sample key counts it is 1, so that neither lq nor lk enters.  Tiles past a sample's last
 // key add exact zeros to accumulators that are never -0.0 (p >= 0, accumulators start at +0).
-#include "lamp_kernels.h"
+#include "attn16_frag.h"
 
 namespace lamp {
 
 namespace {
 
-constexpr int SG_PAD = 8;     // LDS row padding of the Q block / K tiles (attention_small.hip: conflict-free b128 fragment reads)
 constexpr int SG_WAVES = 4;
-
-// key shares for a sample of nt sixteen-key tiles (attention_small.hip's measured thresholds), at most the launch's
-__host__ __device__ inline int sg_shares(int nt) { return nt >= 12 ? 4 : (nt >= 4 ? 2 : 1); }
 
 template <int DP, int MK>
 __global__ __launch_bounds__(SG_WAVES * 64, 2) void attn_sigmoid_kernel(AttnParams p, int ksplit) {
     constexpr int DKC = DP / 16;   // 16-wide k chunks of the QK^T product (one b128 fragment each)
     constexpr int DV8 = DP / 16;   // floats of a V row per lane = number of 16-row blocks of O^T
-    constexpr int QS = DP + SG_PAD;
+    constexpr int QS = DP + ATTN16_PAD;
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x;
@@ -61,10 +58,9 @@ __global__ __launch_bounds__(SG_WAVES * 64, 2) void attn_sigmoid_kernel(AttnPara
     const int64_t v_row0 = p.kv_len ? int64_t(row0) * v_r : int64_t(b) * p.lay.v_b;
     const __amdgpu_buffer_rsrc_t rsQ = make_rsrc(p.Q + int64_t(b) * p.lay.q_b + int64_t(h) * p.lay.q_h,
                                                  (uint64_t(p.lq - 1) * q_r + p.dk) * 4u);
-    const __amdgpu_buffer_rsrc_t rsK = make_rsrc(p.K + k_row0 + int64_t(h) * p.lay.k_h,
-                                                 lk_b > 0 ? (uint64_t(lk_b - 1) * k_r + p.dk) * 4u : 0);
-    const __amdgpu_buffer_rsrc_t rsV = make_rsrc(has_v ? p.V + v_row0 + int64_t(h) * p.lay.v_h : p.K,
-                                                 (has_v && lk_b > 0) ? (uint64_t(lk_b - 1) * v_r + p.dv) * 4u : 0);
+    const __amdgpu_buffer_rsrc_t rsK = attn16_rsrc_rows(p.K + k_row0 + int64_t(h) * p.lay.k_h, lk_b, k_r, p.dk);
+    const __amdgpu_buffer_rsrc_t rsV =
+        attn16_rsrc_rows(has_v ? p.V + v_row0 + int64_t(h) * p.lay.v_h : p.K, lk_b, v_r, p.dv, has_v);
     const __amdgpu_buffer_rsrc_t rsM =
         MK == LAMP_MASK_BITS_U32
             ? make_rsrc(static_cast<const unsigned*>(p.mask) + int64_t(b) * p.m_sb,
@@ -102,7 +98,7 @@ __global__ __launch_bounds__(SG_WAVES * 64, 2) void attn_sigmoid_kernel(AttnPara
     const int n_idx = tl ? 2 * tl[0] : nt;
     auto tile_at = [&](int idx) { return idx < n_idx ? (tl ? 2 * tl[1 + (idx >> 1)] + (idx & 1) : idx) : nt; };   // nt: past the end
     // key shares in use: what the launcher would choose for THIS sample's key count (<= ksplit, sized for the padded length)
-    const int shares = sg_shares(nt_b);
+    const int shares = attn16_key_shares(nt_b);
     const int ks_eff = shares < ksplit ? shares : ksplit;
 
     float4 kg[DKC];        // the NEXT tile's K rows in flight (coalesced: row = i * RPI + lane / C4K, float4 lane % C4K)
@@ -123,24 +119,7 @@ __global__ __launch_bounds__(SG_WAVES * 64, 2) void attn_sigmoid_kernel(AttnPara
     constexpr int DVW = DV8 == 8 ? 4 : DV8;
     const unsigned v_voff = DVW * l15 < p.dv ? unsigned(4 * g * v_r + DVW * l15) * 4u : OOB;
     const unsigned v_voff2 = 64 + DVW * l15 < p.dv ? unsigned(4 * g * v_r + DVW * l15) * 4u + 256u : OOB;
-    auto load_v = [&](int kt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const unsigned so = unsigned((kt * 16 + r) * v_r) * 4u;
-            if constexpr (DV8 == 8) {
-                const float4 a = bload4(rsV, v_voff, so);
-                const float4 c2 = bload4(rsV, v_voff2, so);
-                vf[r][0] = a.x; vf[r][1] = a.y; vf[r][2] = a.z; vf[r][3] = a.w;
-                vf[r][4] = c2.x; vf[r][5] = c2.y; vf[r][6] = c2.z; vf[r][7] = c2.w;
-            } else if constexpr (DV8 == 4) {
-                const float4 a = bload4(rsV, v_voff, so);
-                vf[r][0] = a.x; vf[r][1] = a.y; vf[r][2] = a.z; vf[r][3] = a.w;
-            } else {
-                const f32x2 a = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsV, v_voff, so, 0));
-                vf[r][0] = a.x; vf[r][1] = a.y;
-            }
-        }
-    };
+    auto load_v = [&](int kt) { attn16_load_v<DP>(vf, rsV, v_voff, v_voff2, kt, v_r); };
     const unsigned m_voff = unsigned(int64_t(qc) * p.m_sq) * 4u;
     auto load_mask = [&](int kt) {
         const int kbase = kt * 16 + 4 * g;
@@ -170,30 +149,7 @@ __global__ __launch_bounds__(SG_WAVES * 64, 2) void attn_sigmoid_kernel(AttnPara
         if constexpr (MK == LAMP_MASK_BITS_U32 || MK == LAMP_MASK_NONE) return (word >> (4 * g)) & 0xfu;
         return (mbits | (tail >> (4 * g))) & 0xfu;
     };
-    // S^T = K Q^T for the tile staged in Ks (two accumulator chains, summed: the dependent-issue latency of the 16x16x4 MFMA
-    // is 40 cycles against 32 of issue)
-    auto scores = [&](f32x4& s) {
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-        const float* qp = Qs + l15 * QS + 4 * g;   // lane (query l15, group g): Q[q][16c + 4g + j]
-        const float* kp = Ks + l15 * QS + 4 * g;   // lane (key   l15, group g): K[k][16c + 4g + j]
-#pragma unroll
-        for (int c = 0; c < DKC; c += 2) {
-            const float4 qa = *reinterpret_cast<const float4*>(qp + 16 * c);
-            const float4 qb2 = *reinterpret_cast<const float4*>(qp + 16 * c + 16);
-            const float4 ka = *reinterpret_cast<const float4*>(kp + 16 * c);
-            const float4 kb = *reinterpret_cast<const float4*>(kp + 16 * c + 16);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.x, qa.x, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.x, qb2.x, s1, 0, 0, 0);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.y, qa.y, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.y, qb2.y, s1, 0, 0, 0);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.z, qa.z, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.z, qb2.z, s1, 0, 0, 0);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.w, qa.w, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.w, qb2.w, s1, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[r] = s0[r] + s1[r];
-    };
+    auto scores = [&](f32x4& s) { attn16_scores<DP>(Qs, Ks, l15, g, f32x4{0.f, 0.f, 0.f, 0.f}, s); };
 
     f32x4 o[DV8];
 #pragma unroll
@@ -287,18 +243,9 @@ __global__ __launch_bounds__(SG_WAVES * 64, 2) void attn_sigmoid_kernel(AttnPara
 
 template <int DP, int MK>
 int launch_sigmoid_mk(const AttnParams& p, int ksplit, hipStream_t s) {
-    const int QB = SG_WAVES / ksplit;
-    const size_t lds = size_t(QB + SG_WAVES) * 16 * (DP + SG_PAD) * sizeof(float);   // Q blocks + one K tile per wave (>= the merge)
-    constexpr size_t lds_max = size_t(2 * SG_WAVES) * 16 * (DP + SG_PAD) * sizeof(float);
-    auto kern = attn_sigmoid_kernel<DP, MK>;
-    if constexpr (lds_max > 65536) {
-        static AttrOnce once;
-        if (int e = once.set(reinterpret_cast<const void*>(kern), lds_max)) return e;
-    }
-    const int64_t nwg = int64_t((p.lq + 16 * QB - 1) / (16 * QB)) * p.H * p.B;
-    if (nwg > 0x7fffffffLL) return LAMP_E_DIMS;
-    hipLaunchKernelGGL(kern, dim3(unsigned(nwg)), dim3(SG_WAVES * 64), lds, s, p, ksplit);
-    return int(hipGetLastError());
+    const int QB = SG_WAVES / ksplit;   // Q blocks + one K tile per wave (>= the merge)
+    return attn16_launch<attn_sigmoid_kernel<DP, MK>, attn16_lds_bytes(SG_WAVES, SG_WAVES, DP, DP / 16)>(
+        p, QB, SG_WAVES, attn16_lds_bytes(QB, SG_WAVES, DP, ksplit > 1 ? DP / 16 : 0), s, ksplit);
 }
 
 template <int DP>
@@ -319,7 +266,7 @@ int launch_attn_sigmoid(const AttnParams& p, hipStream_t s) {
         return LAMP_E_UNSUPPORTED;  // the sparsity hint belongs to shared masks
     // Key shares from the (padded) key count; the kernel lowers them per sample from kv_len[b].  Padded self-attention without
     // per-sample key counts: lk is only the padded length, and a split chosen from it would tie a sample's bits to its batch.
-    int ksplit = sg_shares((p.lk + 15) / 16);
+    int ksplit = attn16_key_shares((p.lk + 15) / 16);
     if (p.self_ragged && !p.kv_len) ksplit = 1;
     const int dmax = p.dk > p.dv ? p.dk : p.dv;
     if (dmax <= 32) return launch_sigmoid_dp<32>(p, ksplit, s);

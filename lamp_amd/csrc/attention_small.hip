@@ -19,50 +19,10 @@
 //     (first tile, or a tile maximum 2^32 above the running one); the row SUM stays a per-lane partial until the end.
 // Variant (KSPLIT) and kernel choice depend on the per-sample shape only, never on the batch: a sample's bits do not
 // depend on the batch it is in.
-#include "lamp_kernels.h"
+// attention_sigmoid.hip and attention_bias.hip use the same decomposition; attn16_frag.h holds the code the three share.
+#include "attn16_frag.h"
 
 namespace lamp {
-
-// LDS row padding of the Q block / K tiles: 8 floats.  With 4 (rounds 2-3) the sixteen lanes ds_read_b128 serves together
-// -- rows 0-3 and 12-15 at one k-quad, rows 4-11 at the next (MI355X_MICROARCH.md, LDS lane groups) -- met two by two on a
-// 16-byte slot: 29 % of the kernel's LDS cycles were bank conflicts (profiles/r02_attn_ta_pmc.txt); with 8 none do.
-#ifndef LAMP_LDS_PAD16
-#define LAMP_LDS_PAD16 8
-#endif
-constexpr int ATTN16_PAD = LAMP_LDS_PAD16;
-
-namespace {
-// Exchange across the four lane groups of a query (lanes l, l^16, l^32, l^48) with gfx950's row-swap instructions instead
-// of __shfl_xor (= ds_bpermute through the LDS crossbar, ~100 cycles a step):
-//   v_permlane16_swap a, b  swaps the odd 16-lane rows of a with the even rows of b;  v_permlane32_swap a, b swaps the
-//   upper half of a with the lower half of b.  Starting from a = b = v, a and b then hold the two partners of every lane.
-// (Inline asm: the builtins return their second result equal to the first in hipcc 7.2 -- DESIGN.md 4.4.  Only used in
-// the rescale branch and after the key loop, where the scheduling barrier an asm statement implies costs nothing.)
-// The s_nop pairs: hipcc cannot see inside an asm statement, so the wait states it would insert between a VALU write and
-// a permlane swap reading it (and between the swap and its consumers) are spelled out.
-__device__ __forceinline__ void swap16(float& a, float& b) {
-    asm volatile("s_nop 3\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 3" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ void swap32(float& a, float& b) {
-    asm volatile("s_nop 3\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 3" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ float group_max(float v) {  // max over the 4 lane groups
-    float a = v, b = v;
-    swap16(a, b);
-    a = fmaxf(a, b);
-    b = a;
-    swap32(a, b);
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float group_sum(float v) {  // (v[l] + v[l^16]) + (v[l^32] + v[l^48]), the pairing of the xor butterfly
-    float a = v, b = v;
-    swap16(a, b);
-    a = a + b;
-    b = a;
-    swap32(a, b);
-    return a + b;
-}
-}  // namespace
 
 // PM = 0: O only.  PM = 2: additionally the scaled scores (log2 domain, -inf where blocked) into the map buffer and each
 // row's log2-sum-exp into lse; softmax_from_scores_kernel (attention.hip) then normalises in place.
@@ -113,10 +73,8 @@ __global__ __launch_bounds__(QB* KSPLIT * 64, 3) void attn16_kernel(AttnParams p
     const int64_t v_row0 = p.kv_len ? int64_t(row0) * v_r : int64_t(b) * p.lay.v_b;
     const __amdgpu_buffer_rsrc_t rsQ = make_rsrc(p.Q + int64_t(b) * p.lay.q_b + int64_t(h) * p.lay.q_h,
                                                  (uint64_t(p.lq - 1) * q_r + p.dk) * 4u);
-    const __amdgpu_buffer_rsrc_t rsK = make_rsrc(p.K + k_row0 + int64_t(h) * p.lay.k_h,
-                                                 lk_b > 0 ? (uint64_t(lk_b - 1) * k_r + p.dk) * 4u : 0);
-    const __amdgpu_buffer_rsrc_t rsV = make_rsrc(p.V + v_row0 + int64_t(h) * p.lay.v_h,
-                                                 lk_b > 0 ? (uint64_t(lk_b - 1) * v_r + p.dv) * 4u : 0);
+    const __amdgpu_buffer_rsrc_t rsK = attn16_rsrc_rows(p.K + k_row0 + int64_t(h) * p.lay.k_h, lk_b, k_r, p.dk);
+    const __amdgpu_buffer_rsrc_t rsV = attn16_rsrc_rows(p.V + v_row0 + int64_t(h) * p.lay.v_h, lk_b, v_r, p.dv);
     const __amdgpu_buffer_rsrc_t rsM =
         MK == LAMP_MASK_BITS_U32
             ? make_rsrc(static_cast<const unsigned*>(p.mask) + int64_t(b) * p.m_sb,
@@ -157,7 +115,7 @@ __global__ __launch_bounds__(QB* KSPLIT * 64, 3) void attn16_kernel(AttnParams p
     const int nt = PM == 2 ? (p.lk + 15) / 16 : nt_b;
     // key shares in use: the launch's KSPLIT, or -- ragged batches -- the share count launch_attn_small would choose for
     // THIS sample's key count (<= KSPLIT: the launch was sized for the padded length); the other waves idle
-    const int ks_eff = (KSPLIT > 1 && p.kv_len) ? (nt_b >= 12 ? (KSPLIT < 4 ? KSPLIT : 4) : (nt_b >= 4 ? 2 : 1)) : KSPLIT;
+    const int ks_eff = (KSPLIT > 1 && p.kv_len) ? ATTN16_KEY_SHARES(nt_b, KSPLIT) : KSPLIT;
     float4 kg[DKC];        // the NEXT tile's K rows in flight (coalesced layout: row = i * RPI + lane / C4K, float4 lane % C4K)
     constexpr int C4K = DP / 4, RPI = 64 / C4K;   // float4 per K row; rows per load instruction
     float vf[4][DV8];      // V[kt*16 + 4g + r][.]: block e of O^T holds the d_v columns given at load_v below
@@ -184,24 +142,7 @@ __global__ __launch_bounds__(QB* KSPLIT * 64, 3) void attn16_kernel(AttnParams p
     // d_v is a multiple of 4: all-or-nothing per load; second half (d = 128 only) 64 columns on
     const unsigned v_voff = DVW * l15 < p.dv ? unsigned(4 * g * v_r + DVW * l15) * 4u : OOB;
     const unsigned v_voff2 = 64 + DVW * l15 < p.dv ? unsigned(4 * g * v_r + DVW * l15) * 4u + 256u : OOB;
-    auto load_v = [&](int kt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const unsigned off = v_voff, so = unsigned((kt * 16 + r) * v_r) * 4u;
-            if constexpr (DV8 == 8) {
-                const float4 a = bload4(rsV, off, so);
-                const float4 c2 = bload4(rsV, v_voff2, so);
-                vf[r][0] = a.x; vf[r][1] = a.y; vf[r][2] = a.z; vf[r][3] = a.w;
-                vf[r][4] = c2.x; vf[r][5] = c2.y; vf[r][6] = c2.z; vf[r][7] = c2.w;
-            } else if constexpr (DV8 == 4) {
-                const float4 a = bload4(rsV, off, so);
-                vf[r][0] = a.x; vf[r][1] = a.y; vf[r][2] = a.z; vf[r][3] = a.w;
-            } else {
-                const f32x2 a = bload2(rsV, off + so);
-                vf[r][0] = a.x; vf[r][1] = a.y;
-            }
-        }
-    };
+    auto load_v = [&](int kt) { attn16_load_v<DP>(vf, rsV, v_voff, v_voff2, kt, v_r); };
     const unsigned m_voff = unsigned(int64_t(qc) * p.m_sq) * 4u;
     auto load_mask = [&](int kt) {
         const int kbase = kt * 16 + 4 * g;
@@ -238,38 +179,14 @@ __global__ __launch_bounds__(QB* KSPLIT * 64, 3) void attn16_kernel(AttnParams p
         // poisons that query's row here, while the reference stays finite.  Finite inputs (every model this path serves) are
         // unaffected; attention_tile.hip does the same; attention_sparse.hip never touches a blocked key at all.  Pinned by
         // tests/test_gpu_parity.py::test_non_finite_key_behind_a_blocked_key_is_a_documented_deviation.
-        f32x4 s0, s1 = {0.f, 0.f, 0.f, 0.f};
+        f32x4 s0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             int t;
             asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(t) : "v"(mine), "n"(r));
             s0[r] = __int_as_float(t & int(0xff800000u));
         }
-#ifdef LAMP_SETPRIO   // experiment (profiles/r04_setprio.txt): raised wave priority around the QK^T and PV MFMA runs
-        __builtin_amdgcn_s_setprio(1);
-#endif
-        const float* qp = Qs + l15 * QS + 4 * g;   // lane (query l15, group g): Q[q][16c + 4g + j]
-        const float* kp = Ks + l15 * QS + 4 * g;   // lane (key   l15, group g): K[k][16c + 4g + j]
-#pragma unroll
-        for (int c = 0; c < DKC; c += 2) {
-            const float4 qa = *reinterpret_cast<const float4*>(qp + 16 * c);
-            const float4 qb2 = *reinterpret_cast<const float4*>(qp + 16 * c + 16);
-            const float4 ka = *reinterpret_cast<const float4*>(kp + 16 * c);
-            const float4 kb = *reinterpret_cast<const float4*>(kp + 16 * c + 16);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.x, qa.x, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.x, qb2.x, s1, 0, 0, 0);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.y, qa.y, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.y, qb2.y, s1, 0, 0, 0);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.z, qa.z, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.z, qb2.z, s1, 0, 0, 0);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ka.w, qa.w, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kb.w, qb2.w, s1, 0, 0, 0);
-        }
-#ifdef LAMP_SETPRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[r] = s0[r] + s1[r];
+        attn16_scores<DP>(Qs, Ks, l15, g, s0, s);
     };
 
     f32x4 o[DV8];
@@ -426,18 +343,8 @@ __global__ __launch_bounds__(QB* KSPLIT * 64, 3) void attn16_kernel(AttnParams p
 template <int DP, int QB, int KSPLIT, int PM, int MK>
 static int launch_small_mk(const AttnParams& p, hipStream_t s) {
     constexpr int NW = QB * KSPLIT;
-    constexpr size_t lds_q = size_t(QB + NW) * 16 * (DP + ATTN16_PAD) * sizeof(float);   // Q blocks + one K tile per wave
-    constexpr size_t lds_c = KSPLIT > 1 ? size_t(NW) * (DP / 16 * 4 + 4) * 64 * sizeof(float) : 0;
-    constexpr size_t lds = lds_q > lds_c ? lds_q : lds_c;
-    auto kern = attn16_kernel<DP, QB, KSPLIT, PM, MK>;
-    if constexpr (lds > 65536) {
-        static AttrOnce once;
-        if (int e = once.set(reinterpret_cast<const void*>(kern), lds)) return e;
-    }
-    const int64_t nwg = int64_t((p.lq + 16 * QB - 1) / (16 * QB)) * p.H * p.B;
-    if (nwg > 0x7fffffffLL) return LAMP_E_DIMS;
-    hipLaunchKernelGGL(kern, dim3(unsigned(nwg)), dim3(NW * 64), lds, s, p);
-    return int(hipGetLastError());
+    constexpr size_t lds = attn16_lds_bytes(QB, NW, DP, KSPLIT > 1 ? DP / 16 + 1 : 0);   // merge record: o blocks + (m, l)
+    return attn16_launch<attn16_kernel<DP, QB, KSPLIT, PM, MK>, lds>(p, QB, NW, lds, s);
 }
 
 template <int DP, int QB, int KSPLIT, int PM>
@@ -501,21 +408,18 @@ int launch_attn_small(const AttnParams& p_in, int force, hipStream_t s) {
     p.trace = g_attn_trace;
 #endif
     const int nt = (p.lk + 15) / 16;
-    const int nqb = (p.lq + 15) / 16;
-    // Key shares (measured, profiles/r02_attn_variants.txt): four from 12 sixteen-key tiles on (reuters enc-dec: 19), two
-    // from 4 (reuters' 90-label self-attention: 6; bibtex 7 / 10), else one.  Always four waves per workgroup: larger
+    // Key shares: attn16_key_shares' measured thresholds.  Always four waves per workgroup: larger
     // workgroups (several query blocks sharing their K / V tiles through L1) measured equal or slower on every shape
     // and exist for the tuning build's every-variant tests only.
     int ksplit = force & 7;
     if (ksplit != 1 && ksplit != 2 && ksplit != 4) {
-        ksplit = nt >= 12 ? 4 : (nt >= 4 ? 2 : 1);
+        ksplit = attn16_key_shares(nt);
         // padded self-attention without per-sample key counts (a per-sample byte mask): lk is the padded length, and a split
         // chosen from it would tie a sample's bits to its batch's padding
         if (p.self_ragged && !p.kv_len) ksplit = 1;
     }
     int qb = (force >> 4) & 7;
     if (qb < 1 || qb > 4) qb = 4 / ksplit;
-    (void)nqb;
     const int dmax = p.dk > p.dv ? p.dk : p.dv;
     if (dmax <= 32) return launch_small_dp<32>(p, qb, ksplit, s);
     if (dmax <= 64) return launch_small_dp<64>(p, qb, ksplit, s);

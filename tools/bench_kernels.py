@@ -707,37 +707,160 @@ def attn_tile(rounds=7):
 def attn_lib_ab(rounds=9):
     """A/B of BUILDS of the library (argv[2:]: paths) on the attention shapes of the forwards, heuristic variant, the
     masks the forward uses (bit-packed label graph for self-attention, none for enc-dec: the padding mask of a full-length
-    batch blocks nothing), round-robin medians in one process."""
+    batch blocks nothing), round-robin medians in one process.  Besides softmax: sigmoid attention and a biased softmax at
+    the reuters self-attention shape, and the reuters enc-dec shape at d = 32.  Every library writes its own output buffer;
+    `same bits`: torch.equal of each library's output against the first library's."""
     import statistics
     libs = [(os.path.basename(p), N.load_library(p)) for p in sys.argv[2:]]
     dev = torch.device('cuda:0')
-    cases = [('reuters enc-attn', 32, 4, 90, 302, 128, False), ('reuters self', 32, 4, 90, 90, 128, True),
-             ('bibtex enc-attn', 32, 4, 159, 100, 128, False), ('bibtex self', 32, 4, 159, 159, 128, True),
-             ('delicious enc-attn', 32, 8, 983, 40, 128, False), ('delicious self', 32, 8, 983, 983, 128, False),
-             ('synthetic self', 4, 8, 4096, 4096, 128, True), ('synthetic enc', 4, 8, 4096, 512, 128, False)]
-    print('%-22s' % 'shape (median us)' + ''.join('%28s' % n for n, _ in libs))
-    for name, B, H, lq, lk, dk, masked in cases:
+    cases = [('reuters enc-attn', 32, 4, 90, 302, 128, False, 'softmax'), ('reuters self', 32, 4, 90, 90, 128, True, 'softmax'),
+             ('bibtex enc-attn', 32, 4, 159, 100, 128, False, 'softmax'), ('bibtex self', 32, 4, 159, 159, 128, True, 'softmax'),
+             ('delicious enc-attn', 32, 8, 983, 40, 128, False, 'softmax'), ('delicious self', 32, 8, 983, 983, 128, False, 'softmax'),
+             ('synthetic self', 4, 8, 4096, 4096, 128, True, 'softmax'), ('synthetic enc', 4, 8, 4096, 512, 128, False, 'softmax'),
+             ('reuters self sigmoid', 32, 4, 90, 90, 128, True, 'sigmoid'), ('reuters self bias', 32, 4, 90, 90, 128, True, 'bias'),
+             ('reuters enc-attn d32', 32, 4, 90, 302, 32, False, 'softmax')]
+    print('%-22s' % 'shape (median us)' + ''.join('%28s' % n for n, _ in libs) + '   same bits')
+    for name, B, H, lq, lk, dk, masked, route in cases:
         q = torch.randn(B, lq, H * dk, device=dev)
         k = torch.randn(B, lk, H * dk, device=dev)
         v = torch.randn(B, lk, H * dk, device=dev)
-        o = torch.empty(B, lq, H * dk, device=dev)
+        outs = [torch.empty(B, lq, H * dk, device=dev) for _ in libs]
         mask = (torch.rand(lq, lk, device=dev) < 0.9).to(torch.uint8)
         mask[:, 0] = 0
         bits = N.pack_mask_bits(mask).to(dev)
         ms = N.Mask(N.LAMP_MASK_BITS_U32, 0, bits.data_ptr(), 0, bits.size(1)) if masked else None
+        if route == 'bias':   # the weighted label graph: log-weights on the allowed pairs, -inf on the blocked ones
+            ld = (lk + 3) & ~3
+            bias = torch.zeros(lq, ld, device=dev)
+            bias[:, :lk] = torch.where(mask != 0, torch.full((), float('-inf'), device=dev), torch.rand(lq, lk, device=dev).log())
+            ms = N.Mask(N.LAMP_MASK_BIAS_F32, 0, bias.data_ptr(), 0, ld)
         lay = N.AttnLayout(lq * H * dk, dk, H * dk, lk * H * dk, dk, H * dk, lk * H * dk, dk, H * dk,
                            lq * H * dk, dk, H * dk)
+        m = ctypes.byref(ms) if ms is not None else None
         samples = [[] for _ in libs]
         for _ in range(rounds):
             for i, (_, lib) in enumerate(libs):
+                o = outs[i]
+
                 def fn():
-                    N.check(lib.lamp_sdpa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), None, B, H, lq, lk, dk,
-                                              dk, dk ** -0.5, ctypes.byref(ms) if ms is not None else None,
-                                              ctypes.byref(lay), N.stream()), 'sdpa')
+                    if route == 'sigmoid':
+                        N.check(lib.lamp_sdpa_act_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), None, B, H, lq, lk,
+                                                      dk, dk, dk ** -0.5, N.LAMP_ATTN_SIGMOID, m, ctypes.byref(lay), N.stream()),
+                                'sdpa_act')
+                    else:
+                        N.check(lib.lamp_sdpa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), None, B, H, lq, lk, dk,
+                                                  dk, dk ** -0.5, m, ctypes.byref(lay), N.stream()), 'sdpa')
                 samples[i].append(time_fn(fn, iters=20, warm=3))
         fl = 4.0 * B * H * lq * lk * dk
         med = [statistics.median(x) for x in samples]
-        print('%-22s' % name + ''.join('%19.1f/%6.1fT ' % (m, fl / m / 1e6) for m in med))
+        same = ' '.join('yes' if torch.equal(o, outs[0]) else 'NO' for o in outs[1:])
+        print('%-22s' % name + ''.join('%19.1f/%6.1fT ' % (m_, fl / m_ / 1e6) for m_ in med) + '   ' + same)
+
+
+def _same_bits(a, b):
+    """bit equality of two fp32 tensors; NaNs are compared as positions (their payloads are not the kernels' to choose)"""
+    na, nb = torch.isnan(a), torch.isnan(b)
+    zero = torch.zeros((), device=a.device)
+    return torch.equal(na, nb) and torch.equal(torch.where(na, zero, a).view(torch.int32), torch.where(nb, zero, b).view(torch.int32))
+
+
+def attn_lib_bits():
+    """Bit check of BUILDS of the library (argv[2:]: paths; the first is the reference) on the three 16x16-fragment attention
+    kernels (attention_small / _sigmoid / _bias.hip), small shapes, a few seconds: 37 queries (a partial query block) against 40,
+    100 and 200 keys (3, 7, 13 key tiles = 1, 2, 4 key shares), four head geometries (all three padded widths, d_k != d_v),
+    batch 2 x 2 heads, seeded inputs.  Routes: softmax and sigmoid under each of the four mask kinds, bias shared and per
+    sample.  Outputs: O only; maps with lse (softmax, bias); maps without lse (the bias kernel's two passes; sigmoid with and
+    without V).  Ragged keys (per-sample key counts) reach the kernels through lamp_mha_fwd / lamp_mha_act_fwd with a key-token
+    mask -- the lamp_sdpa_* entries take none -- so each geometry also runs those two, O only and with maps, at d_model 64: the
+    second sample is PAD from two thirds on.  One line per case, exit status 1 on any difference."""
+    libs = [(os.path.basename(p), N.load_library(p)) for p in sys.argv[2:]]
+    dev = torch.device('cuda:0')
+    gen = torch.Generator().manual_seed(20)
+    B, H, lq = 2, 2, 37
+    bad = total = 0
+    neg_inf = float('-inf')
+    for lk in (40, 100, 200):
+        blocked = torch.rand(B, lq, lk, generator=gen) < 0.3
+        blocked[:, :, 0] = False
+        blocked[1, 5, :] = True            # a fully blocked row: NaN under softmax, 0 under sigmoid
+        blocked[0, :, 16:32] = True        # a fully blocked key tile
+        u8 = blocked.to(torch.uint8).to(dev)
+        bits = N.pack_mask_bits(u8[0]).to(dev)
+        toks = torch.randint(1, 50, (B, lk), generator=gen)
+        toks[1, 2 * lk // 3:] = 0
+        toks = toks.to(dev)
+        ld = (lk + 3) & ~3
+        bias = torch.zeros(B, lq, ld)
+        bias[:, :, :lk] = torch.where(blocked, torch.full((), neg_inf), torch.randn(B, lq, lk, generator=gen))
+        bias = bias.to(dev)
+        masks = {'none': None, 'u8': N.Mask(N.LAMP_MASK_U8, 0, u8.data_ptr(), lq * lk, lk),
+                 'tokens': N.Mask(N.LAMP_MASK_KEY_TOKENS_I64, 0, toks.data_ptr(), lk, 0),
+                 'bits': N.Mask(N.LAMP_MASK_BITS_U32, 0, bits.data_ptr(), 0, bits.size(1)),
+                 'bias shared': N.Mask(N.LAMP_MASK_BIAS_F32, 0, bias.data_ptr(), 0, ld),
+                 'bias per sample': N.Mask(N.LAMP_MASK_BIAS_F32, 0, bias.data_ptr(), lq * ld, ld)}
+        for dk, dv in ((32, 32), (20, 36), (64, 48), (128, 128)):
+            q, k, v = (torch.randn(B, l, H * d, generator=gen).to(dev) for l, d in ((lq, dk), (lk, dk), (lk, dv)))
+            scale = dk ** -0.5
+
+            def run(lib, route, ms, mode):
+                """-> the tensors the call wrote (fresh buffers per call)"""
+                act = N.LAMP_ATTN_SIGMOID if route == 'sigmoid' else N.LAMP_ATTN_SOFTMAX
+                if mode == 'O':
+                    return N.sdpa_fused(q, k, v, H, ms, scale, need_attn=False, act=act, _lib=lib)[:1]
+                if mode == 'maps+lse':
+                    return N.sdpa_fused(q, k, v, H, ms, scale, need_attn=True, fast_maps=True, return_lse=True, _lib=lib)
+                if mode == 'maps':
+                    return N.sdpa_fused(q, k, v, H, ms, scale, need_attn=True, act=act, _lib=lib)
+                attn = torch.empty(H * B, lq, lk, device=dev)   # 'maps, no V'
+                lay = N.AttnLayout(lq * H * dk, dk, H * dk, lk * H * dk, dk, H * dk, lk * H * dv, dv, H * dv, lq * H * dv, dv, H * dv)
+                N.check(lib.lamp_sdpa_act_fwd(q.data_ptr(), k.data_ptr(), None, None, attn.data_ptr(), B, H, lq, lk, dk, dv, scale,
+                                              act, ctypes.byref(ms) if ms is not None else None, ctypes.byref(lay), N.stream()),
+                        'sdpa_act')
+                return (attn,)
+
+            plan = [('softmax', mk, mode) for mk in ('none', 'u8', 'tokens', 'bits') for mode in ('O', 'maps+lse')]
+            plan += [('sigmoid', mk, mode) for mk in ('none', 'u8', 'tokens', 'bits') for mode in ('O', 'maps', 'maps, no V')]
+            plan += [('bias', mk, mode) for mk in ('bias shared', 'bias per sample') for mode in ('O', 'maps+lse', 'maps')]
+            for route, mk, mode in plan:
+                res = [run(lib, route, masks[mk], mode) for _, lib in libs]
+                torch.cuda.synchronize()
+                verdict = ['same bits' if all(_same_bits(a, b) for a, b in zip(r, res[0])) else 'DIFFERENT' for r in res[1:]]
+                total += 1
+                bad += 'DIFFERENT' in verdict
+                print('lq %d lk %3d d_k %3d d_v %3d  %-8s %-16s %-11s %s' % (lq, lk, dk, dv, route, mk, mode, ' '.join(verdict)))
+            # ragged keys: lamp_mha_fwd / lamp_mha_act_fwd count each sample's keys from a key-token mask and hand the attention
+            # kernels kv_len / kv_off (per-sample key shares, descriptors that end at the sample's last key)
+            d = 64
+            wts = [(torch.randn(r, c, generator=gen) * c ** -0.5).to(dev) for r, c in ((H * dk, d), (H * dk, d), (H * dv, d), (d, H * dv))]
+            ln_g, ln_b = torch.ones(d, device=dev), torch.zeros(d, device=dev)
+            w = N.MhaWeights(*[t.data_ptr() for t in wts], ln_g.data_ptr(), ln_b.data_ptr(), H, 1)
+            xq, xkv = torch.randn(B, lq, d, generator=gen).to(dev), torch.randn(B, lk, d, generator=gen).to(dev)
+
+            def run_mha(lib, act, maps):
+                out = torch.empty(B, lq, d, device=dev)
+                attn = torch.empty(H * B, lq, lk, device=dev) if maps else None
+                ws = N.workspace(lib.lamp_mha_workspace_bytes(B, lq, lk, d, H, dk, dv), dev)
+                m = ctypes.byref(masks['tokens'])
+                a = attn.data_ptr() if maps else None
+                if act == N.LAMP_ATTN_SOFTMAX:
+                    N.check(lib.lamp_mha_fwd(xq.data_ptr(), xkv.data_ptr(), B, lq, lk, d, dk, dv, ctypes.byref(w), m, out.data_ptr(), a,
+                                             ws.data_ptr(), ws.numel(), N.stream()), 'mha')
+                else:
+                    N.check(lib.lamp_mha_act_fwd(xq.data_ptr(), xkv.data_ptr(), B, lq, lk, d, dk, dv, ctypes.byref(w), act, m,
+                                                 out.data_ptr(), a, ws.data_ptr(), ws.numel(), N.stream()), 'mha_act')
+                torch.cuda.synchronize()   # the workspace is shared between the calls
+                return (out.clone(), attn.clone()) if maps else (out.clone(),)
+
+            for route, act in (('softmax', N.LAMP_ATTN_SOFTMAX), ('sigmoid', N.LAMP_ATTN_SIGMOID)):
+                for maps in (False, True):
+                    res = [run_mha(lib, act, maps) for _, lib in libs]
+                    verdict = ['same bits' if all(_same_bits(a, b) for a, b in zip(r, res[0])) else 'DIFFERENT' for r in res[1:]]
+                    total += 1
+                    bad += 'DIFFERENT' in verdict
+                    print('lq %d lk %3d d_k %3d d_v %3d  %-8s %-16s %-11s %s' % (lq, lk, dk, dv, route, 'ragged (mha)', 'maps' if maps else 'O',
+                                                                                 ' '.join(verdict)))
+    print('%d cases, %d with a difference (%s)' % (total, bad, ' vs '.join(n for n, _ in libs)))
+    sys.exit(1 if bad else 0)
 
 
 def attn_one():
@@ -975,5 +1098,5 @@ def gemm_clock():
 if __name__ == '__main__':
     which = sys.argv[1] if len(sys.argv) > 1 else 'gemm'
     {'gemm': gemm, 'gemm_ab': gemm_ab, 'lib_ab': lib_ab, 'walk': walk, 'walk_pmc': walk_pmc, 'gemm_gen': gemm_gen, 'attn': attn, 'steady': steady, 'sparse': sparse, 'sparse_rows': sparse_rows,
-     'gemm_trace': gemm_trace, 'gemm_clock': gemm_clock, 'attn_lib_ab': attn_lib_ab, 'attn_tile': attn_tile, 'chain': chain, 'ln': ln, 'attn_one': attn_one, 'attn_maps': attn_maps, 'attn_trace': attn_trace, 'residency': residency, 'slab': slab, 'gemm_packed': gemm_packed,
+     'gemm_trace': gemm_trace, 'gemm_clock': gemm_clock, 'attn_lib_ab': attn_lib_ab, 'attn_lib_bits': attn_lib_bits, 'attn_tile': attn_tile, 'chain': chain, 'ln': ln, 'attn_one': attn_one, 'attn_maps': attn_maps, 'attn_trace': attn_trace, 'residency': residency, 'slab': slab, 'gemm_packed': gemm_packed,
      'gemm_packed_residency': gemm_packed_residency}[which]()
