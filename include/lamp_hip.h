@@ -963,6 +963,45 @@ int lamp_multilabel_loss_train(const float* const* logits, const float* weights,
                                const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
                                int64_t ld_row_loss, const lamp_loss_options* opts, lamp_stream_t stream);
 
+/* lamp_bce_logits_train with a RANKING objective: a row's positives are to score above its negatives.  Same leading arguments
+ * and conventions (<= 8 matrices, probs through ld_probs, row_loss through ld_row_loss, 64-bit row offsets, the caller's
+ * stream, no workspace, no allocation, no synchronisation).  For one row with logits x: P = {i : t_i > 0.5}, N = the other
+ * columns (the comparison as written: a NaN target is a negative; a target that is neither 0 nor 1 is the caller's business),
+ * n_p = |P|, n_n = |N|.  The ranking term R of the row:
+ *   LAMP_RANK_LSEP (Li et al., CVPR 2017)   R = log(1 + sum_p sum_n exp(x_n - x_p)), evaluated as softplus(z),
+ *       z = LSE_{n in N}(x_n) + LSE_{p in P}(-x_p): O(L) per row, no overflow (logits of +-1e4 give finite numbers);
+ *       dR/dx_n = sigmoid(z) exp(x_n - LSE_N),  dR/dx_p = -sigmoid(z) exp(-x_p - LSE_P).  Any L is served.
+ *   LAMP_RANK_HINGE      R = 1 / (n_p n_n) sum_p sum_n max(0, a_pn),  a_pn = margin + (x_n - x_p): the fp32 difference FIRST,
+ *       then the margin added to it -- that order decides on which side of the kink a pair lands.  A pair is active iff
+ *       a_pn > 0 (the subgradient at a_pn = 0 is 0); dR/dx_n = (active pairs of n) / (n_p n_n), dR/dx_p = -(those of p) / (n_p n_n).
+ *   LAMP_RANK_LOGISTIC   R = 1 / (n_p n_n) sum_p sum_n softplus(x_n - x_p)  (max(d, 0) + log1p(exp(-|d|)));
+ *       dR/dx_n = sum_p sigmoid(x_n - x_p) / (n_p n_n),  dR/dx_p = -sum_n sigmoid(x_n - x_p) / (n_p n_n).
+ * HINGE and LOGISTIC walk the pairs that exist: the row's positives and negatives are compacted in column order and every
+ * element loops over the opposite class only, n_p n_n evaluations per row and direction (loss + negatives' gradients,
+ * positives' gradients); L <= 4096 is served.  An empty class (n_p = 0 or n_n = 0): R = 0 and a zero ranking gradient; the
+ * row still counts in n_rows.  With beta = bce_weight the trained loss of matrix k is
+ *   loss_k = 1 / n_rows sum_r [ R_r + beta / L sum_i bce(x_ri, t_ri) ]       (bce as lamp_bce_logits_train has it)
+ *   dlogits[k][r, i]               = weights[k] * d loss_k / dx
+ *   row_loss[k * ld_row_loss + r]  = R_r + beta * bce_row_r / L              (the caller divides by n_rows, NOT by n_rows * L)
+ *   probs[r * ld_probs + i]        = sigmoid(logits[0][r, i])                (lamp_bce_logits_train's bits, every kind and beta)
+ * Row sums, the LSE sums and the mixing of the two terms run in double and are rounded once.  Every sum runs in an order
+ * fixed by L and the row's own target pattern (no atomics): a row's probs and row_loss are the same bits in any batch, its
+ * gradients up to the 1 / n_rows factor, and everything from run to run.  A NaN logit makes its row's loss and all of its
+ * row's gradients NaN and touches no other row (probs: its own element); a +-inf logit may give inf or NaN in its own row only.
+ * Validated before any launch, in this order: LAMP_E_DIMS and LAMP_E_NULL as lamp_bce_logits_train (opts == NULL is
+ * LAMP_E_NULL), then LAMP_E_UNSUPPORTED: an unknown kind, a non-finite or negative margin or bce_weight, margin != 0 outside
+ * HINGE, reserved != 0, n_mats > 8, L > 4096 for HINGE and LOGISTIC, n_rows >= 2^31. */
+enum lamp_rank_kind { LAMP_RANK_LSEP = 1, LAMP_RANK_HINGE = 2, LAMP_RANK_LOGISTIC = 3 };
+typedef struct lamp_rank_loss_options {
+    int32_t kind;        /* lamp_rank_kind */
+    float   margin;      /* HINGE only: finite, >= 0; must be 0 for the other two */
+    float   bce_weight;  /* beta >= 0, finite: weight of the row's mean BCE mixed in (0 = the ranking term alone) */
+    int32_t reserved;    /* 0 */
+} lamp_rank_loss_options;
+int lamp_rank_loss_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
+                         const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs,
+                         float* row_loss, int64_t ld_row_loss, const lamp_rank_loss_options* opts, lamp_stream_t stream);
+
 /* lamp_embed_bwd with a fixed summation order, for a training epoch that must be reproducible bit for bit (the embedding
  * gradient feeds optimizer.step(), train.py:47-48): d_emb[src_seq[t], :] += dout[t, :], the rows of a repeated token added in
  * ascending position order by ONE writer per table row -- no atomics.  Same arguments and contract as lamp_embed_bwd; the

@@ -152,6 +152,13 @@ class LossOptions(C.Structure):  # include/lamp_hip.h: lamp_loss_options
                 ('pos_weight', _vp)]
 
 
+class RankLossOptions(C.Structure):  # include/lamp_hip.h: lamp_rank_loss_options
+    _fields_ = [('kind', C.c_int32), ('margin', C.c_float), ('bce_weight', C.c_float), ('reserved', C.c_int32)]
+
+
+LAMP_RANK_LSEP, LAMP_RANK_HINGE, LAMP_RANK_LOGISTIC = 1, 2, 3      # lamp_rank_kind
+RANK_KINDS = {'lsep': LAMP_RANK_LSEP, 'hinge': LAMP_RANK_HINGE, 'logistic': LAMP_RANK_LOGISTIC}
+RANK_PAIR_MAX_L = 4096      # the widest row of the two pair kinds
 LAMP_OPTIM_ADAM, LAMP_OPTIM_SGD = 0, 1
 LAMP_OPTIM_DECOUPLED_DECAY, LAMP_OPTIM_SKIP_NONFINITE = 1, 2   # lamp_optim_ext.flags
 LAMP_GRAD_NORM_NO_CLIP = -1.0
@@ -248,6 +255,8 @@ PROTOTYPES = {
     'lamp_bce_logits_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
     'lamp_multilabel_loss_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64,
                                              C.POINTER(LossOptions), _vp]),
+    'lamp_rank_loss_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64,
+                                       C.POINTER(RankLossOptions), _vp]),
     'lamp_optim_step': (C.c_int, [C.POINTER(OptimEntry), _i32, _i32, _i64] + [C.c_double] * 4 + [_vp]),
     'lamp_grad_norm_workspace_bytes': (_sz, [C.POINTER(OptimEntry), _i32]),
     'lamp_grad_norm': (C.c_int, [C.POINTER(OptimEntry), _i32, C.c_double, _vp, _sz, _vp, _vp, _vp]),
@@ -272,7 +281,8 @@ PROTOTYPES = {
 LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs', 'lamp_forward_packs_kv', 'lamp_attn_bias_bwd_workspace_bytes', 'lamp_attn_bias_bwd',
                      'lamp_label_bias_fold', 'lamp_topk_labels', 'lamp_rank_at_k_workspace_bytes', 'lamp_rank_at_k',
                      'lamp_tune_thresholds_workspace_bytes', 'lamp_tune_thresholds', 'lamp_threshold_counts_vec',
-                     'lamp_multilabel_loss_train', 'lamp_grad_norm_workspace_bytes', 'lamp_grad_norm', 'lamp_optim_step_ext')
+                     'lamp_multilabel_loss_train', 'lamp_grad_norm_workspace_bytes', 'lamp_grad_norm', 'lamp_optim_step_ext',
+                     'lamp_rank_loss_train')
 
 _lib = None
 _lock = threading.Lock()
@@ -1207,6 +1217,37 @@ def multilabel_loss_train(logits, weights, targets, gamma_pos=0., gamma_neg=0., 
                                                            row_loss_out, want_grads, want_probs)
     opts = LossOptions(gamma_pos, gamma_neg, clip, 0, ptr(pos_weight))
     check(lib().lamp_multilabel_loss_train(*args, C.byref(opts), stream()), 'lamp_multilabel_loss_train')
+    return probs, grads, row_loss
+
+
+def check_rank_loss_options(kind, margin=0., bce_weight=0.):
+    """The parameter rules of lamp_rank_loss_train (include/lamp_hip.h) as ValueErrors -> (kind as the library's integer,
+    margin, bce_weight as Python floats).  `kind`: 'lsep', 'hinge', 'logistic' or the integer.  Needs no device."""
+    code = RANK_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+    if isinstance(code, bool) or not isinstance(code, int) or code not in RANK_KINDS.values():
+        raise ValueError('kind = %r: a ranking loss is one of %s' % (kind, ', '.join(sorted(RANK_KINDS))))
+    margin, bce_weight = C.c_float(float(margin)).value, C.c_float(float(bce_weight)).value     # as the library receives them
+    for name, v in (('margin', margin), ('bce_weight', bce_weight)):
+        if not 0.0 <= v < float('inf'):      # (NaN fails both)
+            raise ValueError('%s = %r: a finite number >= 0' % (name, v))
+    if code != LAMP_RANK_HINGE and margin != 0.0:
+        raise ValueError('margin = %r: only the hinge loss has a margin' % (margin,))
+    return code, margin, bce_weight
+
+
+def rank_loss_train(logits, weights, targets, kind, margin=0., bce_weight=0., probs_out=None, row_loss_out=None,
+                    want_grads=True, want_probs=True):
+    """lamp_rank_loss_train: bce_logits_train's launch with a ranking objective (include/lamp_hip.h has the definitions):
+    kind 'lsep', 'hinge' (with `margin`) or 'logistic', plus bce_weight x the row's MEAN BCE.  Same arguments otherwise and
+    the same tuple back; row_loss is R_r + bce_weight * bce_row_r / L, so a batch's mean divides by its rows alone.  A
+    parameter or a width that is not served is a ValueError before the library is called."""
+    code, margin, bce_weight = check_rank_loss_options(kind, margin, bce_weight)
+    if code != LAMP_RANK_LSEP and len(logits) and logits[0].dim() == 2 and logits[0].shape[1] > RANK_PAIR_MAX_L:
+        raise ValueError('rank_loss_train: the pairwise kinds serve L <= %d, not %d' % (RANK_PAIR_MAX_L, logits[0].shape[1]))
+    args, probs, grads, row_loss, _keep = _loss_train_call('rank_loss_train', logits, weights, targets, probs_out, row_loss_out,
+                                                           want_grads, want_probs)
+    opts = RankLossOptions(code, margin, bce_weight, 0)
+    check(lib().lamp_rank_loss_train(*args, C.byref(opts), stream()), 'lamp_rank_loss_train')
     return probs, grads, row_loss
 
 

@@ -8,6 +8,9 @@
 //               it travels in.  No atomics, no scratch.
 //   multilabel_loss_train  the same launch for the objectives of imbalanced label sets: per-label positive weights, focal
 //               and asymmetric loss, specialised at compile time on "has an exponent" and "has a margin".
+//   rank_loss_train  the same launch for ranking objectives: LSEP in O(L) per row (one wave per (matrix, row)), and the pairwise
+//               hinge and logistic losses over the pairs that exist (one workgroup per (matrix, row), the row's positives and
+//               negatives compacted in LDS, every element against the opposite class only), each plus a share of the mean BCE.
 //   optim_step  Adam (torch.optim.Adam's single-tensor arithmetic, no weight decay, no amsgrad) or plain SGD over EVERY
 //               parameter of the model in one launch.  The table of (param, grad, exp_avg, exp_avg_sq, numel) travels in the
 //               kernel arguments (OPTIM_TABLE entries per launch); a workgroup owns one OPTIM_CHUNK-element chunk of one
@@ -169,6 +172,282 @@ __global__ __launch_bounds__(256) void multilabel_loss_train_kernel(const LossTr
     }
     loss = wave64_sum_f64(loss);
     if (lane == 0 && p.row_loss) p.row_loss[int64_t(k) * p.ld_loss + row] = float(loss);
+}
+
+// ---- lamp_rank_loss_train (include/lamp_hip.h): a row's positives against its negatives ------------------------------
+constexpr int RANK_PAIR_MAX_L = 4096;    // HINGE / LOGISTIC: the row lives in LDS (16 KB of logits + 8 KB of column numbers)
+
+struct RankTrainParams {
+    const float* logits[BCE_MAX_MATS];
+    float* dlogits[BCE_MAX_MATS];
+    double coef[BCE_MAX_MATS];           // weight_k / n_rows
+    const float* targets;
+    float* probs;
+    float* row_loss;
+    int64_t n_rows, ld_probs, ld_loss;
+    double beta_over_L;                  // bce_weight / L (0: the ranking term alone, the BCE term is not evaluated)
+    float margin;
+    int L;
+};
+
+__device__ __forceinline__ float wave64_max(float v) {       // wave64_sum's steps with fmaxf (which drops a NaN)
+    v = fmaxf(v, dpp_move<0xB1>(v));
+    v = fmaxf(v, dpp_move<0x4E>(v));
+    v = fmaxf(v, dpp_move<0x141>(v));
+    v = fmaxf(v, dpp_move<0x140>(v));
+    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
+    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
+    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
+    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
+    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+}
+
+// bce_train_kernel's element: the probability (its bits), d bce / dx and the loss term
+__device__ __forceinline__ void bce_element(float x, float t, float& s, float& dx, float& loss) {
+    const float e = expf(-fabsf(x));
+    const float r = 1.0f / (1.0f + e);
+    const float big = r, small = e * r;
+    s = x >= 0.f ? big : small;
+    const float ns = x >= 0.f ? small : big;
+    dx = (1.0f - t) * s - t * ns;
+    loss = fmaxf(x, 0.f) - x * t + log1pf(e);
+}
+
+// LSEP in bce_train_kernel's geometry, one wave per (matrix, row), three passes over the row (the second and third hit the
+// cache): class maxima and counts (+ the BCE side), the two exponential sums in double, the gradients.
+//   R = softplus(z), z = (max_N + log sum_n exp(x_n - max_N)) + (max_P + log sum_p exp(-x_p - max_P)), in double;
+//   dR/dx_n = sigmoid(z) exp(x_n - max_N) / sum_N,  dR/dx_p = -sigmoid(z) exp(-x_p - max_P) / sum_P.
+__global__ __launch_bounds__(256) void rank_lsep_train_kernel(const RankTrainParams p) {
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t row = int64_t(blockIdx.x) * 4 + (int(threadIdx.x) >> 6);
+    const int k = int(blockIdx.y);
+    if (row >= p.n_rows) return;
+    const int L = p.L;
+    const float* __restrict__ x_row = p.logits[k] + row * L;
+    const float* __restrict__ t_row = p.targets + row * L;
+    float* __restrict__ d_row = p.dlogits[k] ? p.dlogits[k] + row * L : nullptr;
+    float* __restrict__ p_row = (k == 0 && p.probs) ? p.probs + row * p.ld_probs : nullptr;
+    const bool mix = p.beta_over_L != 0.0;
+    const float NEG_INF = -__builtin_inff();
+    float max_n = NEG_INF, max_p = NEG_INF;
+    int n_p = 0;
+    bool nan = false;
+    double bce = 0.0;
+    for (int c = 0; c < L; c += 64) {                // (whole waves to the ballot)
+        const int i = c + lane;
+        const bool valid = i < L;
+        const float x = valid ? x_row[i] : 0.f, t = valid ? t_row[i] : 0.f;
+        const bool pos = valid && t > 0.5f;
+        n_p += __builtin_popcountll(__builtin_amdgcn_ballot_w64(pos));
+        if (valid) {
+            nan |= x != x;
+            if (pos) max_p = fmaxf(max_p, -x);
+            else max_n = fmaxf(max_n, x);
+            if (p_row || mix) {
+                float s, dx, l;
+                bce_element(x, t, s, dx, l);
+                if (p_row) p_row[i] = s;
+                bce += double(l);
+            }
+        }
+    }
+    const bool has_nan = __builtin_amdgcn_ballot_w64(nan) != 0;
+    const bool ranked = n_p > 0 && n_p < L;          // an empty class: R = 0, no ranking gradient
+    double R = 0.0, g_n = 0.0, g_p = 0.0;            // g_n = sigmoid(z) / sum_N, g_p = -sigmoid(z) / sum_P
+    if (ranked) {
+        max_n = wave64_max(max_n);
+        max_p = wave64_max(max_p);
+        double sum_n = 0.0, sum_p = 0.0;
+        for (int i = lane; i < L; i += 64) {
+            const float x = x_row[i];
+            if (t_row[i] > 0.5f) sum_p += double(expf(-x - max_p));
+            else sum_n += double(expf(x - max_n));
+        }
+        sum_n = wave64_sum_f64(sum_n);
+        sum_p = wave64_sum_f64(sum_p);
+        const double z = (double(max_n) + log(sum_n)) + (double(max_p) + log(sum_p));
+        const double ez = exp(-fabs(z));
+        const double sig = z >= 0.0 ? 1.0 / (1.0 + ez) : ez / (1.0 + ez);
+        R = fmax(z, 0.0) + log1p(ez);
+        g_n = sig / sum_n;
+        g_p = -sig / sum_p;
+    }
+    const double NAN64 = __builtin_nan("");
+    if (d_row) {
+        const double coef = p.coef[k];
+        for (int i = lane; i < L; i += 64) {
+            const float x = x_row[i], t = t_row[i];
+            double g = 0.0;
+            if (ranked) g = t > 0.5f ? g_p * double(expf(-x - max_p)) : g_n * double(expf(x - max_n));
+            if (mix) {
+                float s, dx, l;
+                bce_element(x, t, s, dx, l);
+                g += p.beta_over_L * double(dx);
+            }
+            d_row[i] = float(has_nan ? NAN64 : coef * g);
+        }
+    }
+    if (mix) R += p.beta_over_L * wave64_sum_f64(bce);
+    if (lane == 0 && p.row_loss) p.row_loss[int64_t(k) * p.ld_loss + row] = float(has_nan ? NAN64 : R);
+}
+
+// The pair kinds: one workgroup per (matrix, row).  The row's logits are compacted into LDS in column order, positives in
+// xs[0, n_p), negatives in xs[n_p, L), col[] the column of each slot; wave w compacts columns [w Q, (w + 1) Q) by ballots, its
+// offsets from one count pass.  An element then loops over the OPPOSITE class only: n_p n_n evaluations per direction.
+__device__ __forceinline__ double block_sum_f64(double v, double* red, int tid) {
+    v = wave64_sum_f64(v);
+    __syncthreads();                                 // (red may still be read from the sum before)
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One element against slots [lo, hi) of the opposite class -> LOGISTIC: sum of sigmoid(x_n - x_p); HINGE: the number of
+// active pairs.  The negatives' direction also takes the loss.
+template <int KIND, bool NEG_OWN>
+__device__ __forceinline__ double pair_range(const float* xs, float x_own, int lo, int hi, float margin, double& loss) {
+    double g = 0.0;
+    int active = 0;
+    for (int o = lo; o < hi; ++o) {
+        const float d = NEG_OWN ? x_own - xs[o] : xs[o] - x_own;      // x_n - x_p
+        if (KIND == LAMP_RANK_HINGE) {
+            const float a = margin + d;                               // the difference first, then the margin
+            const bool on = a > 0.f;
+            active += on ? 1 : 0;
+            if (NEG_OWN) loss += on ? double(a) : 0.0;
+        } else {
+            const float e = expf(-fabsf(d));
+            const float r = 1.0f / (1.0f + e);
+            g += double(d >= 0.f ? r : e * r);
+            if (NEG_OWN) loss += double(fmaxf(d, 0.f)) + double(log1pf(e));
+        }
+    }
+    return KIND == LAMP_RANK_HINGE ? double(active) : g;
+}
+
+struct RankRow {                 // what finishing a slot needs
+    const float* t_row;
+    float* d_row;
+    double coef, inv_pairs, beta_over_L;
+    bool has_nan;
+};
+
+template <bool NEG_OWN>
+__device__ __forceinline__ void rank_finish_slot(const RankRow& r, const float* xs, const unsigned short* col, int slot, double g) {
+    if (!r.d_row) return;
+    const int c = int(col[slot]);
+    double v = NEG_OWN ? g * r.inv_pairs : -(g * r.inv_pairs);
+    if (r.beta_over_L != 0.0) {
+        float s, dx, l;
+        bce_element(xs[slot], r.t_row[c], s, dx, l);
+        v += r.beta_over_L * double(dx);
+    }
+    r.d_row[c] = float(r.has_nan ? __builtin_nan("") : r.coef * v);
+}
+
+// Every element of one class against the other.  With fewer than 256 own elements the opposite class is cut into S slices
+// (S a power of two, own_cnt S <= 256), one (slice, element) per thread, the S partial sums of an element added in slice
+// order: the order of every sum is a function of (n_p, n_n).
+template <int KIND, bool NEG_OWN>
+__device__ __forceinline__ void rank_direction(const RankRow& r, const float* xs, const unsigned short* col, double* part,
+                                               int own_base, int own_cnt, int opp_base, int opp_cnt, float margin, int tid,
+                                               double& loss) {
+    if (own_cnt <= 0) return;                        // (uniform over the workgroup, like every branch around a barrier here)
+    if (own_cnt >= 256 || opp_cnt <= 1) {
+        for (int e = tid; e < own_cnt; e += 256) {
+            const double g = pair_range<KIND, NEG_OWN>(xs, xs[own_base + e], opp_base, opp_base + opp_cnt, margin, loss);
+            rank_finish_slot<NEG_OWN>(r, xs, col, own_base + e, g);
+        }
+        return;
+    }
+    const int S = 1 << (31 - __builtin_clz(256 / own_cnt));
+    const int len = (opp_cnt + S - 1) / S;
+    if (tid < own_cnt * S) {
+        const int s = tid / own_cnt, e = tid - s * own_cnt;
+        const int lo = min(s * len, opp_cnt), hi = min(lo + len, opp_cnt);
+        part[tid] = pair_range<KIND, NEG_OWN>(xs, xs[own_base + e], opp_base + lo, opp_base + hi, margin, loss);
+    }
+    __syncthreads();
+    if (tid < own_cnt) {
+        double g = 0.0;
+        for (int s = 0; s < S; ++s) g += part[s * own_cnt + tid];
+        rank_finish_slot<NEG_OWN>(r, xs, col, own_base + tid, g);
+    }
+    __syncthreads();                                 // (part is the next direction's)
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void rank_pair_train_kernel(const RankTrainParams p) {
+    __shared__ float xs[RANK_PAIR_MAX_L];
+    __shared__ unsigned short col[RANK_PAIR_MAX_L];
+    __shared__ double part[256];
+    __shared__ double red[4];
+    __shared__ int wave_pos[4];
+    const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+    const int64_t row = int64_t(blockIdx.x);
+    const int k = int(blockIdx.y);
+    const int L = p.L;
+    const float* __restrict__ x_row = p.logits[k] + row * L;
+    const float* __restrict__ t_row = p.targets + row * L;
+    float* __restrict__ p_row = (k == 0 && p.probs) ? p.probs + row * p.ld_probs : nullptr;
+    const bool mix = p.beta_over_L != 0.0;
+    const int Q = ((L + 255) >> 8) << 6;             // columns per wave, a multiple of 64
+    const int lo = min(wave * Q, L), hi = min(lo + Q, L);
+    int mine = 0;
+    for (int c = lo; c < hi; c += 64) {
+        const int i = c + lane;
+        mine += __builtin_popcountll(__builtin_amdgcn_ballot_w64(i < hi && t_row[min(i, hi - 1)] > 0.5f));
+    }
+    if (lane == 0) wave_pos[wave] = mine;
+    __syncthreads();
+    int n_p = 0, base_p = 0;
+    for (int w = 0; w < 4; ++w) {
+        base_p += w < wave ? wave_pos[w] : 0;
+        n_p += wave_pos[w];
+    }
+    const int n_n = L - n_p;
+    int base_n = n_p + (lo - base_p);
+    bool nan = false;
+    double bce = 0.0;
+    for (int c = lo; c < hi; c += 64) {
+        const int i = c + lane;
+        const bool valid = i < hi;
+        const float x = valid ? x_row[i] : 0.f, t = valid ? t_row[i] : 0.f;
+        const bool pos = valid && t > 0.5f;
+        const unsigned long long m_pos = __builtin_amdgcn_ballot_w64(pos), m_neg = __builtin_amdgcn_ballot_w64(valid && !pos);
+        const unsigned long long below = (1ull << lane) - 1ull;
+        if (valid) {
+            const int slot = pos ? base_p + __builtin_popcountll(m_pos & below) : base_n + __builtin_popcountll(m_neg & below);
+            xs[slot] = x;
+            col[slot] = (unsigned short)(i);
+            nan |= x != x;
+            if (p_row || mix) {
+                float s, dx, l;
+                bce_element(x, t, s, dx, l);
+                if (p_row) p_row[i] = s;
+                bce += double(l);
+            }
+        }
+        base_p += __builtin_popcountll(m_pos);
+        base_n += __builtin_popcountll(m_neg);
+    }
+    RankRow r;
+    r.has_nan = __syncthreads_or(nan ? 1 : 0) != 0;  // (also: xs and col are complete)
+    r.t_row = t_row;
+    r.d_row = p.dlogits[k] ? p.dlogits[k] + row * L : nullptr;
+    r.coef = p.coef[k];
+    r.beta_over_L = p.beta_over_L;
+    const double pairs = double(n_p) * double(n_n);
+    r.inv_pairs = pairs > 0.0 ? 1.0 / pairs : 0.0;   // an empty class: the loops below are empty and R = 0
+    double loss = 0.0;
+    rank_direction<KIND, true>(r, xs, col, part, n_p, n_n, 0, n_p, p.margin, tid, loss);
+    if (r.d_row) {
+        double unused = 0.0;
+        rank_direction<KIND, false>(r, xs, col, part, 0, n_p, n_p, n_n, p.margin, tid, unused);
+    }
+    double R = block_sum_f64(loss, red, tid) * r.inv_pairs;
+    if (mix) R += p.beta_over_L * block_sum_f64(bce, red, tid);
+    if (tid == 0 && p.row_loss) p.row_loss[int64_t(k) * p.ld_loss + row] = float(r.has_nan ? __builtin_nan("") : R);
 }
 
 struct OptimEntry {
@@ -571,6 +850,48 @@ int lamp_multilabel_loss_train(const float* const* logits, const float* weights,
     else if (focus) hipLaunchKernelGGL((multilabel_loss_train_kernel<true, false>), grid, block, 0, hipStream_t(stream), q);
     else if (margin) hipLaunchKernelGGL((multilabel_loss_train_kernel<false, true>), grid, block, 0, hipStream_t(stream), q);
     else hipLaunchKernelGGL((multilabel_loss_train_kernel<false, false>), grid, block, 0, hipStream_t(stream), q);
+    return int(hipGetLastError());
+}
+
+static bool rank_weight_served(float v) { return v >= 0.f && v <= 3.402823466e38f; }   // finite and >= 0 (false for NaN)
+
+int lamp_rank_loss_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
+                         const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
+                         int64_t ld_row_loss, const lamp_rank_loss_options* opts, lamp_stream_t stream) {
+    if (n_rows <= 0 || L <= 0 || n_mats <= 0) return LAMP_E_DIMS;
+    if ((probs && ld_probs < L) || (row_loss && n_mats > 1 && ld_row_loss < n_rows)) return LAMP_E_DIMS;
+    if (!logits || !weights || !targets || !opts) return LAMP_E_NULL;
+    for (int k = 0; k < n_mats && k < BCE_MAX_MATS; ++k)
+        if (!logits[k]) return LAMP_E_NULL;
+    const int kind = opts->kind;
+    if (kind != LAMP_RANK_LSEP && kind != LAMP_RANK_HINGE && kind != LAMP_RANK_LOGISTIC) return LAMP_E_UNSUPPORTED;
+    if (!rank_weight_served(opts->margin) || !rank_weight_served(opts->bce_weight)) return LAMP_E_UNSUPPORTED;
+    if ((kind != LAMP_RANK_HINGE && opts->margin != 0.f) || opts->reserved != 0) return LAMP_E_UNSUPPORTED;
+    if (n_mats > BCE_MAX_MATS) return LAMP_E_UNSUPPORTED;
+    if (kind != LAMP_RANK_LSEP && L > RANK_PAIR_MAX_L) return LAMP_E_UNSUPPORTED;
+    if (n_rows >= (int64_t(1) << 31)) return LAMP_E_UNSUPPORTED;
+    RankTrainParams p{};
+    for (int k = 0; k < n_mats; ++k) {
+        p.logits[k] = logits[k];
+        p.dlogits[k] = dlogits ? dlogits[k] : nullptr;
+        p.coef[k] = double(weights[k]) / double(n_rows);
+    }
+    p.targets = targets;
+    p.probs = probs;
+    p.row_loss = row_loss;
+    p.n_rows = n_rows;
+    p.ld_probs = ld_probs;
+    p.ld_loss = ld_row_loss;
+    p.beta_over_L = double(opts->bce_weight) / double(L);
+    p.margin = opts->margin;
+    p.L = L;
+    const hipStream_t s = hipStream_t(stream);
+    if (kind == LAMP_RANK_LSEP)
+        hipLaunchKernelGGL(rank_lsep_train_kernel, dim3(unsigned((n_rows + 3) / 4), unsigned(n_mats)), dim3(256), 0, s, p);
+    else if (kind == LAMP_RANK_HINGE)
+        hipLaunchKernelGGL((rank_pair_train_kernel<LAMP_RANK_HINGE>), dim3(unsigned(n_rows), unsigned(n_mats)), dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL((rank_pair_train_kernel<LAMP_RANK_LOGISTIC>), dim3(unsigned(n_rows), unsigned(n_mats)), dim3(256), 0, s, p);
     return int(hipGetLastError());
 }
 

@@ -80,7 +80,9 @@ def parse(argv=None):
     ap.add_argument('-dropout', type=float, default=0.1)
     ap.add_argument('-dec_dropout', type=float, default=-1)
     ap.add_argument('-no_dec_self_att', action='store_true')
-    ap.add_argument('-loss', type=str, choices=['ce', 'adv', 'ranking'], default='ce')
+    ap.add_argument('-loss', type=str, choices=['ce', 'adv', 'ranking'], default='ce',
+                    help="parsed for compatibility with the reference (config_args.py:37) and, as there, ignored: '-loss ranking' "
+                         "trains nothing different.  The ranking objectives are -loss_fn lsep | rank_hinge | rank_logistic")
     ap.add_argument('-save_mode', type=str, choices=['all', 'best'], default='best')
     ap.add_argument('-encoder', type=str, choices=['rnn', 'graph', 'emb', 'mlp'], default='graph')
     ap.add_argument('-decoder', type=str, choices=['sa_m', 'rnn_m', 'sa_b', 'graph', 'mlp'], default='graph')
@@ -113,9 +115,11 @@ def parse(argv=None):
                     help="after each validation epoch fit one decision threshold per label on the valid predictions (lamp_amd/"
                          "metrics.py: tune_thresholds), report the test epoch's tuned_* figures and store label_thresholds / "
                          "tune_criterion in the checkpoint for run_eval -tune_thresholds checkpoint")
-    ap.add_argument('-loss_fn', type=str, choices=['bce', 'focal', 'asl'], default='bce',
+    ap.add_argument('-loss_fn', type=str, choices=['bce', 'focal', 'asl', 'lsep', 'rank_hinge', 'rank_logistic'], default='bce',
                     help="the TRAINED objective (lamp_multilabel_loss_train, DESIGN.md section 8.10): focal = -focal_gamma on both "
-                         "branches, asl = the asymmetric loss of -asl_gamma_pos / -asl_gamma_neg / -asl_clip.  Only the training "
+                         "branches, asl = the asymmetric loss of -asl_gamma_pos / -asl_gamma_neg / -asl_clip; or a ranking loss "
+                         "(lamp_rank_loss_train, section 8.12): lsep, rank_hinge (-rank_margin) or rank_logistic, each plus "
+                         "-rank_bce_weight x the mean BCE, the train loss then a mean over samples.  Only the training "
                          "loss changes: the valid and test losses stay plain BCE, so -save_mode best and runs with different "
                          "objectives stay comparable; the train column of losses.csv is the trained loss")
     ap.add_argument('-focal_gamma', type=float, default=2.0, help='focal loss: the focusing exponent (0, or 1 .. 16)')
@@ -123,10 +127,13 @@ def parse(argv=None):
     ap.add_argument('-asl_gamma_neg', type=float, default=4.0, help='asymmetric loss: the exponent of the negatives')
     ap.add_argument('-asl_clip', type=float, default=0.05,
                     help='asymmetric loss: the probability margin in [0, 1); a negative predicted below it is discarded')
+    ap.add_argument('-rank_margin', type=float, default=1.0, help='rank_hinge: the margin a positive must lead a negative by (>= 0)')
+    ap.add_argument('-rank_bce_weight', type=float, default=0.0,
+                    help='lsep / rank_hinge / rank_logistic: the weight of the mean BCE mixed into the ranking loss (>= 0)')
     ap.add_argument('-pos_weight', type=str, choices=['none', 'inv', 'sqrt_inv'], default='none',
                     help="per-label weights of the positives in the TRAINED loss, from the train split's label counts "
                          "(lamp_amd/data.py: label_pos_weight): inv = negatives / positives, sqrt_inv = its square root; "
-                         "combines with every -loss_fn; the valid and test losses stay plain BCE")
+                         "combines with bce, focal and asl (not with a ranking loss); the valid and test losses stay plain BCE")
     ap.add_argument('-pos_weight_cap', type=float, default=100.0, help='the largest weight, also given to a label without a positive')
     ap.add_argument('-max_grad_norm', type=float, default=None,
                     help='clip the gradient to this GLOBAL L2 norm before every update (DESIGN.md section 8.11): lamp = one '
@@ -155,12 +162,17 @@ DEFAULT_OPTIM_IMPL = 'torch'
 
 
 # -loss_fn -> the flags that parameterise it (they enter the results name and the checkpoint's settings only with it)
-LOSS_FN_FLAGS = {'bce': (), 'focal': ('focal_gamma',), 'asl': ('asl_gamma_pos', 'asl_gamma_neg', 'asl_clip')}
+LOSS_FN_FLAGS = {'bce': (), 'focal': ('focal_gamma',), 'asl': ('asl_gamma_pos', 'asl_gamma_neg', 'asl_clip'),
+                 'lsep': ('rank_bce_weight',), 'rank_hinge': ('rank_margin', 'rank_bce_weight'), 'rank_logistic': ('rank_bce_weight',)}
+# -loss_fn -> the kind of train.RankLossOptions (lamp_rank_loss_train)
+RANK_LOSS_FNS = {'lsep': 'lsep', 'rank_hinge': 'hinge', 'rank_logistic': 'logistic'}
 
 
 def loss_parameters(opt):
     """-loss_fn and its flags -> (gamma_pos, gamma_neg, clip) of lamp_multilabel_loss_train; ValueError for what it refuses."""
     from . import _native as N
+    if opt.loss_fn in RANK_LOSS_FNS:
+        raise ValueError('-loss_fn %s is a ranking loss: rank_loss_parameters' % opt.loss_fn)
     if opt.loss_fn == 'focal':
         return N.check_loss_options(opt.focal_gamma, opt.focal_gamma, 0.0)
     if opt.loss_fn == 'asl':
@@ -168,10 +180,31 @@ def loss_parameters(opt):
     return N.check_loss_options()
 
 
+def rank_loss_parameters(opt):
+    """A ranking -loss_fn and its flags -> (kind, margin, bce_weight) of train.RankLossOptions; ValueError for what
+    lamp_rank_loss_train refuses, and for -pos_weight beside it."""
+    from . import _native as N
+    kind = RANK_LOSS_FNS[opt.loss_fn]
+    if getattr(opt, 'pos_weight', 'none') != 'none':
+        raise ValueError('-pos_weight %s with -loss_fn %s: per-label positive weights belong to the BCE family (bce, focal, '
+                         'asl); a ranking loss has none' % (opt.pos_weight, opt.loss_fn))
+    margin = opt.rank_margin if kind == 'hinge' else 0.0
+    N.check_rank_loss_options(kind, margin, opt.rank_bce_weight)
+    return kind, margin, opt.rank_bce_weight
+
+
+def build_rank_loss(opt):
+    """-> the train.RankLossOptions of a ranking -loss_fn, or None."""
+    if opt.loss_fn not in RANK_LOSS_FNS:
+        return None
+    from .train import RankLossOptions
+    return RankLossOptions(*rank_loss_parameters(opt))
+
+
 def build_loss_options(opt, data, device):
     """-> the train.LossOptions of -loss_fn / -pos_weight (the weights from the TRAIN split's label counts), or None for plain
-    BCE: train_batch then makes the call it has always made."""
-    if opt.loss_fn == 'bce' and opt.pos_weight == 'none':
+    BCE -- train_batch then makes the call it has always made -- and for a ranking loss (build_rank_loss)."""
+    if (opt.loss_fn == 'bce' and opt.pos_weight == 'none') or opt.loss_fn in RANK_LOSS_FNS:
         return None
     from .train import LossOptions
     w = None
@@ -279,13 +312,16 @@ def derive(opt):
     if opt.loss_fn not in LOSS_FN_FLAGS:
         raise ValueError("-loss_fn %r: one of %s" % (opt.loss_fn, ', '.join(sorted(LOSS_FN_FLAGS))))
     for flag, default in (('focal_gamma', 2.0), ('asl_gamma_pos', 0.0), ('asl_gamma_neg', 4.0), ('asl_clip', 0.05),
-                          ('pos_weight_cap', 100.0)):
+                          ('pos_weight_cap', 100.0), ('rank_margin', 1.0), ('rank_bce_weight', 0.0)):
         setattr(opt, flag, float(getattr(opt, flag, default)))
     opt.pos_weight = getattr(opt, 'pos_weight', None) or 'none'
     if opt.pos_weight not in ('none', 'inv', 'sqrt_inv'):
         raise ValueError("-pos_weight %r: none, inv or sqrt_inv" % (opt.pos_weight,))
-    if opt.loss_fn != 'bce':
+    if opt.loss_fn in RANK_LOSS_FNS:
+        rank_loss_parameters(opt)
+    elif opt.loss_fn != 'bce':
         loss_parameters(opt)    # (refuses what the kernel does not serve, here and not in the first batch)
+    if opt.loss_fn != 'bce':
         name += '.lossfn_%s_%s' % (opt.loss_fn, '_'.join(str(getattr(opt, f)) for f in LOSS_FN_FLAGS[opt.loss_fn]))
     if opt.pos_weight != 'none':
         if not 0.0 < opt.pos_weight_cap < float('inf'):
@@ -389,13 +425,13 @@ def checkpoint_settings(opt):
     """The Namespace that travels in the checkpoint: plain values only, so that it unpickles anywhere.  `learn_label_bias`
     and `tune_thresholds` travel only when they are set: without the flags the settings are what they were before they
     existed.  Likewise `loss_fn` with the flags of the chosen objective, and `pos_weight` with its cap."""
-    drop = {'loss_options'}      # (the run's device-side object, None for plain BCE: never a setting)
+    drop = {'loss_options', 'rank_loss'}      # (the run's own objects, None for plain BCE: never a setting)
     loss_fn = getattr(opt, 'loss_fn', 'bce')
     if loss_fn == 'bce':
         drop.add('loss_fn')
     for fn, flags in LOSS_FN_FLAGS.items():
         if fn != loss_fn:
-            drop.update(flags)
+            drop.update(f for f in flags if f not in LOSS_FN_FLAGS.get(loss_fn, ()))
     if getattr(opt, 'pos_weight', 'none') == 'none':
         drop.update(('pos_weight', 'pos_weight_cap'))
     for f in OPTIM_CONTROL_FLAGS:      # (set flags travel, unset ones never)
@@ -446,6 +482,7 @@ def main(argv=None):
     model = model.to(device)       # (before the optimizer: torch's fused Adam wants device parameters at construction)
     optimizer = build_optimizer(model, opt)
     opt.loss_options = build_loss_options(opt, data, device)      # (None for plain BCE; never part of the checkpoint's settings)
+    opt.rank_loss = build_rank_loss(opt)                          # (likewise; None unless -loss_fn is a ranking loss)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=opt.lr_step_size, gamma=opt.lr_decay, last_epoch=-1)

@@ -9,7 +9,8 @@ twice as many with -int_preds), and torch's multi-tensor Adam (:48).  Here, symm
     of the epoch's device prediction matrix, d loss / d logits of the final prediction and of every int_preds intermediate,
     and the per-row loss sums -- then torch.autograd.backward from those gradients and optimizer.step(); with
     `opt.loss_options` (LossOptions: per-label positive weights, focal or asymmetric loss) that launch is
-    lamp_multilabel_loss_train, still one;
+    lamp_multilabel_loss_train, still one; with `opt.rank_loss` (RankLossOptions: LSEP, pairwise hinge or logistic, plus a
+    share of the mean BCE) it is lamp_rank_loss_train, still one;
   * the embedding gradient takes lamp_embed_bwd_ordered (one writer per table row instead of the atomic scatter-add; switched
     on for the epoch through training.ORDERED_EMBED_GRAD), so an epoch is reproducible bit for bit;
   * nothing comes back to the host inside the loop: no `.item()`, no copy, no synchronize.  Predictions and row sums come
@@ -113,6 +114,20 @@ class LossOptions(object):
         self.pos_weight = pos_weight
 
 
+class RankLossOptions(object):
+    """`opt.rank_loss`: train on a ranking objective (lamp_rank_loss_train): kind 'lsep', 'hinge' or
+    'logistic', the hinge margin (1 by default; the other two have none), and bce_weight x the row's mean BCE mixed in.
+    Not to be combined with `opt.loss_options`.  Parameters that are not served are refused here."""
+
+    def __init__(self, kind='lsep', margin=None, bce_weight=0.0):
+        if kind not in N.RANK_KINDS:
+            raise ValueError('kind = %r: a ranking loss is one of %s' % (kind, ', '.join(sorted(N.RANK_KINDS))))
+        if margin is None:
+            margin = 1.0 if kind == 'hinge' else 0.0
+        _, self.margin, self.bce_weight = N.check_rank_loss_options(kind, margin, bce_weight)
+        self.kind = kind
+
+
 def _loss_weights(n_mats, int_pred_weight):
     return [1.0] + [float(int_pred_weight)] * (n_mats - 1)
 
@@ -121,7 +136,8 @@ def train_batch(model, optimizer, opt, src, adj, gold_d, probs_rows, loss_rows):
     """The loop body (train.py:35-48) for one batch already on the device.  probs_rows (real, L) / loss_rows (n_mats, real):
     this batch's rows of the epoch's prediction matrix and loss-sum matrix.  `opt.loss_options` (a LossOptions, or absent / None
     for the reference's BCE) picks the trained objective: the loss launch is then lamp_multilabel_loss_train and the row sums
-    are that loss.  Nothing here waits for the device."""
+    are that loss.  `opt.rank_loss` (a RankLossOptions) picks a ranking objective instead: lamp_rank_loss_train, whose row
+    numbers are R_r + bce_weight * bce_row_r / L; both options together are a ValueError.  Nothing here waits for the device."""
     optimizer.zero_grad()
     pred, enc_output, *results = model(src, adj, None, gold_d, return_attns=opt.attns_loss, int_preds=opt.int_preds)
     mats = [pred]
@@ -134,8 +150,16 @@ def train_batch(model, optimizer, opt, src, adj, gold_d, probs_rows, loss_rows):
     grads = []
     M = N.BCE_TRAIN_MAX_MATS
     lo = getattr(opt, 'loss_options', None)
+    rl = getattr(opt, 'rank_loss', None)
+    if rl is not None and lo is not None:
+        raise ValueError('opt.rank_loss and opt.loss_options are both set: a ranking loss does not combine with focal, '
+                         'asymmetric or positive-weighted BCE')
     for k in range(0, len(mats), M):   # (more than 8 matrices: 5+ decoder layers with -int_preds)
-        if lo is None:
+        if rl is not None:
+            _, g, _ = N.rank_loss_train(mats[k:k + M], weights[k:k + M], gold_d, rl.kind, margin=rl.margin,
+                                        bce_weight=rl.bce_weight, probs_out=probs_rows if k == 0 else None,
+                                        row_loss_out=loss_rows[k:k + M], want_probs=k == 0)
+        elif lo is None:
             _, g, _ = N.bce_logits_train(mats[k:k + M], weights[k:k + M], gold_d, probs_out=probs_rows if k == 0 else None,
                                          row_loss_out=loss_rows[k:k + M], want_probs=k == 0)
         else:
@@ -161,7 +185,8 @@ def train_epoch(model, train_data, optimizer, opt, device=None, prefetch=8, stre
     `train_data` yields ((src_seq, src_pos), adj, tgt) batches of at most `train_data._batch_size` rows (TrainBatcher, or any
     iterable with `n_insts`, `__len__` and `_batch_size`); `opt` carries what the reference's loop reads: tgt_vocab_size,
     binary_relevance, int_preds, int_pred_weight, attns_loss (only changes return_attns, as in the reference), decoder, and
-    optionally `loss_options` (LossOptions): the third return value and 'row_loss' are then the TRAINED loss, not BCE.
+    optionally `loss_options` (LossOptions) or `rank_loss` (RankLossOptions): the third return value and 'row_loss' are then
+    the TRAINED loss, not BCE -- with a ranking loss a per-row number, whose batch mean divides by the rows alone, not by rows * L.
     `prefetch` = batches per stage of the producer thread (evaluate.py); `streams=2` issues the stage uploads on a stream of
     their own instead of in front of the stage's first forward.  Every batch's numbers are the same in every mode, bit for bit.
     `timeline` / `device_results` as in evaluate.test_epoch: 'probs' and 'targets' (n, L) stay on the device for
@@ -215,8 +240,10 @@ def train_epoch(model, train_data, optimizer, opt, device=None, prefetch=8, stre
     row_loss = row_loss_d[0].cpu().numpy().astype(np.float64)
     E._return_ring(ring)
     bce_total = 0.0
+    # a ranking loss is a per-ROW number (lamp_rank_loss_train has divided its BCE share by L already): its mean is over rows
+    per_row = 1 if getattr(opt, 'rank_loss', None) is not None else n_labels
     for lo, real in seen:   # the reference adds one python float per batch, the batch's MEAN loss (train.py:38-40)
-        bce_total += float(row_loss[lo:lo + real].sum()) / (real * n_labels)
+        bce_total += float(row_loss[lo:lo + real].sum()) / (real * per_row)
     if device_results is not None:
         device_results.update(probs=probs_d, targets=targets_d, rows=(0, n), row_loss=row_loss_d, batches=list(seen))
     return all_predictions, all_targets, bce_total
