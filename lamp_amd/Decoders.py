@@ -9,10 +9,25 @@ the device as uint8 and broadcast over batch and heads by the kernel, instead of
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import Constants, utils
 from . import _native as N
 from .Layers import DecoderLayer
+
+
+# optimizer.step() calls anywhere in the process (torch's global step hook; lamp_amd.optim's classes are torch.optim.Optimizer
+# subclasses and count too).  The weights-only tables of the eval path watch Parameter._version, and torch's fused
+# implementations (torch.optim.Adam / AdamW / SGD with fused=True) write the parameters WITHOUT moving it: this count stands in
+# the tables' keys beside the versions (current_label_bias below, LAMP._native_key), so the forward after a step rebuilds them.
+_optimizer_steps = [0]
+
+
+def _count_optimizer_step(optimizer, args, kwargs):
+    _optimizer_steps[0] += 1
+
+
+register_optimizer_step_post_hook(_count_optimizer_step)
 
 
 def build_label_mask(n_tgt_vocab, label_adj_matrix, label_mask):
@@ -103,6 +118,12 @@ class GraphDecoder(nn.Module):
             DecoderLayer(d_model, d_inner_hid, n_head, n_head2, d_k, d_v, dropout=dropout, dropout2=dropout2,
                          no_dec_self_att=no_dec_self_att, attn_type=attn_type, dec_attn_type=dec_attn_type) for _ in range(n_layers))
 
+    def __getstate__(self):
+        """copy.deepcopy / pickle: a copy has a bias buffer of its own, which nobody has folded the parameter into yet."""
+        state = self.__dict__.copy()
+        state['_label_bias_key'] = None
+        return state
+
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         """A state_dict without ``label_bias`` (a run with a constant bias or with none) loads into a learnable decoder, which
         keeps the bias it was built with: the graph starts from the prior and is trained from there."""
@@ -113,7 +134,8 @@ class GraphDecoder(nn.Module):
     def current_label_bias(self):
         """``label_bias_f32`` (or None), current with the learnable ``label_bias``: lamp_label_bias_fold writes the buffer in
         place when the parameter's version or address -- or the buffer's own, after .to() -- differ from the last fold's
-        (load_state_dict and optimizer steps bump the version; both are host integers, nothing is read back).  Outside
+        (load_state_dict and optimizer steps bump the version -- a fused torch optimizer does not: _optimizer_steps; all are host
+        integers, nothing is read back).  Outside
         training the fold is followed by a one-off stream synchronisation, as the other weights-only tables of the eval path
         are: forwards may be issued from several streams.  An nn.DataParallel replica folds its own copy of the parameter
         into a fresh buffer on every forward."""
@@ -126,7 +148,7 @@ class GraphDecoder(nn.Module):
                 buf = N.label_bias_fold(p.detach(), mask, torch.empty_like(buf))
             self.label_bias_f32 = buf
             return buf
-        key = (p._version, p.data_ptr(), buf.data_ptr(), N.ptr(mask))
+        key = (p._version, p.data_ptr(), buf.data_ptr(), N.ptr(mask), _optimizer_steps[0])
         if key != self._label_bias_key:
             N.label_bias_fold(p.detach(), mask, buf)
             if not self.training:

@@ -32,9 +32,25 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
-from .Decoders import GraphDecoder, MLPDecoder, RNNDecoder
+from .Decoders import GraphDecoder, MLPDecoder, RNNDecoder, _optimizer_steps
 from .Encoders import GraphEncoder, MLPEncoder, RNNEncoder
 from .SubLayers import XavierLinear
+
+
+# Registrations of a Parameter or a submodule anywhere in the process (nn.Module.__setattr__, register_parameter, add_module,
+# ModuleList.__setitem__ ... all run torch's global registration hooks).  LAMP._native_model() keeps the Parameter OBJECTS of its
+# first walk; it walks again once this count has moved, so `lin.weight = nn.Parameter(...)`, `encoder.src_word_emb =
+# nn.Embedding.from_pretrained(...)` and weight tying are seen by the next forward -- at the price of one integer comparison per
+# cache hit.  (Writes into a module's `_parameters` / `_modules` dicts behind nn.Module's back are not seen.)
+_registrations = [0]
+
+
+def _count_registration(module, name, value):
+    _registrations[0] += 1
+
+
+torch.nn.modules.module.register_module_parameter_registration_hook(_count_registration)
+torch.nn.modules.module.register_module_module_registration_hook(_count_registration)
 
 
 def _chain_pack(fc, w1, w2, keep):
@@ -148,6 +164,13 @@ class LAMP(nn.Module):
         self._native_cache = None
         self._param_list = None
 
+    def __getstate__(self):
+        """copy.deepcopy, pickle and torch.save(model): the cached descriptor (ctypes structures full of device addresses) and the
+        cached Parameter list stay behind -- a copy builds its own tables on its first forward."""
+        state = self.__dict__.copy()
+        state['_native_cache'] = state['_param_list'] = None
+        return state
+
     def get_trainable_parameters(self):
         """Everything but the frozen sinusoid table, and the one-hot encoder's identity table (reference: lamp/Models.py:97-107)."""
         frozen = set()
@@ -161,7 +184,9 @@ class LAMP(nn.Module):
     def invalidate_native_cache(self):
         """Drop the cached lamp_model descriptor and the hoisted layer-0 query projection.  Called by load_state_dict,
         train() / eval() and _apply (.to / .cuda); call it yourself after modifying weights through ``.data`` (in-place
-        updates via ``p.data`` do not bump ``p._version``, which is what the cache otherwise watches)."""
+        updates via ``p.data`` do not bump ``p._version``, which is what the cache otherwise watches) or after writing into a
+        module's ``_parameters`` / ``_modules`` dicts directly (replacing a Parameter or a submodule by assignment is seen without
+        it: _native_key)."""
         self._native_cache = None
         self._param_list = None
         if getattr(getattr(self, 'decoder', None), '_label_bias_key', None) is not None:
@@ -256,16 +281,23 @@ class LAMP(nn.Module):
         kv = [(l.enc_attn.w_ks.weight, l.enc_attn.w_vs.weight) for l in self.decoder.layer_stack]
         return enc, dec, kv
 
-    def _native_model(self):
-        """Build (and cache, keyed on every weight's data_ptr) the lamp_model struct."""
+    def _native_key(self):
+        """What decides whether the cached descriptor is current -- host integers only, nothing is launched or read back (but a
+        learnable label bias that changed is folded again on the way: GraphDecoder.current_label_bias).  The key holds data_ptr()
+        of every weight, the route switches, and _version of exactly the weights each weights-only table reads.
+        -> (key, the weight tensors, what _native_model builds from)"""
         replica = getattr(self, '_is_replica', False)
         # the Parameter objects of the original module are stable (load_state_dict / .to() replace their data, not
-        # them): keep the list.  A DataParallel replica is rebuilt on every forward with fresh tensors: no caching.
-        params = None if replica else self._param_list
+        # them) until somebody registers a Parameter or a submodule (_registrations): keep the list until then.  A
+        # DataParallel replica is rebuilt on every forward with fresh tensors: no caching.
+        params = None
+        if not replica and self._param_list is not None and self._param_list[1] == _registrations[0]:
+            params = self._param_list[0]
         if params is None:
+            epoch = _registrations[0]
             params = self._weight_tensors()
             if not replica:
-                self._param_list = params
+                self._param_list = (params, epoch)
         mask = self.decoder.label_mask_u8
         tiles = self.decoder.label_tiles
         bits = self.decoder.label_mask_bits
@@ -283,7 +315,8 @@ class LAMP(nn.Module):
         fold = self.fold_embedding and not replica and len(self.encoder.layer_stack) > 0 and not onehot and not live
         sparse = bool(self.use_sparse_label_attention and self.use_mask_bits and self.decoder.label_rows_sparse and bias is None)
         key = tuple(p.data_ptr() for p in params) + (N.ptr(mask), N.ptr(bits), N.ptr(tiles), self.use_label_tiles,
-                                                      hoist, self.use_mask_bits, packs, fold, sparse, live, bias is not None, gpacks, kvpacks)
+                                                      hoist, self.use_mask_bits, packs, fold, sparse, live, bias is not None, gpacks, kvpacks,
+                                                      _optimizer_steps[0])   # (fused torch optimizers move no _version)
         if hoist:  # the hoisted projection below is stale once either operand changes
             l0 = self.decoder.layer_stack[0].enc_attn
             key += (self.decoder.tgt_word_emb.weight._version, l0.w_qs.weight._version)
@@ -297,9 +330,16 @@ class LAMP(nn.Module):
             key += tuple(w._version for w in self._fold_weights() if w is not None)
         if onehot:   # the tap table and W2's repack are weights-only: rebuilt per weight version
             key += tuple((w.data_ptr(), w._version) for w in self._onehot_weights())
+        return key, params, (replica, mask, tiles, bits, hoist, packs, onehot, live, gpacks, kvpacks, fold, sparse)
+
+    def _native_model(self):
+        """Build (and cache under _native_key) the lamp_model struct and the weights-only tables that go with it."""
+        key, params, flags = self._native_key()
+        replica = flags[0]
         cache = None if replica else self._native_cache
         if cache is not None and cache[0] == key:
             return cache[1]
+        replica, mask, tiles, bits, hoist, packs, onehot, live, gpacks, kvpacks, fold, sparse = flags
         for p in params:
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError('lamp_amd expects contiguous fp32 parameters')
