@@ -912,6 +912,46 @@ int lamp_rank_at_k(const int32_t* idx, int64_t ld_idx, const float* targets, int
                    int32_t k, const double* discount, const double* ideal, int64_t* hits_at_rank, double* ndcg_sum,
                    double* recall_sum, int64_t* n_with_gold, void* workspace, size_t workspace_bytes, lamp_stream_t stream);
 
+/* ---- label-ranking metrics of whole rows: LRAP, coverage error, ranking loss, one-error, per-sample AUC (csrc/rank_at_k.hip)
+ * scores / targets fp32 [n_rows, L] (row strides ld_scores, ld_targets >= L, elements), device-resident, not modified; the
+ * scores may be logits or probabilities, any finite or non-finite value.
+ * ROW ORDERING.  key(x) is the integer key behind THE ORDER above: +0.0 and -0.0 share a key, all NaNs share one key, which
+ * lies below that of -inf; otherwise keys order as the floats do, denormals distinct.  a >= b below means key(a) >= key(b),
+ * compared as integers.  The gold set of a row is P = {j : targets[j] != 0} (the rule of lamp_rank_at_k), N the other columns,
+ * n_p = |P|, n_n = L - n_p.  For every p in P:
+ *   rank_p = #{j : s_j >= s_p}            pos_p = #{j in P : s_j >= s_p}            (both count p itself)
+ * THE TIE RULE: a column tied with p counts against it (it is "at or above"), as sklearn's label_ranking_loss and
+ * label_ranking_average_precision_score (rank method 'max') have it.
+ * Per row, int32 (row_counts, nullable, [n_rows, 6] contiguous, in this order):
+ *   n_pos       n_p
+ *   coverage    max_p rank_p; 0 for an empty row (n_p = 0), sklearn's coverage_error row
+ *   misordered  sum_p (rank_p - pos_p): the pairs (p in P, n in N) with s_n >= s_p
+ *   tied        sum_p #{n in N : key(s_n) == key(s_p)}
+ *   top1_hit    1 when the first-ranked column in THE ORDER (lowest column on a tie) is gold: rank 1 of lamp_topk_labels
+ *   has_nan     1 when the row holds a NaN score; the row is still ranked, NaN lowest
+ * Per row, fp64:
+ *   lrap  (row_lrap, nullable, [n_rows]) = (1 / n_p) sum_p pos_p / rank_p, every quotient in fp64, added in an order that
+ *         the row alone fixes (its L and its gold columns); 1.0 for an empty row (sklearn's convention; a full row gives 1)
+ *   rloss = misordered / (n_p n_n), 0 when n_p n_n = 0
+ *   auc   = 1 - (misordered - tied / 2) / (n_p n_n), for rows with 0 < n_p < L only: roc_auc_score of that row
+ * Dataset outputs (device):
+ *   sums   fp64 [3]:  lrap_sum, rloss_sum, auc_sum (auc over the rows with both classes)
+ *   counts int64 [5]: coverage_sum, top1_hits, n_with_gold (n_p > 0), n_with_both (0 < n_p < L), n_rows_with_nan
+ * so that LRAP = lrap_sum / n_rows, coverage_error = coverage_sum / n_rows, ranking_loss = rloss_sum / n_rows, one_error =
+ * 1 - top1_hits / n_rows (1 - P@1 of lamp_rank_at_k) and instance AUC = auc_sum / n_with_both.  Per-row terms are written to
+ * the workspace first and added in an order fixed by n_rows alone: the same bits from run to run; the integer outputs are
+ * also invariant under a permutation of the rows.  A row's results do not depend on n_rows, its position, the strides or the
+ * padding.  The figures describe the matrix given: probabilities that saturate to exactly 0 or 1 tie where their logits did
+ * not.  L <= 32768, n_rows < 2^31, 64-bit row offsets; every score and target is read once; no atomics, nothing allocated
+ * or synchronised; the kernel chosen is a function of L alone.  The workspace needs no alignment.
+ * Validation before any launch, in this order: LAMP_E_DIMS (a non-positive size, ld_scores < L, ld_targets < L),
+ * LAMP_E_NULL (any pointer but row_counts and row_lrap), LAMP_E_UNSUPPORTED (L > 32768, n_rows >= 2^31), LAMP_E_WORKSPACE.
+ * lamp_label_ranking_workspace_bytes is 0 for a request that is not served. */
+size_t lamp_label_ranking_workspace_bytes(int64_t n_rows, int32_t L);
+int lamp_label_ranking(const float* scores, int64_t ld_scores, const float* targets, int64_t ld_targets, int64_t n_rows,
+                       int32_t L, double* sums, int64_t* counts, int32_t* row_counts, double* row_lrap, void* workspace,
+                       size_t workspace_bytes, lamp_stream_t stream);
+
 /* ---- the training step around the model (train.py:37-48, main.py:99) ------------------------------------------------ */
 
 /* train.py:37-44 forward AND backward in one launch: F.sigmoid(pred), F.binary_cross_entropy_with_logits(.., reduction='mean')

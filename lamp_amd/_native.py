@@ -251,6 +251,8 @@ PROTOTYPES = {
     'lamp_rank_at_k_workspace_bytes': (_sz, [_i64, _i32]),
     'lamp_rank_at_k': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp, _vp,
                                  _vp, _vp, _sz, _vp]),
+    'lamp_label_ranking_workspace_bytes': (_sz, [_i64, _i32]),
+    'lamp_label_ranking': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'lamp_embed_bwd_ordered': (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i64, _vp, _vp]),
     'lamp_bce_logits_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
     'lamp_multilabel_loss_train': (C.c_int, [C.POINTER(_vp), _f32p, C.POINTER(_vp), _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64,
@@ -282,7 +284,7 @@ LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs', 'lamp_forwa
                      'lamp_label_bias_fold', 'lamp_topk_labels', 'lamp_rank_at_k_workspace_bytes', 'lamp_rank_at_k',
                      'lamp_tune_thresholds_workspace_bytes', 'lamp_tune_thresholds', 'lamp_threshold_counts_vec',
                      'lamp_multilabel_loss_train', 'lamp_grad_norm_workspace_bytes', 'lamp_grad_norm', 'lamp_optim_step_ext',
-                     'lamp_rank_loss_train')
+                     'lamp_rank_loss_train', 'lamp_label_ranking_workspace_bytes', 'lamp_label_ranking')
 
 _lib = None
 _lock = threading.Lock()

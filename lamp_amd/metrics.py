@@ -23,6 +23,11 @@ columns once more and picks, per label, the candidate threshold that is best und
 Find_Optimal_Cutoff balance, compared in integers with ties to the highest threshold (lamp_tune_thresholds); threshold_counts
 and compute_metrics(thresholds=...) then take one threshold per label (lamp_threshold_counts_vec).
 
+Label-ranking metrics of whole rows (csrc/rank_at_k.hip) are opt-in as well: label_ranking and
+compute_metrics(label_ranking=True) give LRAP, coverage error, ranking loss, one-error and the per-sample AUC from every gold
+label's rank among all L labels (lamp_label_ranking: exact integers per row, fixed-order fp64 sums; a tie counts against the
+gold label, as sklearn's label_ranking_average_precision_score, coverage_error and label_ranking_loss have it).
+
 There is no CPU path: without a HIP device compute_metrics raises (N.require_device).
 """
 import ctypes as C
@@ -289,8 +294,70 @@ def rank_at_k(scores, targets, ks=(1, 3, 5)):
     return rank_at_k_from_sums(buf, scores.size(0), k, ks)
 
 
+LABEL_RANKING_KEYS = ('LRAP', 'coverage_error', 'ranking_loss', 'one_error', 'instance_AUC', 'n_with_gold', 'n_with_both',
+                      'n_rows_with_nan')
+LABEL_RANKING_ROW_COUNTS = ('n_pos', 'coverage', 'misordered', 'tied', 'top1_hit', 'has_nan')   # columns of row_counts
+
+
+def _label_ranking_buffer(scores, targets, rows=False):
+    """-> (float64 (8) device buffer: lrap_sum, rloss_sum, auc_sum, then coverage_sum, top1_hits, n_with_gold, n_with_both and
+    n_rows_with_nan as int64 bit patterns; row_counts int32 (n, 6) and row_lrap float64 (n) when `rows`, else None, None)."""
+    N.require_device(scores, targets)
+    s, lds = _matrix(scores)
+    t, ldt = _matrix(targets)
+    if s.shape != t.shape:
+        raise ValueError('scores %s and targets %s differ in shape' % (tuple(s.shape), tuple(t.shape)))
+    n, L = s.shape
+    lib = N.lib()
+    nbytes = lib.lamp_label_ranking_workspace_bytes(n, L)
+    if nbytes == 0:
+        raise ValueError('label ranking: unsupported shape (%d, %d); L <= %d' % (n, L, TOPK_MAX_L))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+    out = torch.empty(8, dtype=torch.float64, device=s.device)
+    row_counts = torch.empty((n, 6), dtype=torch.int32, device=s.device) if rows else None
+    row_lrap = torch.empty(n, dtype=torch.float64, device=s.device) if rows else None
+    N.check(lib.lamp_label_ranking(N.ptr(s), lds, N.ptr(t), ldt, n, L, N.ptr(out[:3]), N.ptr(out[3:].view(torch.int64)),
+                                   N.ptr(row_counts), N.ptr(row_lrap), N.ptr(ws), nbytes, N.stream()), 'lamp_label_ranking')
+    return out, row_counts, row_lrap
+
+
+def label_ranking_from_sums(buf, n):
+    """The figures of label_ranking from the host copy of _label_ranking_buffer's first result and the number of rows."""
+    buf = np.ascontiguousarray(buf, dtype=np.float64)
+    coverage, top1, with_gold, with_both, with_nan = (int(v) for v in buf[3:].view(np.int64))
+    return {
+        'LRAP': float(buf[0]) / n,
+        'coverage_error': float(coverage) / n,
+        'ranking_loss': float(buf[1]) / n,
+        'one_error': 1.0 - float(top1) / n,
+        'instance_AUC': float(buf[2]) / with_both if with_both > 0 else float('nan'),
+        'n_with_gold': with_gold,
+        'n_with_both': with_both,
+        'n_rows_with_nan': with_nan,
+    }
+
+
+def label_ranking(scores, targets):
+    """Label-ranking metrics of (n, L) device matrices, from every gold label's rank among all L labels of its row
+    (include/lamp_hip.h: lamp_label_ranking): a dict with 'LRAP', 'coverage_error' and 'ranking_loss' (sklearn's
+    label_ranking_average_precision_score, coverage_error and label_ranking_loss: a tie counts against the gold label, a row
+    without a gold label has LRAP 1, coverage 0 and loss 0), 'one_error' (1 - P@1 of rank_at_k), 'instance_AUC' (the mean
+    roc_auc_score of the rows that hold both classes; NaN when there is none), 'n_with_gold', 'n_with_both' and
+    'n_rows_with_nan'.  A gold label is a nonzero target; NaN scores rank lowest.  The figures describe the matrix given:
+    probabilities that saturate to exactly 0 or 1 tie where their logits did not.  One copy back."""
+    buf, _, _ = _label_ranking_buffer(scores, targets)
+    return label_ranking_from_sums(buf.cpu().numpy(), scores.size(0))
+
+
+def label_ranking_rows(scores, targets):
+    """The per-row results of lamp_label_ranking -> (row_counts int32 (n, 6): n_pos, coverage, misordered, tied, top1_hit,
+    has_nan; row_lrap float64 (n,)) on the device, nothing synchronised."""
+    _, row_counts, row_lrap = _label_ranking_buffer(scores, targets, rows=True)
+    return row_counts, row_lrap
+
+
 def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapsed=0.0, all_metrics=True, device=None,
-                    fdr_cutoff=0.5, at_k=None, thresholds=None):
+                    fdr_cutoff=0.5, at_k=None, thresholds=None, label_ranking=False):
     """utils/evals.py:316-407 for the binary-relevance decoders: a dict with the reference's keys -- ACC, HA, ebF1, miF1, maF1,
     meanAUC, medianAUC, meanAUPR, medianAUPR, allAUC, allAUPR, meanFDR, medianFDR, loss, time.  allAUC / allAUPR are float64
     arrays of length L (NaN for a label that cannot be ranked); all_metrics=False gives 0 for the ranking entries, as the
@@ -298,7 +365,9 @@ def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapse
     current HIP device) or on the device; the inputs are not modified.  at_k=(1, 3, 5) adds the keys of rank_at_k for those k
     (P@k, nDCG@k, R@k, n_with_gold); with the default the dict is what it was.  thresholds = a float32 tensor of length L (as
     tune_thresholds fitted it, on another split) makes the five thresholded figures use one threshold per label instead of
-    br_threshold; with None not one more launch happens."""
+    br_threshold; with None not one more launch happens.  label_ranking=True adds the keys of label_ranking (LRAP,
+    coverage_error, ranking_loss, one_error, instance_AUC, n_with_gold, n_with_both, n_rows_with_nan) of the predictions as
+    given; with the default there is not one more launch, key or copy."""
     if not all_predictions.is_cuda:
         if not torch.cuda.is_available():
             N.require_device(all_predictions)      # raises: HIP device only
@@ -314,6 +383,8 @@ def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapse
         if at_k is not None:
             ks = _check_ks(at_k, L)
             at_k_d = _rank_at_k_buffer(all_predictions, all_targets, max(ks))
+        if label_ranking:
+            label_ranking_d = _label_ranking_buffer(all_predictions, all_targets)[0]
         counts = counts_d.cpu().numpy()
         out = thresholded_from_counts(counts[:3 * L].reshape(3, L), counts[3 * L:].reshape(4, n), L)
         if all_metrics:
@@ -328,6 +399,8 @@ def compute_metrics(all_predictions, all_targets, loss, br_threshold=0.5, elapse
                 out[k] = 0
         if at_k is not None:
             out.update(rank_at_k_from_sums(at_k_d.cpu().numpy(), n, max(ks), ks))
+        if label_ranking:
+            out.update(label_ranking_from_sums(label_ranking_d.cpu().numpy(), n))
     out['loss'] = loss
     out['time'] = elapsed
     return out

@@ -4,7 +4,7 @@ on the MI355X path.
     python -m lamp_amd.run_eval -data data/reuters/train_valid_test.pt -dataset reuters \
            -d_model 512 -d_inner_hid 512 -n_layers_enc 2 -n_head 4 -label_mask prior \
            [-checkpoint results/.../model.chkpt] [-split test] [-batch_size 32] [-streams 2] [-gpus N] [-all_metrics]
-           [-at_k 1,3,5] [-tune_thresholds f1|youden|balance|checkpoint [-tune_split valid] [-tune_scope label|global]]
+           [-at_k 1,3,5] [-label_ranking] [-tune_thresholds f1|youden|balance|checkpoint [-tune_split valid] [-tune_scope label|global]]
 
 -gpus N starts one process per GPU (rendezvous on 127.0.0.1; "nccl" = RCCL for the final gather only); every rank
 evaluates its contiguous share of the batches -- the forward path needs no collective (lamp_amd/sharding.py).
@@ -19,7 +19,10 @@ adjacency from the train split).  Metrics are the thresholded multi-label basics
 reference's conventions for empty samples / labels); with -all_metrics also the ranking metrics the reference computes with
 all_metrics=True (:208-298: mean / median AUC, AUPR and recall at FDR <= 0.5 over the labels, and the per-label arrays), on the
 device (lamp_amd/metrics.py); with -at_k 1,3,5 precision, nDCG and recall at those ranks, each sample's labels ranked on
-the device in the order include/lamp_hip.h defines (the figures are printed on stderr and join the JSON result line).
+the device in the order include/lamp_hip.h defines (the figures are printed on stderr and join the JSON result line); with
+-label_ranking the label-ranking metrics of whole rows (lamp_amd/metrics.py: label_ranking; DESIGN.md section 8.13: LRAP,
+coverage_error, ranking_loss, one_error, instance_AUC and the row counts n_with_gold, n_with_both, n_rows_with_nan), printed
+and joined to the JSON line in the same way, with label_ranking_seconds.
 With -tune_thresholds f1|youden|balance the -tune_split (valid) is evaluated first and one decision threshold per label is
 fitted on it on the device (lamp_amd/metrics.py: tune_thresholds), then -split is evaluated as always and
 the five thresholded figures at the fitted thresholds join the JSON line as tuned_ACC, tuned_HA, tuned_ebF1, tuned_miF1 and
@@ -94,6 +97,10 @@ def parse(argv=None):
                     help='comma-separated ranks, e.g. 1,3,5: also report precision (P@k), nDCG@k and recall (R@k) at those k, each '
                          "sample's labels ranked on the device (lamp_amd/metrics.py: rank_at_k; every k <= min(n_labels, 64)); "
                          'independent of -all_metrics; with -gpus N by rank 0 after the combine')
+    ap.add_argument('-label_ranking', action='store_true',
+                    help='also report LRAP, coverage_error, ranking_loss, one_error and instance_AUC, from the rank of every gold '
+                         "label among all labels of its sample, on the device (lamp_amd/metrics.py: label_ranking); independent "
+                         'of -all_metrics and -at_k; with -gpus N by rank 0 after the combine')
     ap.add_argument('-tune_thresholds', type=str, choices=['f1', 'youden', 'balance', 'checkpoint'], default=None,
                     help='fit one decision threshold per label on -tune_split under this criterion (lamp_amd/metrics.py: '
                          "tune_thresholds) and also report the thresholded figures of -split at them (tuned_*); 'checkpoint' takes "
@@ -336,7 +343,7 @@ def main(argv=None):
     batches = D.EvalBatcher(split['src'], split['tgt'], opt.batch_size)
     torch.cuda.synchronize()
     # one rank holds the whole split: nothing goes back up
-    on_device = {} if (opt.all_metrics or opt.at_k or opt.tune_thresholds) and world == 1 else None
+    on_device = {} if (opt.all_metrics or opt.at_k or opt.label_ranking or opt.tune_thresholds) and world == 1 else None
     t0 = time.perf_counter()
     preds, targets, bce_total = test_epoch(model, batches, n_labels, opt.batch_size, device, streams=opt.streams,
                                            prefetch=opt.prefetch, merge_stage=opt.merge_stages,
@@ -364,6 +371,15 @@ def main(argv=None):
         out['at_k_seconds'] = time.perf_counter() - t1
         print('  '.join('%s %.6f' % (key, at_k[key]) for key in at_k if key != 'n_with_gold') +
               '  n_with_gold %d' % at_k['n_with_gold'], file=sys.stderr, flush=True)
+    if opt.label_ranking and rank == 0:
+        from .metrics import label_ranking
+        t1 = time.perf_counter()
+        lr = (label_ranking(on_device['probs'], on_device['targets']) if on_device else
+              label_ranking(preds.to(device), targets.to(device)))
+        out.update(lr)
+        out['label_ranking_seconds'] = time.perf_counter() - t1
+        print('  '.join(('%s %d' if key.startswith('n_') else '%s %.6f') % (key, lr[key]) for key in lr), file=sys.stderr,
+              flush=True)
     if tuned is not None and rank == 0:
         from .metrics import compute_metrics
         t1 = time.perf_counter()

@@ -4,7 +4,7 @@ decoder=graph, on the MI355X path.
     python -m lamp_amd.run_train -data data/reuters/train_valid_test.pt -dataset reuters -batch_size 32 \
            -d_model 512 -n_layers_enc 2 -n_head 4 -label_mask prior -epoch 50 -dropout 0.1 -lr 0.0002 [-int_preds] \
            [-enc_self_att] [-attn_type sigmoid] [-lr_decay 0.9 -lr_step_size 10] [-save_mode best] [-load_pretrained] [-name run1] [-results_dir results/]
-           [-tune_thresholds f1|youden|balance]
+           [-tune_thresholds f1|youden|balance] [-label_ranking] [-at_k 1,3,5]
 
 Flag names and derived defaults are config_args.py's for everything on this path (n_layers_dec = n_layers_enc :87-88,
 test_batch_size = batch_size :93-94, d_k = d_v = d_model / n_head :96-99, dec_dropout = dropout :101-102, no position
@@ -28,6 +28,12 @@ device (lamp_amd/metrics.py: tune_thresholds), reports th
 tuned_ACC .. tuned_maF1 next to the fixed ones in that epoch's record, stores `label_thresholds` (a CPU float32 tensor) and
 `tune_criterion` in the checkpoint beside model / settings / epoch (run_eval -tune_thresholds checkpoint reads them) and adds
 .thr_<criterion> to the results name.
+
+-label_ranking and -at_k 1,3,5 are reporting only: the per-epoch metrics of all three splits then also carry the label-ranking
+figures (LRAP, coverage_error, ranking_loss, one_error, instance_AUC) and P@k / nDCG@k / R@k (section
+8.8), computed on the device from the probabilities the epoch left there -- what a ranking -loss_fn optimises, next to the BCE
+it is selected on.  They change neither the results name nor the checkpoint (no settings entry, no key) nor losses.csv, and
+-save_mode best still looks at the BCE valid loss.
 
 -loss_fn focal|asl and -pos_weight inv|sqrt_inv change the TRAINED objective (focal loss, asymmetric loss, per-label positive
 weights from the train split's counts), still in the one loss launch per batch.  The train column of
@@ -115,6 +121,14 @@ def parse(argv=None):
                     help="after each validation epoch fit one decision threshold per label on the valid predictions (lamp_amd/"
                          "metrics.py: tune_thresholds), report the test epoch's tuned_* figures and store label_thresholds / "
                          "tune_criterion in the checkpoint for run_eval -tune_thresholds checkpoint")
+    ap.add_argument('-label_ranking', action='store_true',
+                    help="reporting only: every epoch's train / valid / test metrics also carry LRAP, coverage_error, "
+                         "ranking_loss, one_error and instance_AUC (lamp_amd/metrics.py: label_ranking); no change to the results "
+                         "name, the checkpoint or losses.csv")
+    ap.add_argument('-at_k', type=str, default='',
+                    help="reporting only: comma-separated ranks, e.g. 1,3,5: every epoch's metrics also carry P@k, nDCG@k and R@k "
+                         "(lamp_amd/metrics.py: rank_at_k; every k <= min(n_labels, 64)); no change to the results name, the "
+                         "checkpoint or losses.csv")
     ap.add_argument('-loss_fn', type=str, choices=['bce', 'focal', 'asl', 'lsep', 'rank_hinge', 'rank_logistic'], default='bce',
                     help="the TRAINED objective (lamp_multilabel_loss_train, DESIGN.md section 8.10): focal = -focal_gamma on both "
                          "branches, asl = the asymmetric loss of -asl_gamma_pos / -asl_gamma_neg / -asl_clip; or a ranking loss "
@@ -152,6 +166,12 @@ def parse(argv=None):
     ap.add_argument('-seed', type=int, default=0, help='torch.manual_seed: weight init, shuffling, dropout seeds')
     ap.add_argument('-gpus', type=int, default=1)
     opt = ap.parse_args(argv)
+    try:
+        opt.at_k = tuple(int(v) for v in opt.at_k.split(',') if v.strip())
+    except ValueError:
+        ap.error('-at_k takes comma-separated integers, e.g. 1,3,5')
+    if any(k < 1 or k > 64 for k in opt.at_k):
+        ap.error('-at_k: every k must lie in 1 .. 64')
     return derive(opt)
 
 
@@ -426,6 +446,7 @@ def checkpoint_settings(opt):
     and `tune_thresholds` travel only when they are set: without the flags the settings are what they were before they
     existed.  Likewise `loss_fn` with the flags of the chosen objective, and `pos_weight` with its cap."""
     drop = {'loss_options', 'rank_loss'}      # (the run's own objects, None for plain BCE: never a setting)
+    drop.update(('label_ranking', 'at_k'))    # (reporting only: a checkpoint does not depend on what was printed beside it)
     loss_fn = getattr(opt, 'loss_fn', 'bce')
     if loss_fn == 'bce':
         drop.add('loss_fn')
@@ -495,6 +516,11 @@ def main(argv=None):
     test_data = D.EvalBatcher(data['test']['src'], data['test']['tgt'], opt.test_batch_size)
     n_labels = opt.tgt_vocab_size
     valid_losses, history = [], []
+    report = {}                    # -label_ranking / -at_k: more keys in the per-epoch metrics, nothing else
+    if getattr(opt, 'label_ranking', False):
+        report['label_ranking'] = True
+    if getattr(opt, 'at_k', ()):
+        report['at_k'] = tuple(opt.at_k)
     skipped_before = 0
     with open(os.path.join(opt.model_name, 'losses.csv'), 'w+') as loss_file:
         for epoch_i in range(opt.epoch):
@@ -511,7 +537,8 @@ def main(argv=None):
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             train_loss = train_loss / train_data.n_insts
-            metrics = {'train': compute_metrics(on_dev['probs'], on_dev['targets'], train_loss, opt.br_threshold, dt / 60)}
+            metrics = {'train': compute_metrics(on_dev['probs'], on_dev['targets'], train_loss, opt.br_threshold, dt / 60,
+                                                **report)}
             out.update(train_loss=train_loss, train_seconds=dt,
                        train_samples_per_s=sum(real for _, real in on_dev['batches']) / dt)
             if opt.skip_nonfinite:      # (the loop has synchronised above: the device counter's first and only read-back)
@@ -528,7 +555,8 @@ def main(argv=None):
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 losses[split] = loss / batches.n_insts
-                metrics[split] = compute_metrics(on_dev['probs'], on_dev['targets'], losses[split], opt.br_threshold, dt / 60)
+                metrics[split] = compute_metrics(on_dev['probs'], on_dev['targets'], losses[split], opt.br_threshold, dt / 60,
+                                                 **report)
                 if opt.tune_thresholds and split == 'valid':   # (valid comes first: the test epoch below uses them)
                     fit = tune_thresholds(on_dev['probs'], on_dev['targets'], opt.tune_thresholds, opt.br_threshold)
                     label_thresholds = fit['threshold']
