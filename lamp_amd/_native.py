@@ -1259,12 +1259,7 @@ def optim_step(entries, kind, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
     n = len(entries)
     if n == 0:
         return
-    arr = (OptimEntry * n)()
-    for i, (p, g, m, v) in enumerate(entries):
-        e = arr[i]
-        e.param, e.grad, e.numel = p.data_ptr(), g.data_ptr(), p.numel()
-        if m is not None:
-            e.exp_avg, e.exp_avg_sq = m.data_ptr(), v.data_ptr()
+    arr = _optim_table(entries)
     check(lib().lamp_optim_step(arr, n, int(kind), int(step), float(lr), float(beta1), float(beta2), float(eps), stream()),
           'lamp_optim_step')
 

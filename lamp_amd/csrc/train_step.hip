@@ -14,14 +14,25 @@
 //   optim_step  Adam (torch.optim.Adam's single-tensor arithmetic, no weight decay, no amsgrad) or plain SGD over EVERY
 //               parameter of the model in one launch.  The table of (param, grad, exp_avg, exp_avg_sq, numel) travels in the
 //               kernel arguments (OPTIM_TABLE entries per launch); a workgroup owns one OPTIM_CHUNK-element chunk of one
-//               tensor, found by a binary search over the table's running chunk counts.  16-byte accesses when all four
-//               pointers allow it, the chunk's last numel % 4 elements by single lanes; 4-byte accesses otherwise.
+//               tensor.
 //   grad_norm   the global L2 norm of a table's gradients in fp64, one partial per chunk and one closing workgroup: the device
 //               record {norm, scale, finite, 0} that optim_step_ext reads.  No atomics.
 //   optim_step_ext  optim_step behind gradient clipping (the record's scale, applied in registers), per-entry weight decay
-//               (L2 or decoupled), SGD momentum, and "write nothing when the norm is not finite".  optim_step is untouched.
+//               (L2 or decoupled), SGD momentum, and "write nothing when the norm is not finite".
 //   embed_bwd_ordered  the embedding scatter-add without atomics (see the kernel), so that an epoch is reproducible.
 // All are enqueued on the caller's stream; neither allocates, synchronises or reads anything back.
+//
+// What the entries share, each written once:
+//   device  table_entry()      a workgroup's table entry, by binary search over the running chunk counts (the three table kernels)
+//           walk_chunk()       the walk over one chunk -- 16-byte path, tail lanes, 4-byte path -- with the update passed in
+//                              (optim_step and optim_step_ext; grad_norm only reads g and keeps its own loop)
+//           block_sum_f64()    a workgroup's fp64 sum (grad_norm's two stages, the pair kernels)
+//           bce_element()      the BCE term of the rank kernels.  bce_train_kernel keeps its own copy on purpose (see there).
+//   host    check_loss_args() / fill_loss_params()   the argument rules of multilabel and rank, the parameter fill of all three
+//           for_each_launch()  cuts a table into launches of OPTIM_TABLE entries with their chunk counts (all three table entries)
+//           check_optim_entries() / set_optim_scalars()   the per-entry rules and the step's scalars (optim_step, optim_step_ext)
+// The order in which an entry answers a call that breaks two rules is its own (lamp_bce_logits_train's differs from the
+// other two loss entries'); tests/test_train_step_refusals_cpu.py holds every such answer.
 #include "lamp_kernels.h"
 
 namespace lamp {
@@ -55,6 +66,7 @@ __global__ __launch_bounds__(256) void bce_train_kernel(const BceTrainParams p) 
     float loss = 0.f;
     for (int i = lane; i < p.L; i += 64) {
         const float x = x_row[i], t = t_row[i];
+        // (bce_element's arithmetic, a second copy on purpose: through bce_element this kernel takes other registers and schedule)
         // e = exp(-|x|) <= 1: sigmoid(|x|) = 1 / (1 + e), sigmoid(-|x|) = e / (1 + e), neither cancels
         const float e = expf(-fabsf(x));
         const float r = 1.0f / (1.0f + e);
@@ -172,6 +184,16 @@ __global__ __launch_bounds__(256) void multilabel_loss_train_kernel(const LossTr
     }
     loss = wave64_sum_f64(loss);
     if (lane == 0 && p.row_loss) p.row_loss[int64_t(k) * p.ld_loss + row] = float(loss);
+}
+
+// A 256-lane workgroup's sum of one double per lane: the lanes of a wave by wave64_sum_f64, the four waves as
+// (w0 + w1) + (w2 + w3) through red[4].  A caller that sums twice through one red puts a barrier between the two calls.
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+    v = wave64_sum_f64(v);
+    const int tid = int(threadIdx.x);
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // ---- lamp_rank_loss_train (include/lamp_hip.h): a row's positives against its negatives ------------------------------
@@ -294,13 +316,6 @@ __global__ __launch_bounds__(256) void rank_lsep_train_kernel(const RankTrainPar
 // The pair kinds: one workgroup per (matrix, row).  The row's logits are compacted into LDS in column order, positives in
 // xs[0, n_p), negatives in xs[n_p, L), col[] the column of each slot; wave w compacts columns [w Q, (w + 1) Q) by ballots, its
 // offsets from one count pass.  An element then loops over the OPPOSITE class only: n_p n_n evaluations per direction.
-__device__ __forceinline__ double block_sum_f64(double v, double* red, int tid) {
-    v = wave64_sum_f64(v);
-    __syncthreads();                                 // (red may still be read from the sum before)
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // One element against slots [lo, hi) of the opposite class -> LOGISTIC: sum of sigmoid(x_n - x_p); HINGE: the number of
 // active pairs.  The negatives' direction also takes the loss.
@@ -445,8 +460,12 @@ __global__ __launch_bounds__(256) void rank_pair_train_kernel(const RankTrainPar
         double unused = 0.0;
         rank_direction<KIND, false>(r, xs, col, part, 0, n_p, n_p, n_n, p.margin, tid, unused);
     }
-    double R = block_sum_f64(loss, red, tid) * r.inv_pairs;
-    if (mix) R += p.beta_over_L * block_sum_f64(bce, red, tid);
+    __syncthreads();                                 // (nothing has used red yet: the barrier this kernel has always had here)
+    double R = block_sum_f64(loss, red) * r.inv_pairs;
+    if (mix) {
+        __syncthreads();                             // (red is still being read from the sum before)
+        R += p.beta_over_L * block_sum_f64(bce, red);
+    }
     if (tid == 0 && p.row_loss) p.row_loss[int64_t(k) * p.ld_loss + row] = float(r.has_nan ? __builtin_nan("") : R);
 }
 
@@ -482,67 +501,73 @@ __device__ __forceinline__ void optim_update(float& w, float g, float& m, float&
     }
 }
 
-template <bool ADAM>
-__global__ __launch_bounds__(256) void optim_step_kernel(const OptimParams p) {
-    const int b = int(blockIdx.x);
-    int lo = 0, hi = p.n;            // the entry with chunk_start[lo] <= b < chunk_start[lo + 1] (uniform: scalar loads)
+// The table entry that owns workgroup b: chunk_start[lo] <= b < chunk_start[lo + 1] (uniform: scalar loads).
+__device__ __forceinline__ int table_entry(const int32_t* chunk_start, int n, int b) {
+    int lo = 0, hi = n;
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
-        if (p.chunk_start[mid] <= b) lo = mid; else hi = mid;
+        if (chunk_start[mid] <= b) lo = mid; else hi = mid;
     }
-    const OptimEntry& t = p.e[lo];
-    const int64_t off = int64_t(b - p.chunk_start[lo]) * OPTIM_CHUNK;
+    return lo;
+}
+
+// One workgroup's walk over the OPTIM_CHUNK elements of entry t from element `off` on: update(w, g, m, v) on every element,
+// the moments the kernel has (HAS_M, HAS_V) loaded before it and stored after it.  16-byte accesses when every pointer allows
+// them, the chunk's last numel % 4 elements by single lanes; 4-byte accesses otherwise.
+template <bool HAS_M, bool HAS_V, class Update>
+__device__ __forceinline__ void walk_chunk(const OptimEntry& t, int64_t off, Update update) {
     const int64_t left = t.numel - off;
     const int n = left < OPTIM_CHUNK ? int(left) : OPTIM_CHUNK;
     float* __restrict__ w = t.param + off;
     const float* __restrict__ g = t.grad + off;
-    float* __restrict__ m = ADAM ? t.exp_avg + off : nullptr;
-    float* __restrict__ v = ADAM ? t.exp_avg_sq + off : nullptr;
+    float* __restrict__ m = HAS_M ? t.exp_avg + off : nullptr;
+    float* __restrict__ v = HAS_V ? t.exp_avg_sq + off : nullptr;
     const int tid = int(threadIdx.x);
     // off is a multiple of 4096 floats: the chunk is 16-byte aligned iff the tensor is
     const uintptr_t bits = reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) |
-                           (ADAM ? reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) : uintptr_t(0));
+                           (HAS_M ? reinterpret_cast<uintptr_t>(m) : uintptr_t(0)) |
+                           (HAS_V ? reinterpret_cast<uintptr_t>(v) : uintptr_t(0));
     if ((bits & 15u) == 0) {
         const int nq = n >> 2;
         for (int q = tid; q < nq; q += 256) {
             float4 w4 = reinterpret_cast<float4*>(w)[q];
             const float4 g4 = reinterpret_cast<const float4*>(g)[q];
             float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), v4 = m4;
-            if (ADAM) {
-                m4 = reinterpret_cast<float4*>(m)[q];
-                v4 = reinterpret_cast<float4*>(v)[q];
-            }
-            optim_update<ADAM>(w4.x, g4.x, m4.x, v4.x, p);
-            optim_update<ADAM>(w4.y, g4.y, m4.y, v4.y, p);
-            optim_update<ADAM>(w4.z, g4.z, m4.z, v4.z, p);
-            optim_update<ADAM>(w4.w, g4.w, m4.w, v4.w, p);
+            if (HAS_M) m4 = reinterpret_cast<float4*>(m)[q];
+            if (HAS_V) v4 = reinterpret_cast<float4*>(v)[q];
+            update(w4.x, g4.x, m4.x, v4.x);
+            update(w4.y, g4.y, m4.y, v4.y);
+            update(w4.z, g4.z, m4.z, v4.z);
+            update(w4.w, g4.w, m4.w, v4.w);
             reinterpret_cast<float4*>(w)[q] = w4;
-            if (ADAM) {
-                reinterpret_cast<float4*>(m)[q] = m4;
-                reinterpret_cast<float4*>(v)[q] = v4;
-            }
+            if (HAS_M) reinterpret_cast<float4*>(m)[q] = m4;
+            if (HAS_V) reinterpret_cast<float4*>(v)[q] = v4;
         }
         const int i = (nq << 2) + tid;      // the tail: at most three single lanes
         if (i < n) {
-            float wi = w[i], mi = ADAM ? m[i] : 0.f, vi = ADAM ? v[i] : 0.f;
-            optim_update<ADAM>(wi, g[i], mi, vi, p);
+            float wi = w[i], mi = HAS_M ? m[i] : 0.f, vi = HAS_V ? v[i] : 0.f;
+            update(wi, g[i], mi, vi);
             w[i] = wi;
-            if (ADAM) {
-                m[i] = mi;
-                v[i] = vi;
-            }
+            if (HAS_M) m[i] = mi;
+            if (HAS_V) v[i] = vi;
         }
     } else {
         for (int i = tid; i < n; i += 256) {
-            float wi = w[i], mi = ADAM ? m[i] : 0.f, vi = ADAM ? v[i] : 0.f;
-            optim_update<ADAM>(wi, g[i], mi, vi, p);
+            float wi = w[i], mi = HAS_M ? m[i] : 0.f, vi = HAS_V ? v[i] : 0.f;
+            update(wi, g[i], mi, vi);
             w[i] = wi;
-            if (ADAM) {
-                m[i] = mi;
-                v[i] = vi;
-            }
+            if (HAS_M) m[i] = mi;
+            if (HAS_V) v[i] = vi;
         }
     }
+}
+
+template <bool ADAM>
+__global__ __launch_bounds__(256) void optim_step_kernel(const OptimParams p) {
+    const int b = int(blockIdx.x);
+    const int lo = table_entry(p.chunk_start, p.n, b);
+    walk_chunk<ADAM, ADAM>(p.e[lo], int64_t(b - p.chunk_start[lo]) * OPTIM_CHUNK,
+                           [&](float& w, float g, float& m, float& v) { optim_update<ADAM>(w, g, m, v, p); });
 }
 
 // lamp_embed_bwd with a fixed order.  One wave per token position.  The wave of a token id's FIRST position owns that id's
@@ -598,22 +623,10 @@ struct NormParams {
     double* partial;     // this launch's first partial
 };
 
-__device__ __forceinline__ double block256_sum_f64(double acc, double* red) {
-    acc = wave64_sum_f64(acc);
-    const int tid = int(threadIdx.x);
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(256) void grad_norm_partial_kernel(const NormParams p) {
     __shared__ double red[4];
     const int b = int(blockIdx.x);
-    int lo = 0, hi = p.n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (p.chunk_start[mid] <= b) lo = mid; else hi = mid;
-    }
+    const int lo = table_entry(p.chunk_start, p.n, b);
     const int64_t off = int64_t(b - p.chunk_start[lo]) * OPTIM_CHUNK;
     const int64_t left = p.numel[lo] - off;
     const int n = left < OPTIM_CHUNK ? int(left) : OPTIM_CHUNK;
@@ -634,7 +647,7 @@ __global__ __launch_bounds__(256) void grad_norm_partial_kernel(const NormParams
     } else {
         for (int i = tid; i < n; i += 256) acc += double(g[i]) * double(g[i]);
     }
-    const double total = block256_sum_f64(acc, red);
+    const double total = block_sum_f64(acc, red);
     if (tid == 0) p.partial[b] = total;
 }
 
@@ -649,7 +662,7 @@ __global__ __launch_bounds__(256) void grad_norm_final_kernel(const double* __re
     const int tid = int(threadIdx.x);
     double acc = 0.0;
     for (int64_t i = tid; i < n_partials; i += 256) acc += partial[i];
-    const double total = block256_sum_f64(acc, red);
+    const double total = block_sum_f64(acc, red);
     if (tid == 0) {
         const float norm = float(sqrt(total));
         float scale = 1.0f;
@@ -712,60 +725,14 @@ __global__ __launch_bounds__(256) void optim_step_ext_kernel(const OptimExtParam
     }
     s.momentum = x.momentum;
     const int b = int(blockIdx.x);
-    int lo = 0, hi = p.n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (p.chunk_start[mid] <= b) lo = mid; else hi = mid;
-    }
+    const int lo = table_entry(p.chunk_start, p.n, b);
     const OptimEntry& t = p.e[lo];
     s.decay = x.decay[lo];
     // an entry without decay takes exactly optim_step_kernel's arithmetic: 0 * w would turn an infinite weight into NaN
     s.decay_mode = (x.decay_mode == DECAY_L2 && s.decay != 0.0f) || (x.decay_mode == DECAY_DECOUPLED && s.decay != 1.0f)
                        ? x.decay_mode : DECAY_NONE;
-    const int64_t off = int64_t(b - p.chunk_start[lo]) * OPTIM_CHUNK;
-    const int64_t left = t.numel - off;
-    const int n = left < OPTIM_CHUNK ? int(left) : OPTIM_CHUNK;
-    float* __restrict__ w = t.param + off;
-    const float* __restrict__ g = t.grad + off;
-    float* __restrict__ m = HAS_M ? t.exp_avg + off : nullptr;
-    float* __restrict__ v = HAS_V ? t.exp_avg_sq + off : nullptr;
-    const int tid = int(threadIdx.x);
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) |
-                           (HAS_M ? reinterpret_cast<uintptr_t>(m) : uintptr_t(0)) |
-                           (HAS_V ? reinterpret_cast<uintptr_t>(v) : uintptr_t(0));
-    if ((bits & 15u) == 0) {
-        const int nq = n >> 2;
-        for (int q = tid; q < nq; q += 256) {
-            float4 w4 = reinterpret_cast<float4*>(w)[q];
-            const float4 g4 = reinterpret_cast<const float4*>(g)[q];
-            float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), v4 = m4;
-            if (HAS_M) m4 = reinterpret_cast<float4*>(m)[q];
-            if (HAS_V) v4 = reinterpret_cast<float4*>(v)[q];
-            optim_update_ext<KIND>(w4.x, g4.x, m4.x, v4.x, p, s);
-            optim_update_ext<KIND>(w4.y, g4.y, m4.y, v4.y, p, s);
-            optim_update_ext<KIND>(w4.z, g4.z, m4.z, v4.z, p, s);
-            optim_update_ext<KIND>(w4.w, g4.w, m4.w, v4.w, p, s);
-            reinterpret_cast<float4*>(w)[q] = w4;
-            if (HAS_M) reinterpret_cast<float4*>(m)[q] = m4;
-            if (HAS_V) reinterpret_cast<float4*>(v)[q] = v4;
-        }
-        const int i = (nq << 2) + tid;      // the tail: at most three single lanes
-        if (i < n) {
-            float wi = w[i], mi = HAS_M ? m[i] : 0.f, vi = HAS_V ? v[i] : 0.f;
-            optim_update_ext<KIND>(wi, g[i], mi, vi, p, s);
-            w[i] = wi;
-            if (HAS_M) m[i] = mi;
-            if (HAS_V) v[i] = vi;
-        }
-    } else {
-        for (int i = tid; i < n; i += 256) {
-            float wi = w[i], mi = HAS_M ? m[i] : 0.f, vi = HAS_V ? v[i] : 0.f;
-            optim_update_ext<KIND>(wi, g[i], mi, vi, p, s);
-            w[i] = wi;
-            if (HAS_M) m[i] = mi;
-            if (HAS_V) v[i] = vi;
-        }
-    }
+    walk_chunk<HAS_M, HAS_V>(t, int64_t(b - p.chunk_start[lo]) * OPTIM_CHUNK,
+                             [&](float& w, float g, float& m, float& v) { optim_update_ext<KIND>(w, g, m, v, p, s); });
 }
 
 }  // namespace
@@ -773,22 +740,31 @@ __global__ __launch_bounds__(256) void optim_step_ext_kernel(const OptimExtParam
 
 using namespace lamp;
 
-int lamp_bce_logits_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
-                          const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
-                          int64_t ld_row_loss, lamp_stream_t stream) {
+// ---- the loss entries' shared host side -------------------------------------------------------------------------------
+// The argument rules lamp_multilabel_loss_train and lamp_rank_loss_train answer in one order: sizes and leading dimensions
+// (DIMS), then the three arrays and the first n_checked matrices (NULL).  lamp_bce_logits_train keeps an order of its own
+// (tests/test_train_step_refusals_cpu.py pins both).
+static int check_loss_args(const float* const* logits, const float* weights, int32_t n_mats, int32_t n_checked, const float* targets,
+                           int64_t n_rows, int32_t L, const float* probs, int64_t ld_probs, const float* row_loss,
+                           int64_t ld_row_loss) {
     if (n_rows <= 0 || L <= 0 || n_mats <= 0) return LAMP_E_DIMS;
-    if (n_mats > BCE_MAX_MATS) return LAMP_E_UNSUPPORTED;
-    if (!logits || !weights || !targets) return LAMP_E_NULL;
     if ((probs && ld_probs < L) || (row_loss && n_mats > 1 && ld_row_loss < n_rows)) return LAMP_E_DIMS;
-    const int64_t blocks = (n_rows + 3) / 4;
-    if (blocks >= (int64_t(1) << 31)) return LAMP_E_UNSUPPORTED;
-    BceTrainParams p{};
-    const double n_mean = double(n_rows) * double(L);
-    for (int k = 0; k < n_mats; ++k) {
+    if (!logits || !weights || !targets) return LAMP_E_NULL;
+    for (int k = 0; k < n_checked; ++k)
         if (!logits[k]) return LAMP_E_NULL;
+    return LAMP_OK;
+}
+
+// What BceTrainParams and RankTrainParams have in common: the matrices, their coefficients weight_k / denom (taken in double,
+// rounded to the struct's own type), the target and output pointers, the strides and L.
+template <class Params>
+static void fill_loss_params(Params& p, const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
+                             double denom, const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs,
+                             float* row_loss, int64_t ld_row_loss) {
+    for (int k = 0; k < n_mats; ++k) {
         p.logits[k] = logits[k];
         p.dlogits[k] = dlogits ? dlogits[k] : nullptr;
-        p.coef[k] = float(double(weights[k]) / n_mean);
+        p.coef[k] = decltype(+p.coef[0])(double(weights[k]) / denom);
     }
     p.targets = targets;
     p.probs = probs;
@@ -797,6 +773,23 @@ int lamp_bce_logits_train(const float* const* logits, const float* weights, floa
     p.ld_probs = ld_probs;
     p.ld_loss = ld_row_loss;
     p.L = L;
+}
+
+int lamp_bce_logits_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
+                          const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
+                          int64_t ld_row_loss, lamp_stream_t stream) {
+    // this entry's own order of answers (the oldest of the three; unifying them would change recorded statuses)
+    if (n_rows <= 0 || L <= 0 || n_mats <= 0) return LAMP_E_DIMS;
+    if (n_mats > BCE_MAX_MATS) return LAMP_E_UNSUPPORTED;
+    if (!logits || !weights || !targets) return LAMP_E_NULL;
+    if ((probs && ld_probs < L) || (row_loss && n_mats > 1 && ld_row_loss < n_rows)) return LAMP_E_DIMS;
+    const int64_t blocks = (n_rows + 3) / 4;
+    if (blocks >= (int64_t(1) << 31)) return LAMP_E_UNSUPPORTED;
+    for (int k = 0; k < n_mats; ++k)
+        if (!logits[k]) return LAMP_E_NULL;
+    BceTrainParams p{};
+    fill_loss_params(p, logits, weights, dlogits, n_mats, double(n_rows) * double(L), targets, n_rows, L, probs, ld_probs, row_loss,
+                     ld_row_loss);
     p.n_mats = n_mats;
     hipLaunchKernelGGL(bce_train_kernel, dim3(unsigned(blocks), unsigned(n_mats)), dim3(256), 0, hipStream_t(stream), p);
     return int(hipGetLastError());
@@ -807,11 +800,7 @@ static bool loss_exponent_served(float g) { return g == 0.f || (g >= 1.f && g <=
 int lamp_multilabel_loss_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
                                const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
                                int64_t ld_row_loss, const lamp_loss_options* opts, lamp_stream_t stream) {
-    if (n_rows <= 0 || L <= 0 || n_mats <= 0) return LAMP_E_DIMS;
-    if ((probs && ld_probs < L) || (row_loss && n_mats > 1 && ld_row_loss < n_rows)) return LAMP_E_DIMS;
-    if (!logits || !weights || !targets) return LAMP_E_NULL;
-    for (int k = 0; k < n_mats; ++k)
-        if (!logits[k]) return LAMP_E_NULL;
+    if (int st = check_loss_args(logits, weights, n_mats, n_mats, targets, n_rows, L, probs, ld_probs, row_loss, ld_row_loss)) return st;
     if (n_mats > BCE_MAX_MATS) return LAMP_E_UNSUPPORTED;
     const int64_t blocks = (n_rows + 3) / 4;
     if (blocks >= (int64_t(1) << 31)) return LAMP_E_UNSUPPORTED;
@@ -826,21 +815,9 @@ int lamp_multilabel_loss_train(const float* const* logits, const float* weights,
         return lamp_bce_logits_train(logits, weights, dlogits, n_mats, targets, n_rows, L, probs, ld_probs, row_loss, ld_row_loss,
                                      stream);
     LossTrainParams q{};
-    BceTrainParams& p = q.b;
-    const double n_mean = double(n_rows) * double(L);
-    for (int k = 0; k < n_mats; ++k) {
-        p.logits[k] = logits[k];
-        p.dlogits[k] = dlogits ? dlogits[k] : nullptr;
-        p.coef[k] = float(double(weights[k]) / n_mean);
-    }
-    p.targets = targets;
-    p.probs = probs;
-    p.row_loss = row_loss;
-    p.n_rows = n_rows;
-    p.ld_probs = ld_probs;
-    p.ld_loss = ld_row_loss;
-    p.L = L;
-    p.n_mats = n_mats;
+    fill_loss_params(q.b, logits, weights, dlogits, n_mats, double(n_rows) * double(L), targets, n_rows, L, probs, ld_probs, row_loss,
+                     ld_row_loss);
+    q.b.n_mats = n_mats;
     q.pos_weight = opts->pos_weight;
     q.gamma_pos = opts->gamma_pos;
     q.gamma_neg = opts->gamma_neg;
@@ -858,11 +835,11 @@ static bool rank_weight_served(float v) { return v >= 0.f && v <= 3.402823466e38
 int lamp_rank_loss_train(const float* const* logits, const float* weights, float* const* dlogits, int32_t n_mats,
                          const float* targets, int64_t n_rows, int32_t L, float* probs, int64_t ld_probs, float* row_loss,
                          int64_t ld_row_loss, const lamp_rank_loss_options* opts, lamp_stream_t stream) {
-    if (n_rows <= 0 || L <= 0 || n_mats <= 0) return LAMP_E_DIMS;
-    if ((probs && ld_probs < L) || (row_loss && n_mats > 1 && ld_row_loss < n_rows)) return LAMP_E_DIMS;
-    if (!logits || !weights || !targets || !opts) return LAMP_E_NULL;
-    for (int k = 0; k < n_mats && k < BCE_MAX_MATS; ++k)
-        if (!logits[k]) return LAMP_E_NULL;
+    // (the matrices beyond BCE_MAX_MATS are not looked at: n_mats is refused further down)
+    if (int st = check_loss_args(logits, weights, n_mats, n_mats < BCE_MAX_MATS ? n_mats : BCE_MAX_MATS, targets, n_rows, L, probs,
+                                 ld_probs, row_loss, ld_row_loss))
+        return st;
+    if (!opts) return LAMP_E_NULL;
     const int kind = opts->kind;
     if (kind != LAMP_RANK_LSEP && kind != LAMP_RANK_HINGE && kind != LAMP_RANK_LOGISTIC) return LAMP_E_UNSUPPORTED;
     if (!rank_weight_served(opts->margin) || !rank_weight_served(opts->bce_weight)) return LAMP_E_UNSUPPORTED;
@@ -871,20 +848,9 @@ int lamp_rank_loss_train(const float* const* logits, const float* weights, float
     if (kind != LAMP_RANK_LSEP && L > RANK_PAIR_MAX_L) return LAMP_E_UNSUPPORTED;
     if (n_rows >= (int64_t(1) << 31)) return LAMP_E_UNSUPPORTED;
     RankTrainParams p{};
-    for (int k = 0; k < n_mats; ++k) {
-        p.logits[k] = logits[k];
-        p.dlogits[k] = dlogits ? dlogits[k] : nullptr;
-        p.coef[k] = double(weights[k]) / double(n_rows);
-    }
-    p.targets = targets;
-    p.probs = probs;
-    p.row_loss = row_loss;
-    p.n_rows = n_rows;
-    p.ld_probs = ld_probs;
-    p.ld_loss = ld_row_loss;
+    fill_loss_params(p, logits, weights, dlogits, n_mats, double(n_rows), targets, n_rows, L, probs, ld_probs, row_loss, ld_row_loss);
     p.beta_over_L = double(opts->bce_weight) / double(L);
     p.margin = opts->margin;
-    p.L = L;
     const hipStream_t s = hipStream_t(stream);
     if (kind == LAMP_RANK_LSEP)
         hipLaunchKernelGGL(rank_lsep_train_kernel, dim3(unsigned((n_rows + 3) / 4), unsigned(n_mats)), dim3(256), 0, s, p);
@@ -906,30 +872,60 @@ int lamp_embed_bwd_ordered(const int64_t* src_seq, int64_t n_tokens, const float
     return int(hipGetLastError());
 }
 
-int lamp_optim_step(const lamp_optim_entry* entries, int32_t n, int32_t kind, int64_t step, double lr, double beta1,
-                    double beta2, double eps, lamp_stream_t stream) {
-    static_assert(sizeof(OptimEntry) == sizeof(lamp_optim_entry), "the table is copied entry by entry");
-    static_assert(sizeof(OptimParams) <= 4096, "kernel arguments");
-    if (n < 0) return LAMP_E_DIMS;
-    if (n == 0) return LAMP_OK;
-    if (!entries) return LAMP_E_NULL;
-    if (kind != LAMP_OPTIM_ADAM && kind != LAMP_OPTIM_SGD) return LAMP_E_UNSUPPORTED;
-    if (kind == LAMP_OPTIM_ADAM && step < 1) return LAMP_E_DIMS;
+// ---- the optimizer entries' shared host side --------------------------------------------------------------------------
+// The table batcher: cuts a table into launches of at most OPTIM_TABLE non-empty entries.  put(slot, i) stores entries[i] in
+// the launch's slot, chunk_start[] takes the running chunk counts and n_slots the count, launch(chunks) enqueues.  A launch ends
+// in front of the entry that would take it to 2^31 chunks; an entry that has that many alone is LAMP_E_UNSUPPORTED (after the
+// launches in front of it).
+template <class Put, class Launch>
+static int for_each_launch(const lamp_optim_entry* entries, int32_t n, int32_t* chunk_start, int32_t& n_slots, Put put, Launch launch) {
+    int i = 0;
+    while (i < n) {
+        int cnt = 0;
+        int64_t chunks = 0;
+        for (; i < n && cnt < OPTIM_TABLE; ++i) {
+            if (entries[i].numel == 0) continue;     // (an empty tensor has no storage to point to)
+            const int64_t c = (entries[i].numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
+            if (chunks + c >= (int64_t(1) << 31)) {
+                if (cnt == 0) return LAMP_E_UNSUPPORTED;
+                break;
+            }
+            put(cnt, i);
+            chunk_start[cnt] = int32_t(chunks);
+            chunks += c;
+            ++cnt;
+        }
+        if (cnt == 0) break;
+        chunk_start[cnt] = int32_t(chunks);
+        n_slots = cnt;
+        launch(chunks);
+        if (hipError_t e = hipGetLastError()) return int(e);
+    }
+    return LAMP_OK;
+}
+
+// Every non-empty entry of an optimizer step: numel (DIMS), the pointers its kind reads (NULL), 4-byte alignment (ALIGN).
+static int check_optim_entries(const lamp_optim_entry* entries, int32_t n, bool needs_m, bool needs_v) {
     for (int i = 0; i < n; ++i) {
         const lamp_optim_entry& e = entries[i];
         if (e.numel < 0) return LAMP_E_DIMS;
-        if (e.numel == 0) continue;      // (an empty tensor has no storage to point to)
-        if (!e.param || !e.grad || (kind == LAMP_OPTIM_ADAM && (!e.exp_avg || !e.exp_avg_sq))) return LAMP_E_NULL;
+        if (e.numel == 0) continue;
+        if (!e.param || !e.grad || (needs_m && !e.exp_avg) || (needs_v && !e.exp_avg_sq)) return LAMP_E_NULL;
         if ((reinterpret_cast<uintptr_t>(e.param) | reinterpret_cast<uintptr_t>(e.grad) |
              reinterpret_cast<uintptr_t>(e.exp_avg) | reinterpret_cast<uintptr_t>(e.exp_avg_sq)) & 3u)
             return LAMP_E_ALIGN;
     }
-    OptimParams p{};
+    return LAMP_OK;
+}
+
+// The scalars of a step, computed in double as torch computes them on the host (torch/optim/adam.py, _single_tensor_adam) and
+// rounded once.
+static void set_optim_scalars(OptimParams& p, int32_t kind, int64_t step, double lr, double beta1, double beta2, double eps) {
     p.beta2 = float(beta2);
     p.omb1 = float(1.0 - beta1);
     p.omb2 = float(1.0 - beta2);
     p.eps = float(eps);
-    if (kind == LAMP_OPTIM_ADAM) {   // the scalars torch computes on the host in double (torch/optim/adam.py, _single_tensor_adam)
+    if (kind == LAMP_OPTIM_ADAM) {
         const double bc1 = 1.0 - pow(beta1, double(step));
         const double bc2 = 1.0 - pow(beta2, double(step));
         p.lr = float(lr / bc1);
@@ -938,34 +934,30 @@ int lamp_optim_step(const lamp_optim_entry* entries, int32_t n, int32_t kind, in
         p.lr = float(lr);
         p.inv_bc2_sqrt = 1.f;
     }
-    hipStream_t s = hipStream_t(stream);
-    int i = 0;
-    while (i < n) {
-        int cnt = 0;
-        int64_t chunks = 0;
-        for (; i < n && cnt < OPTIM_TABLE; ++i) {
-            const lamp_optim_entry& e = entries[i];
-            if (e.numel == 0) continue;
-            const int64_t c = (e.numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
-            if (chunks + c >= (int64_t(1) << 31)) {
-                if (cnt == 0) return LAMP_E_UNSUPPORTED;
-                break;
-            }
-            p.e[cnt] = OptimEntry{e.param, e.grad, e.exp_avg, e.exp_avg_sq, e.numel};
-            p.chunk_start[cnt] = int32_t(chunks);
-            chunks += c;
-            ++cnt;
-        }
-        if (cnt == 0) break;
-        p.chunk_start[cnt] = int32_t(chunks);
-        p.n = cnt;
-        if (kind == LAMP_OPTIM_ADAM)
-            hipLaunchKernelGGL(optim_step_kernel<true>, dim3(unsigned(chunks)), dim3(256), 0, s, p);
-        else
-            hipLaunchKernelGGL(optim_step_kernel<false>, dim3(unsigned(chunks)), dim3(256), 0, s, p);
-        if (hipError_t e = hipGetLastError()) return int(e);
-    }
-    return LAMP_OK;
+}
+
+static OptimEntry optim_entry(const lamp_optim_entry& e) { return OptimEntry{e.param, e.grad, e.exp_avg, e.exp_avg_sq, e.numel}; }
+
+int lamp_optim_step(const lamp_optim_entry* entries, int32_t n, int32_t kind, int64_t step, double lr, double beta1,
+                    double beta2, double eps, lamp_stream_t stream) {
+    static_assert(sizeof(OptimEntry) == sizeof(lamp_optim_entry), "the table is copied entry by entry");
+    static_assert(sizeof(OptimParams) <= 4096, "kernel arguments");
+    if (n < 0) return LAMP_E_DIMS;
+    if (n == 0) return LAMP_OK;
+    if (!entries) return LAMP_E_NULL;
+    if (kind != LAMP_OPTIM_ADAM && kind != LAMP_OPTIM_SGD) return LAMP_E_UNSUPPORTED;
+    const bool adam = kind == LAMP_OPTIM_ADAM;
+    if (adam && step < 1) return LAMP_E_DIMS;
+    if (int st = check_optim_entries(entries, n, adam, adam)) return st;
+    OptimParams p{};
+    set_optim_scalars(p, kind, step, lr, beta1, beta2, eps);
+    const hipStream_t s = hipStream_t(stream);
+    return for_each_launch(
+        entries, n, p.chunk_start, p.n, [&](int slot, int i) { p.e[slot] = optim_entry(entries[i]); },
+        [&](int64_t chunks) {
+            if (adam) hipLaunchKernelGGL(optim_step_kernel<true>, dim3(unsigned(chunks)), dim3(256), 0, s, p);
+            else hipLaunchKernelGGL(optim_step_kernel<false>, dim3(unsigned(chunks)), dim3(256), 0, s, p);
+        });
 }
 
 // The chunk count of a table, or -1 when an entry's numel is negative / the count leaves int32 (the partials are indexed by it).
@@ -995,7 +987,7 @@ int lamp_grad_norm(const lamp_optim_entry* entries, int32_t n, double max_norm, 
     for (int i = 0; i < n; ++i)
         if (entries[i].numel < 0) return LAMP_E_DIMS;
     const int64_t total = grad_norm_chunks(entries, n);
-    if (total < 0) return LAMP_E_UNSUPPORTED;      // 2^31 chunks or more
+    if (total < 0) return LAMP_E_UNSUPPORTED;      // 2^31 chunks or more: the batcher below never has to cut for them
     for (int i = 0; i < n; ++i) {
         if (entries[i].numel == 0) continue;
         if (!entries[i].grad) return LAMP_E_NULL;
@@ -1006,30 +998,21 @@ int lamp_grad_norm(const lamp_optim_entry* entries, int32_t n, double max_norm, 
         return LAMP_E_ALIGN;
     if (total > 0 && !workspace) return LAMP_E_NULL;
     if (workspace_bytes < size_t(total) * sizeof(double)) return LAMP_E_WORKSPACE;
-    hipStream_t s = hipStream_t(stream);
+    const hipStream_t s = hipStream_t(stream);
     NormParams p{};
     int64_t done = 0;
-    int i = 0;
-    while (i < n) {
-        int cnt = 0;
-        int64_t chunks = 0;
-        for (; i < n && cnt < OPTIM_TABLE; ++i) {
-            const lamp_optim_entry& e = entries[i];
-            if (e.numel == 0) continue;
-            p.grad[cnt] = e.grad;
-            p.numel[cnt] = e.numel;
-            p.chunk_start[cnt] = int32_t(chunks);
-            chunks += (e.numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
-            ++cnt;
-        }
-        if (cnt == 0) break;
-        p.chunk_start[cnt] = int32_t(chunks);
-        p.n = cnt;
-        p.partial = static_cast<double*>(workspace) + done;
-        hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(unsigned(chunks)), dim3(256), 0, s, p);
-        if (hipError_t e = hipGetLastError()) return int(e);
-        done += chunks;
-    }
+    const int st = for_each_launch(
+        entries, n, p.chunk_start, p.n,
+        [&](int slot, int i) {
+            p.grad[slot] = entries[i].grad;
+            p.numel[slot] = entries[i].numel;
+        },
+        [&](int64_t chunks) {
+            p.partial = static_cast<double*>(workspace) + done;
+            hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(unsigned(chunks)), dim3(256), 0, s, p);
+            done += chunks;
+        });
+    if (st) return st;
     const bool clip = max_norm >= 0.0;
     hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, s, static_cast<const double*>(workspace), done,
                        clip ? float(max_norm) : 0.0f, clip ? 1 : 0, grad_state, skipped);
@@ -1062,65 +1045,29 @@ int lamp_optim_step_ext(const lamp_optim_entry* entries, int32_t n, int32_t kind
     const bool mom = ext->momentum != 0.0;
     if (!any_decay && !mom && !ext->grad_state)      // nothing asked for: the kernel it has always been, the same bits
         return lamp_optim_step(entries, n, kind, step, lr, beta1, beta2, eps, stream);
-    if (kind == LAMP_OPTIM_ADAM && step < 1) return LAMP_E_DIMS;
-    const bool needs_m = kind == LAMP_OPTIM_ADAM || mom;
-    for (int i = 0; i < n; ++i) {
-        const lamp_optim_entry& e = entries[i];
-        if (e.numel < 0) return LAMP_E_DIMS;
-        if (e.numel == 0) continue;
-        if (!e.param || !e.grad || (needs_m && !e.exp_avg) || (kind == LAMP_OPTIM_ADAM && !e.exp_avg_sq)) return LAMP_E_NULL;
-        if ((reinterpret_cast<uintptr_t>(e.param) | reinterpret_cast<uintptr_t>(e.grad) |
-             reinterpret_cast<uintptr_t>(e.exp_avg) | reinterpret_cast<uintptr_t>(e.exp_avg_sq)) & 3u)
-            return LAMP_E_ALIGN;
-    }
+    const bool adam = kind == LAMP_OPTIM_ADAM;
+    if (adam && step < 1) return LAMP_E_DIMS;
+    if (int st = check_optim_entries(entries, n, adam || mom, adam)) return st;
     OptimExtParams x{};
     OptimParams& p = x.o;
-    p.beta2 = float(beta2);
-    p.omb1 = float(1.0 - beta1);
-    p.omb2 = float(1.0 - beta2);
-    p.eps = float(eps);
-    if (kind == LAMP_OPTIM_ADAM) {
-        const double bc1 = 1.0 - pow(beta1, double(step));
-        const double bc2 = 1.0 - pow(beta2, double(step));
-        p.lr = float(lr / bc1);
-        p.inv_bc2_sqrt = float(1.0 / sqrt(bc2));
-    } else {
-        p.lr = float(lr);
-        p.inv_bc2_sqrt = 1.f;
-    }
+    set_optim_scalars(p, kind, step, lr, beta1, beta2, eps);
     x.grad_state = ext->grad_state;
     x.momentum = float(ext->momentum);
     x.decay_mode = !any_decay ? DECAY_NONE : decoupled ? DECAY_DECOUPLED : DECAY_L2;
     x.skip_nonfinite = skip ? 1 : 0;
-    hipStream_t s = hipStream_t(stream);
-    int i = 0;
-    while (i < n) {
-        int cnt = 0;
-        int64_t chunks = 0;
-        for (; i < n && cnt < OPTIM_TABLE; ++i) {
-            const lamp_optim_entry& e = entries[i];
-            if (e.numel == 0) continue;
-            const int64_t c = (e.numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
-            if (chunks + c >= (int64_t(1) << 31)) {
-                if (cnt == 0) return LAMP_E_UNSUPPORTED;
-                break;
-            }
-            p.e[cnt] = OptimEntry{e.param, e.grad, e.exp_avg, e.exp_avg_sq, e.numel};
+    const hipStream_t s = hipStream_t(stream);
+    return for_each_launch(
+        entries, n, p.chunk_start, p.n,
+        [&](int slot, int i) {
+            p.e[slot] = optim_entry(entries[i]);
             const float wd = any_decay ? ext->entry_weight_decay[i] : 0.f;
             // AdamW's factor is taken in double on the host and rounded once, as torch passes it to param.mul_
-            x.decay[cnt] = x.decay_mode == DECAY_DECOUPLED ? float(1.0 - lr * double(wd)) : wd;
-            p.chunk_start[cnt] = int32_t(chunks);
-            chunks += c;
-            ++cnt;
-        }
-        if (cnt == 0) break;
-        p.chunk_start[cnt] = int32_t(chunks);
-        p.n = cnt;
-        const dim3 grid = dim3(unsigned(chunks)), block = dim3(256);
-        if (kind == LAMP_OPTIM_ADAM) hipLaunchKernelGGL(optim_step_ext_kernel<OPT_ADAM>, grid, block, 0, s, x);
-        else if (mom) hipLaunchKernelGGL(optim_step_ext_kernel<OPT_SGD_MOMENTUM>, grid, block, 0, s, x);
-        else hipLaunchKernelGGL(optim_step_ext_kernel<OPT_SGD>, grid, block, 0, s, x);
-        if (hipError_t e = hipGetLastError()) return int(e);
-    }
-    return LAMP_OK;
+            x.decay[slot] = x.decay_mode == DECAY_DECOUPLED ? float(1.0 - lr * double(wd)) : wd;
+        },
+        [&](int64_t chunks) {
+            const dim3 grid = dim3(unsigned(chunks)), block = dim3(256);
+            if (adam) hipLaunchKernelGGL(optim_step_ext_kernel<OPT_ADAM>, grid, block, 0, s, x);
+            else if (mom) hipLaunchKernelGGL(optim_step_ext_kernel<OPT_SGD_MOMENTUM>, grid, block, 0, s, x);
+            else hipLaunchKernelGGL(optim_step_ext_kernel<OPT_SGD>, grid, block, 0, s, x);
+        });
 }

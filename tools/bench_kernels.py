@@ -863,6 +863,177 @@ def attn_lib_bits():
     sys.exit(1 if bad else 0)
 
 
+def train_lib_bits(rounds=11):
+    """Bit check of BUILDS of the library (argv[2:]: paths; the first is the reference) on the two ends of the training step
+    (csrc/train_step.hip), seeded inputs, a few seconds.  One line per case, exit status 1 on any difference.
+    Loss launches: 5 rows (a partial four-row workgroup), 1 and 3 matrices, probs through a wider row stride and absent, dlogits
+    given and NULL, with and without one NaN logit in one row.  Wave kernels (BCE; the four multilabel specialisations with and
+    without pos_weight; LSEP at bce_weight 0 and 1) at L = 1, 63, 64, 65, 200; pair kernels (hinge, logistic; bce_weight 0 and 1)
+    at L = 1, 64, 257, 4096 with 0, 1, 3, L/2 and L positives per row (the empty class, the sliced and the strided direction).
+    Optimizer: lamp_optim_step (Adam, SGD) and lamp_optim_step_ext (L2 and decoupled decay, SGD alone and with momentum), each
+    without a clip record, with lamp_grad_norm's record, and with LAMP_OPTIM_SKIP_NONFINITE on a table that holds an inf
+    gradient in its first step; over the sizes of tests/optim_ext_common.py (12293 one float past a 16-byte boundary, 0) and
+    over its 80-entry table (two launches); every parameter and moment, the four-float record and `skipped` are compared after
+    one step and after two.
+    --time (the first TWO paths are then two copies of the reference's file, so that every case carries its own noise floor):
+    also times the lamp_optim_step_ext cases on the SGD kernels, HIP events, median of `rounds` windows, libraries alternating;
+    a case is out when the last library's median exceeds the larger reference median by more than the two references differ."""
+    import statistics
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import optim_ext_common as XC
+    timed = '--time' in sys.argv[2:]
+    libs = [(os.path.basename(p), N.load_library(p)) for p in sys.argv[2:] if p != '--time']
+    dev = torch.device('cuda:0')
+    gen = torch.Generator().manual_seed(21)
+    bad = total = 0
+
+    def verdicts(res):
+        nonlocal bad, total
+        v = ['same bits' if all(_same_bits(a, b) for a, b in zip(r, res[0])) else 'DIFFERENT' for r in res[1:]]
+        total += 1
+        bad += 'DIFFERENT' in v
+        return ' '.join(v)
+
+    # ---- the loss launches
+    B = 5
+    vp = ctypes.c_void_p
+
+    def loss_run(lib, entry, opts, xs, z, wts, wide, want_grads, L):
+        n = len(xs)
+        ld = L + 3 if wide else L
+        probs = torch.full((B, ld), -7.0, device=dev) if wide is not None else None
+        grads = [torch.full_like(x, -7.0) for x in xs] if want_grads else []
+        row_loss = torch.full((n, B), -7.0, device=dev)
+        xp, wp = (vp * n)(*[x.data_ptr() for x in xs]), (ctypes.c_float * n)(*wts)
+        gp = (vp * n)(*[g.data_ptr() for g in grads]) if want_grads else None
+        args = (xp, wp, gp, n, z.data_ptr(), B, L, N.ptr(probs), ld, row_loss.data_ptr(), B)
+        more = () if opts is None else (ctypes.byref(opts),)
+        N.check(getattr(lib, entry)(*args, *more, N.stream()), entry)
+        return ([probs] if probs is not None else []) + grads + [row_loss]
+
+    def loss_cases(name, entry, make_opts, L, z):
+        for n in (1, 3):
+            for wide in (True, None):
+                for want_grads in (True, False):
+                    for nan in (False, True):
+                        xs = [(torch.randn(B, L, generator=gen) * 3).to(dev) for _ in range(n)]
+                        if nan:
+                            xs[n - 1][3, L // 2] = float('nan')
+                        wts = [1.0, 0.5, 0.25][:n]
+                        res = [loss_run(lib, entry, make_opts(), xs, z, wts, wide, want_grads, L) for _, lib in libs]
+                        torch.cuda.synchronize()
+                        print('%-34s L %4d  mats %d  probs %-5s dlogits %-5s %-4s %s' % (
+                            name, L, n, 'wide' if wide else 'none', 'given' if want_grads else 'NULL', 'NaN' if nan else '', verdicts(res)))
+
+    for L in (1, 63, 64, 65, 200):
+        z = (torch.rand(B, L, generator=gen) < 0.3).float().to(dev)
+        pw = (torch.rand(L, generator=gen) * 4 + 0.5).to(dev)
+        loss_cases('bce', 'lamp_bce_logits_train', lambda: None, L, z)
+        for gp_, gn_, clip in ((0., 0., 0.), (0., 0., 0.05), (2., 2., 0.), (1., 4., 0.05)):     # <F, F>, <F, T>, <T, F>, <T, T>
+            for w in (None, pw):
+                loss_cases('multilabel g+ %g g- %g m %g %s' % (gp_, gn_, clip, 'pos_weight' if w is not None else ''),
+                           'lamp_multilabel_loss_train', lambda: N.LossOptions(gp_, gn_, clip, 0, N.ptr(w)), L, z)
+        for beta in (0., 1.):
+            loss_cases('lsep bce_weight %g' % beta, 'lamp_rank_loss_train', lambda: N.RankLossOptions(N.LAMP_RANK_LSEP, 0., beta, 0), L, z)
+    for L in (1, 64, 257, 4096):
+        for n_p in sorted({k for k in (0, 1, 3, L // 2, L) if k <= L}):
+            z = torch.zeros(B, L)
+            for r in range(B):
+                z[r, torch.randperm(L, generator=gen)[:n_p]] = 1.0
+            z = z.to(dev)
+            for kind, kname, margin in ((N.LAMP_RANK_HINGE, 'hinge', 1.0), (N.LAMP_RANK_LOGISTIC, 'logistic', 0.0)):
+                for beta in (0., 1.):
+                    loss_cases('%s n_p %d bce_weight %g' % (kname, n_p, beta), 'lamp_rank_loss_train',
+                               lambda: N.RankLossOptions(kind, margin, beta, 0), L, z)
+
+    # ---- the optimizer step
+    def place(t, misaligned):
+        """a device copy; misaligned: one float past a 16-byte boundary"""
+        if not misaligned:
+            return t.to(dev)
+        buf = torch.empty(t.numel() + 1, device=dev)
+        buf[1:].copy_(t)
+        return buf[1:]
+
+    tables = {'sizes': XC.norm_case(seed=3), 'long table': XC.long_table_case(seed=4)}
+    # name -> (entry, kind, weight decay, decoupled, momentum)
+    configs = {'optim_step adam': ('step', N.LAMP_OPTIM_ADAM, 0., False, 0.), 'optim_step sgd': ('step', N.LAMP_OPTIM_SGD, 0., False, 0.),
+               'ext adam l2': ('ext', N.LAMP_OPTIM_ADAM, 0.05, False, 0.), 'ext adamw': ('ext', N.LAMP_OPTIM_ADAM, 0.01, True, 0.),
+               'ext sgd l2': ('ext', N.LAMP_OPTIM_SGD, 0.05, False, 0.), 'ext sgd momentum': ('ext', N.LAMP_OPTIM_SGD, 0., False, 0.9),
+               'ext sgd momentum l2': ('ext', N.LAMP_OPTIM_SGD, 0.05, False, 0.9)}
+
+    def optim_state(params, kind, momentum):
+        ps = [place(t, t.numel() == XC.MISALIGNED) for t in params]
+        ms = [place(torch.zeros_like(t), t.numel() == XC.MISALIGNED) for t in params] if kind == N.LAMP_OPTIM_ADAM or momentum else None
+        vs = [place(torch.zeros_like(t), t.numel() == XC.MISALIGNED) for t in params] if kind == N.LAMP_OPTIM_ADAM else None
+        return ps, ms, vs, torch.full((4,), -7.0, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def optim_call(lib, cfg, clip, state, grads, step, max_norm):
+        entry, kind, wd, decoupled, momentum = cfg
+        ps, ms, vs, record, skipped = state
+        n = len(ps)
+        arr = N._optim_table([(ps[i], grads[i], ms[i] if ms else None, vs[i] if vs else None) for i in range(n)])
+        lr = 2e-3 if kind == N.LAMP_OPTIM_ADAM else 0.05
+        if entry == 'step':
+            N.check(lib.lamp_optim_step(arr, n, kind, step, lr, 0.9, 0.98, 1e-8, N.stream()), 'lamp_optim_step')
+            return
+        if clip != 'none':
+            ws = N.grad_norm_workspace(lib.lamp_grad_norm_workspace_bytes(arr, n), dev)
+            N.check(lib.lamp_grad_norm(arr, n, max_norm, N.ptr(ws), ws.numel(), N.ptr(record), N.ptr(skipped), N.stream()), 'lamp_grad_norm')
+        wds = (ctypes.c_float * n)(*[wd if i % 2 == 0 else 0. for i in range(n)]) if wd else None
+        ext = N.OptimExt(wds, N.ptr(record) if clip != 'none' else None, momentum,
+                         (N.LAMP_OPTIM_DECOUPLED_DECAY if decoupled else 0) | (N.LAMP_OPTIM_SKIP_NONFINITE if clip == 'skip' else 0), 0)
+        N.check(lib.lamp_optim_step_ext(arr, n, kind, step, lr, 0.9, 0.98, 1e-8, ctypes.byref(ext), N.stream()), 'lamp_optim_step_ext')
+
+    for tname, params in tables.items():
+        grads = [[place(torch.randn(t.shape, generator=gen) * 0.1, t.numel() == XC.MISALIGNED) for t in params] for _ in range(2)]
+        inf_grads = list(grads[0])
+        inf_grads[2] = grads[0][2].clone()
+        inf_grads[2][min(5, inf_grads[2].numel() - 1)] = float('inf')
+        max_norm = 0.5 * XC.norm64([g.cpu() for g in grads[0]])          # binds in the first step
+        for cname, cfg in configs.items():
+            for clip in ('none',) if cfg[0] == 'step' else ('none', 'clip', 'skip'):
+                states = [optim_state(params, cfg[1], cfg[4]) for _ in libs]
+                for step in (1, 2):
+                    gs = inf_grads if clip == 'skip' and step == 1 else grads[step - 1]
+                    for (_, lib), st in zip(libs, states):
+                        optim_call(lib, cfg, clip, st, gs, step, max_norm)
+                    torch.cuda.synchronize()
+                    res = [ps + (ms or []) + (vs or []) + [record, skipped.float()] for ps, ms, vs, record, skipped in states]
+                    print('%-22s %-11s %-5s after step %d  %s' % (cname, tname, clip, step, verdicts(res)))
+    print('%d cases, %d with a difference (%s)' % (total, bad, ' vs '.join(n for n, _ in libs)))
+
+    # ---- timing of the cases on the kernels whose instruction streams moved (the two SGD instantiations of optim_step_ext)
+    out = 0
+    if timed:
+        tables['big'] = [torch.randn(n, generator=gen) for n in (1 << 20, 1 << 18, (1 << 16) + 3, 512, 512)]
+        print('%-22s %-11s %-5s' % ('median us', '', '') + ''.join('%26s' % n for n, _ in libs))
+        for tname, params in tables.items():
+            grads = [place(torch.randn(t.shape, generator=gen) * 0.1, t.numel() == XC.MISALIGNED) for t in params]
+            for cname in ('ext sgd l2', 'ext sgd momentum', 'ext sgd momentum l2'):
+                cfg = configs[cname]
+                for clip in ('none', 'clip'):
+                    states = [optim_state(params, cfg[1], cfg[4]) for _ in libs]
+                    for (_, lib), st in zip(libs, states):       # the record is computed once; the windows hold the step alone
+                        optim_call(lib, cfg, clip, st, grads, 1, 1e6)
+                    samples = [[] for _ in libs]
+                    for _ in range(rounds):
+                        for i, ((_, lib), st) in enumerate(zip(libs, states)):
+                            ps, ms, vs, record, skipped = st
+                            n = len(ps)
+                            arr = N._optim_table([(ps[j], grads[j], ms[j] if ms else None, None) for j in range(n)])
+                            wds = (ctypes.c_float * n)(*[cfg[2] if j % 2 == 0 else 0. for j in range(n)]) if cfg[2] else None
+                            ext = N.OptimExt(wds, N.ptr(record) if clip == 'clip' else None, cfg[4], 0, 0)
+                            fn = lambda: lib.lamp_optim_step_ext(arr, n, cfg[1], 1, 1e-5, 0.9, 0.98, 1e-8, ctypes.byref(ext), N.stream())
+                            samples[i].append(time_fn(fn, iters=20, warm=3))
+                    med = [statistics.median(x) for x in samples]
+                    ok = len(med) < 3 or med[-1] <= max(med[0], med[1]) + abs(med[0] - med[1])
+                    out += not ok
+                    print('%-22s %-11s %-5s' % (cname, tname, clip) + ''.join('%26.3f' % m for m in med) + ('' if ok else '   OUT'))
+        print('%d timed cases outside their noise floor' % out)
+    sys.exit(1 if bad or out else 0)
+
+
 def attn_one():
     """One attention shape, heuristic variant, bit-packed shared mask, a handful of launches: small enough for a
     rocprofv3 --pmc pass (tools/pmc_ta.sh).  argv[2] = case name prefix (default 'synthetic self')."""
@@ -1098,5 +1269,5 @@ def gemm_clock():
 if __name__ == '__main__':
     which = sys.argv[1] if len(sys.argv) > 1 else 'gemm'
     {'gemm': gemm, 'gemm_ab': gemm_ab, 'lib_ab': lib_ab, 'walk': walk, 'walk_pmc': walk_pmc, 'gemm_gen': gemm_gen, 'attn': attn, 'steady': steady, 'sparse': sparse, 'sparse_rows': sparse_rows,
-     'gemm_trace': gemm_trace, 'gemm_clock': gemm_clock, 'attn_lib_ab': attn_lib_ab, 'attn_lib_bits': attn_lib_bits, 'attn_tile': attn_tile, 'chain': chain, 'ln': ln, 'attn_one': attn_one, 'attn_maps': attn_maps, 'attn_trace': attn_trace, 'residency': residency, 'slab': slab, 'gemm_packed': gemm_packed,
+     'gemm_trace': gemm_trace, 'gemm_clock': gemm_clock, 'attn_lib_ab': attn_lib_ab, 'attn_lib_bits': attn_lib_bits, 'train_lib_bits': train_lib_bits, 'attn_tile': attn_tile, 'chain': chain, 'ln': ln, 'attn_one': attn_one, 'attn_maps': attn_maps, 'attn_trace': attn_trace, 'residency': residency, 'slab': slab, 'gemm_packed': gemm_packed,
      'gemm_packed_residency': gemm_packed_residency}[which]()
