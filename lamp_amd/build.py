@@ -31,7 +31,8 @@ LIB_TUNING = os.path.join(HERE, 'liblamp_hip_tuning.so')
 SOURCES = ['gemm.hip', 'gemm_split.hip', 'gemm_gen.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_general.hip', 'attention_sparse.hip',
            'attention_ragged.hip', 'attention_sigmoid.hip', 'attention_bias.hip', 'pointwise.hip',
            'backward.hip', 'chain.hip', 'conv.hip', 'metrics.hip', 'thresholds.hip', 'rank_at_k.hip', 'train_step.hip', 'api.hip']
-TUNING_SOURCES = {'gemm.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_sparse.hip', 'chain.hip'}
+TUNING_SOURCES = {'gemm.hip', 'attention.hip', 'attention_tile.hip', 'attention_small.hip', 'attention_sparse.hip', 'chain.hip',
+                  'pointwise.hip'}
 TUNING_ONLY = ['experiments/slab.hip']   # experiments kept bit-identical and benchmarkable, never part of the product library
 HEADERS = [os.path.join(CSRC, 'lamp_kernels.h'), os.path.join(CSRC, 'lamp_asm.h'), os.path.join(CSRC, 'attn16_frag.h'),
            os.path.join(HERE, '..', 'include', 'lamp_hip.h')]

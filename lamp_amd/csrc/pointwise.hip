@@ -203,6 +203,9 @@ struct PlanGranules {
     unsigned long long* plen;   // [nb]
     unsigned long long* off;    // [nb + 2]: off[b]; [nb] = n_tok; [nb + 1] = 1 when some position is skipped
     unsigned epoch;
+#ifdef LAMP_TUNING
+    int mode;   // lamp_debug_embed_plan_mode: bit 0 no plen granules, bit 1 no off granules, bit 2 no dense shortcut
+#endif
 };
 __device__ __forceinline__ void granule_put(unsigned long long* g, unsigned v, unsigned epoch) {
     __hip_atomic_store(g, (static_cast<unsigned long long>(epoch) << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -259,6 +262,9 @@ __device__ __forceinline__ void plan_prefix(const int64_t* __restrict__ seq, con
         const int off = carry + incl - pl;
         if (publish && valid) {
             sp.off[l] = off;
+#ifdef LAMP_TUNING
+            if (!(gr.mode & 2))
+#endif
             granule_put(gr.off + l, unsigned(off), gr.epoch);
         }
         if (want >= 0 && want >= base && want < base + 64) {
@@ -285,6 +291,9 @@ __global__ __launch_bounds__(256) void embed_plan_kernel(const int64_t* __restri
             if (lane == 0) {
                 sp.klen[b] = kl;
                 sp.plen[b] = pl;
+#ifdef LAMP_TUNING
+                if (!(gr.mode & 1))   // withheld: the scanner and the gather waves count this sample themselves
+#endif
                 granule_put(gr.plen + b, unsigned(pl), gr.epoch);
             }
         }
@@ -297,6 +306,9 @@ __global__ __launch_bounds__(256) void embed_plan_kernel(const int64_t* __restri
             sp.off[nb] = total;
             sp.rows[0] = total;
             sp.rows[1] = total + (any_skipped ? 1 : 0);
+#ifdef LAMP_TUNING
+            if (gr.mode & 2) return;   // withheld: the PAD-row wave takes its own prefix sum over all samples
+#endif
             granule_put(gr.off + nb, unsigned(total), gr.epoch);
             granule_put(gr.off + nb + 1, any_skipped ? 1u : 0u, gr.epoch);
         }
@@ -326,6 +338,9 @@ __global__ __launch_bounds__(256) void embed_plan_kernel(const int64_t* __restri
             const int64_t lt = seq[at], lp = plan_pos ? plan_pos[at] : 0;
             dense = dense && __all(bb >= nb || lt != 0 || lp != 0);
         }
+#ifdef LAMP_TUNING
+        if (gr.mode & 4) dense = false;   // the shortcut is off: a fixed-length batch goes through the hand-off too
+#endif
         if (dense) {
             va = pad_row ? 0u : unsigned(T);
             vb = pad_row ? unsigned(n_flat) : unsigned(b) * unsigned(T);
@@ -642,6 +657,14 @@ int launch_embed_packed(const int64_t* seq, const int64_t* pos, int nb, int T, c
     return int(hipGetLastError());
 }
 
+#ifdef LAMP_TUNING
+// Forces embed_plan_kernel's fall-back routes, which an idle GPU never takes (tests/test_ragged_plan_gpu.py).  Bit flags: 1 = the
+// plan waves withhold their plen granules, 2 = the scanner withholds every off granule (n_tok and the skipped word included),
+// 4 = no dense shortcut; -1 or 0 = product behaviour.  Stores are withheld and a shortcut is skipped: no wait, no loop is added.
+static int g_embed_plan_mode = 0;
+extern "C" __attribute__((visibility("default"))) void lamp_debug_embed_plan_mode(int mode) { g_embed_plan_mode = mode < 0 ? 0 : mode & 7; }
+#endif
+
 // Plan + packed gather in one launch (embed_plan_kernel).  `granules`: 2 * nb + 2 unsigned 64-bit words of workspace, any content.
 int launch_embed_plan(const int64_t* seq, const int64_t* pos, bool plan_uses_pos, int nb, int T, const float* emb, int n_vocab,
                       const float* pos_table, int n_position, int d, const SeqPlan& sp, unsigned long long* granules, float* out,
@@ -662,6 +685,9 @@ int launch_embed_plan(const int64_t* seq, const int64_t* pos, bool plan_uses_pos
     unsigned epoch = epoch_counter.fetch_add(1, std::memory_order_relaxed);
     if (epoch == 0) epoch = epoch_counter.fetch_add(1, std::memory_order_relaxed);
     PlanGranules gr{granules, granules + nb, epoch};
+#ifdef LAMP_TUNING
+    gr.mode = g_embed_plan_mode;
+#endif
     ProfScope prof(LAMP_K_EMBED, 0.0, 16.0 * double(n_tok) + embed_bytes(n_tok, d, pos_table != nullptr, f), s);
     hipLaunchKernelGGL(embed_plan_kernel, dim3(g + unsigned(n_plan)), dim3(256), 0, s, seq, pos, plan_uses_pos ? pos : nullptr, nb, T, emb,
                        n_vocab, pos_table, n_position, d, sp, gr, n_plan, out, f);
