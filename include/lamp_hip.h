@@ -1125,6 +1125,32 @@ typedef struct lamp_optim_ext {
 int lamp_optim_step_ext(const lamp_optim_entry* entries, int32_t n, int32_t kind, int64_t step, double lr, double beta1,
                         double beta2, double eps, const lamp_optim_ext* ext, lamp_stream_t stream);
 
+/* An average of the weights (EMA, SWA) kept beside them, in one launch per 72 table entries, after optimizer.step().
+ * entries: lamp_optim_step's HOST table; `param` is the live weight and is READ ONLY, `exp_avg` is the average and is updated
+ * in place, `grad` and `exp_avg_sq` are ignored (may be NULL), `numel` counts elements.  weight in [0, 1] is rounded to fp32
+ * once on the host.  Per element, without contraction, torch's lerp (what _foreach_lerp_ does for
+ * torch.optim.swa_utils.get_ema_multi_avg_fn / get_swa_multi_avg_fn), a = the average, p = the weight:
+ *     w < 0.5:  a = a + w (p - a)          otherwise:  a = p - (p - a)(1 - w)
+ * with three defined edges:
+ *   w == 1   copies the 32-bit patterns of p (the first update of an average; NaN payloads included);
+ *   w == 0   launches nothing;
+ *   p == a   leaves a as it is: a label bias holds -inf where an edge never moves, and -inf - -inf would make the average
+ *            NaN there (torch's lerp does; this does not).
+ * A NaN or an infinity anywhere else behaves as fp32 arithmetic does and touches its own element only.
+ * lamp_optim_step's geometry: one 256-lane workgroup per 4096-element chunk of an entry, 16-byte accesses when both pointers
+ * of the entry allow them (the last numel % 4 elements by single lanes), 4-byte accesses otherwise; zero-numel entries are
+ * skipped; an entry may pass 2^32 bytes.  No LDS, no atomics, no workspace, nothing synchronised.  Elementwise: bit-identical
+ * from run to run and independent of the table an entry travels in.  An entry whose param and exp_avg are the SAME pointer
+ * is a no-op.  Refused before any launch: LAMP_E_DIMS (n < 0, numel < 0), LAMP_E_NULL (entries; param or exp_avg of a
+ * non-empty entry), LAMP_E_ALIGN (a pointer that is not 4-byte aligned), LAMP_E_UNSUPPORTED (a weight outside [0, 1] or NaN,
+ * an entry of 2^31 chunks, a param and an exp_avg that overlap without being identical). */
+int lamp_weight_average(const lamp_optim_entry* entries, int32_t n, double weight, lamp_stream_t stream);
+
+/* Exchanges the 32-bit patterns of `param` and `exp_avg` of every entry (evaluate the average in place, then swap back): NaN
+ * payloads are preserved and two calls are the identity.  Table, geometry and refusals are lamp_weight_average's (no weight).
+ * The caller bumps the version counters of what it swapped (lamp_amd/optim.py: WeightAverage.swap). */
+int lamp_weight_swap(const lamp_optim_entry* entries, int32_t n, lamp_stream_t stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline) ------ */
 enum lamp_kernel_class {
     LAMP_K_EMBED = 0, LAMP_K_GEMM = 1, LAMP_K_ATTN = 2, LAMP_K_LAYERNORM = 3, LAMP_K_DIAG = 4,

@@ -263,6 +263,8 @@ PROTOTYPES = {
     'lamp_grad_norm_workspace_bytes': (_sz, [C.POINTER(OptimEntry), _i32]),
     'lamp_grad_norm': (C.c_int, [C.POINTER(OptimEntry), _i32, C.c_double, _vp, _sz, _vp, _vp, _vp]),
     'lamp_optim_step_ext': (C.c_int, [C.POINTER(OptimEntry), _i32, _i32, _i64] + [C.c_double] * 4 + [C.POINTER(OptimExt), _vp]),
+    'lamp_weight_average': (C.c_int, [C.POINTER(OptimEntry), _i32, C.c_double, _vp]),
+    'lamp_weight_swap': (C.c_int, [C.POINTER(OptimEntry), _i32, _vp]),
     'lamp_sdpa_act_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _i32,
                                     C.POINTER(Mask), C.POINTER(AttnLayout), _vp]),
     'lamp_mha_act_fwd': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(MhaWeights), _i32,
@@ -284,7 +286,8 @@ LATE_ENTRY_POINTS = ('lamp_linear_packed_fwd', 'lamp_forward_packs', 'lamp_forwa
                      'lamp_label_bias_fold', 'lamp_topk_labels', 'lamp_rank_at_k_workspace_bytes', 'lamp_rank_at_k',
                      'lamp_tune_thresholds_workspace_bytes', 'lamp_tune_thresholds', 'lamp_threshold_counts_vec',
                      'lamp_multilabel_loss_train', 'lamp_grad_norm_workspace_bytes', 'lamp_grad_norm', 'lamp_optim_step_ext',
-                     'lamp_rank_loss_train', 'lamp_label_ranking_workspace_bytes', 'lamp_label_ranking')
+                     'lamp_rank_loss_train', 'lamp_label_ranking_workspace_bytes', 'lamp_label_ranking', 'lamp_weight_average',
+                     'lamp_weight_swap')
 
 _lib = None
 _lock = threading.Lock()
@@ -1326,6 +1329,43 @@ def optim_step_ext(entries, kind, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, we
                    (LAMP_OPTIM_SKIP_NONFINITE if skip_nonfinite else 0), 0)
     check(lib().lamp_optim_step_ext(arr, n, int(kind), int(step), float(lr), float(beta1), float(beta2), float(eps),
                                     C.byref(ext), stream()), 'lamp_optim_step_ext')
+
+
+def average_table(who, entries):
+    n = len(entries)
+    arr = (OptimEntry * n)()
+    for i, (p, a) in enumerate(entries):
+        if not (p.dtype == torch.float32 and a.dtype == torch.float32 and p.is_contiguous() and a.is_contiguous()):
+            raise RuntimeError('%s: contiguous fp32 tensors only; entry %d is %s / %s' % (who, i, p.dtype, a.dtype))
+        if p.numel() != a.numel() or p.device != a.device:
+            raise ValueError('%s: entry %d: the weight has %d elements on %s, its average %d on %s' %
+                             (who, i, p.numel(), p.device, a.numel(), a.device))
+        e = arr[i]
+        e.param, e.exp_avg, e.numel = p.data_ptr(), a.data_ptr(), p.numel()
+    require_device(*[t for e in entries for t in e])
+    return arr
+
+
+def weight_average(entries, weight, table=None):
+    """lamp_weight_average over [(param, avg)]: contiguous fp32 device tensors of one device (the current one).  avg becomes
+    torch's lerp(avg, param, weight) in place -- weight 1 copies the bits, weight 0 launches nothing, an element whose two sides
+    compare equal keeps its average (include/lamp_hip.h) -- and param is only read.  The caller bumps avg's version counter.
+    `table`: what average_table() made of these very entries (a caller whose pointers are stable keeps it between calls)."""
+    n = len(entries)
+    if n == 0:
+        return
+    arr = table if table is not None else average_table('weight_average', entries)
+    check(lib().lamp_weight_average(arr, n, float(weight), stream()), 'lamp_weight_average')
+
+
+def weight_swap(entries, table=None):
+    """lamp_weight_swap over [(param, avg)]: the two tensors of every entry exchange their bits.  The caller bumps the version
+    counters of both (the eval path's weights-only tables are keyed on them)."""
+    n = len(entries)
+    if n == 0:
+        return
+    arr = table if table is not None else average_table('weight_swap', entries)
+    check(lib().lamp_weight_swap(arr, n, stream()), 'lamp_weight_swap')
 
 
 # ------------------------------------------------------------------ profiling

@@ -19,6 +19,8 @@
 //               record {norm, scale, finite, 0} that optim_step_ext reads.  No atomics.
 //   optim_step_ext  optim_step behind gradient clipping (the record's scale, applied in registers), per-entry weight decay
 //               (L2 or decoupled), SGD momentum, and "write nothing when the norm is not finite".
+//   weight_average / weight_swap  an average of the weights (EMA, SWA) kept beside them: torch's lerp of (param, exp_avg) over the
+//               optimizer's table in optim_step's geometry, and the exchange of the two; walk_chunk2 is their two-pointer walk.
 //   embed_bwd_ordered  the embedding scatter-add without atomics (see the kernel), so that an epoch is reproducible.
 // All are enqueued on the caller's stream; neither allocates, synchronises or reads anything back.
 //
@@ -735,6 +737,80 @@ __global__ __launch_bounds__(256) void optim_step_ext_kernel(const OptimExtParam
                              [&](float& w, float g, float& m, float& v) { optim_update_ext<KIND>(w, g, m, v, p, s); });
 }
 
+// ---- lamp_weight_average / lamp_weight_swap: optim_step_kernel's geometry over the two pointers (param, exp_avg) ----------
+// The table is OptimParams itself (grad and exp_avg_sq are carried and never read); the only scalar, the weight, travels in
+// `lr`.  1 - w is taken in fp32 as torch takes it; it is only used for w >= 0.5, where it is exact.
+// torch's lerp (ATen/native/Lerp.h) with a = the average, p = the weight:  w < 0.5: a + w (p - a);  else p - (p - a)(1 - w).
+// Two deviations (include/lamp_hip.h): w == 1 copies the bits, and an element with p == a keeps a (-inf - -inf would be NaN).
+template <bool COPY>
+__device__ __forceinline__ void average_update(float p, float& a, float w) {
+#pragma clang fp contract(off)
+    if (COPY) {
+        a = p;
+    } else if (p != a) {                                    // (a NaN on either side compares unequal and spreads)
+        const float d = p - a;
+        a = w < 0.5f ? a + w * d : p - d * (1.0f - w);
+    }
+}
+
+// walk_chunk's walk for two pointers: update(p, a) with both loaded before it and both stored after it when STORE_P (the swap),
+// p read only otherwise (the average).  COPY / swap move 32-bit patterns: a float4 load and store keep a NaN's payload.
+template <bool STORE_P, class Update>
+__device__ __forceinline__ void walk_chunk2(const OptimEntry& t, int64_t off, Update update) {
+    const int64_t left = t.numel - off;
+    const int n = left < OPTIM_CHUNK ? int(left) : OPTIM_CHUNK;
+    float* __restrict__ p = t.param + off;
+    float* __restrict__ a = t.exp_avg + off;
+    const int tid = int(threadIdx.x);
+    // off is a multiple of 4096 floats: the chunk is 16-byte aligned iff the tensor is
+    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(a)) & 15u) == 0) {
+        const int nq = n >> 2;
+        for (int q = tid; q < nq; q += 256) {
+            float4 p4 = reinterpret_cast<const float4*>(p)[q];
+            float4 a4 = reinterpret_cast<float4*>(a)[q];
+            update(p4.x, a4.x);
+            update(p4.y, a4.y);
+            update(p4.z, a4.z);
+            update(p4.w, a4.w);
+            if (STORE_P) reinterpret_cast<float4*>(p)[q] = p4;
+            reinterpret_cast<float4*>(a)[q] = a4;
+        }
+        const int i = (nq << 2) + tid;      // the tail: at most three single lanes
+        if (i < n) {
+            float pi = p[i], ai = a[i];
+            update(pi, ai);
+            if (STORE_P) p[i] = pi;
+            a[i] = ai;
+        }
+    } else {
+        for (int i = tid; i < n; i += 256) {
+            float pi = p[i], ai = a[i];
+            update(pi, ai);
+            if (STORE_P) p[i] = pi;
+            a[i] = ai;
+        }
+    }
+}
+
+template <bool COPY>
+__global__ __launch_bounds__(256) void weight_average_kernel(const OptimParams p) {
+    const int b = int(blockIdx.x);
+    const int lo = table_entry(p.chunk_start, p.n, b);
+    const float w = p.lr;
+    walk_chunk2<false>(p.e[lo], int64_t(b - p.chunk_start[lo]) * OPTIM_CHUNK,
+                       [&](float& x, float& a) { average_update<COPY>(x, a, w); });
+}
+
+__global__ __launch_bounds__(256) void weight_swap_kernel(const OptimParams p) {
+    const int b = int(blockIdx.x);
+    const int lo = table_entry(p.chunk_start, p.n, b);
+    walk_chunk2<true>(p.e[lo], int64_t(b - p.chunk_start[lo]) * OPTIM_CHUNK, [](float& x, float& a) {
+        const float t = x;
+        x = a;
+        a = t;
+    });
+}
+
 }  // namespace
 }  // namespace lamp
 
@@ -1070,4 +1146,80 @@ int lamp_optim_step_ext(const lamp_optim_entry* entries, int32_t n, int32_t kind
             else if (mom) hipLaunchKernelGGL(optim_step_ext_kernel<OPT_SGD_MOMENTUM>, grid, block, 0, s, x);
             else hipLaunchKernelGGL(optim_step_ext_kernel<OPT_SGD>, grid, block, 0, s, x);
         });
+}
+
+// ---- lamp_weight_average / lamp_weight_swap ---------------------------------------------------------------------------
+// The rules of both (check_optim_entries' order over the two pointers they read): numel (DIMS), param / exp_avg (NULL),
+// 4-byte alignment (ALIGN), a param and an exp_avg that overlap without being identical (UNSUPPORTED).  `skip` says whether
+// an entry with identical pointers -- a no-op -- exists: the table is then copied without them.
+static int check_average_entries(const lamp_optim_entry* entries, int32_t n, bool& skip) {
+    skip = false;
+    for (int i = 0; i < n; ++i) {
+        const lamp_optim_entry& e = entries[i];
+        if (e.numel < 0) return LAMP_E_DIMS;
+        if (e.numel == 0) continue;
+        if (!e.param || !e.exp_avg) return LAMP_E_NULL;
+        const uintptr_t p = reinterpret_cast<uintptr_t>(e.param), a = reinterpret_cast<uintptr_t>(e.exp_avg);
+        if ((p | a) & 3u) return LAMP_E_ALIGN;
+        if (p == a) {
+            skip = true;
+            continue;
+        }
+        const uintptr_t gap = p < a ? a - p : p - a;
+        if (gap / sizeof(float) < uintptr_t(e.numel)) return LAMP_E_UNSUPPORTED;
+    }
+    return LAMP_OK;
+}
+
+// 2^31 chunks in one entry, asked before any launch (for_each_launch would answer after the launches in front of it)
+static bool average_chunks_served(const lamp_optim_entry* entries, int32_t n) {
+    for (int i = 0; i < n; ++i)
+        if ((entries[i].numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK >= (int64_t(1) << 31)) return false;
+    return true;
+}
+
+template <class Launch>
+static int average_launches(const lamp_optim_entry* entries, int32_t n, bool skip, OptimParams& p, Launch launch) {
+    if (!skip)
+        return for_each_launch(entries, n, p.chunk_start, p.n, [&](int slot, int i) { p.e[slot] = optim_entry(entries[i]); }, launch);
+    lamp_optim_entry* kept = new lamp_optim_entry[n];
+    int m = 0;
+    for (int i = 0; i < n; ++i)
+        if (entries[i].numel == 0 || entries[i].param != entries[i].exp_avg) kept[m++] = entries[i];
+    const int st = for_each_launch(kept, m, p.chunk_start, p.n, [&](int slot, int i) { p.e[slot] = optim_entry(kept[i]); }, launch);
+    delete[] kept;
+    return st;
+}
+
+int lamp_weight_average(const lamp_optim_entry* entries, int32_t n, double weight, lamp_stream_t stream) {
+    if (n < 0) return LAMP_E_DIMS;
+    if (!(weight >= 0.0 && weight <= 1.0)) return LAMP_E_UNSUPPORTED;      // (NaN fails both)
+    if (n == 0) return LAMP_OK;
+    if (!entries) return LAMP_E_NULL;
+    bool skip = false;
+    if (int st = check_average_entries(entries, n, skip)) return st;
+    if (!average_chunks_served(entries, n)) return LAMP_E_UNSUPPORTED;
+    const float w = float(weight);
+    if (w == 0.f) return LAMP_OK;                    // the average keeps its bits: nothing to launch
+    OptimParams p{};
+    p.lr = w;
+    const hipStream_t s = hipStream_t(stream);
+    return average_launches(entries, n, skip, p, [&](int64_t chunks) {
+        if (w == 1.f) hipLaunchKernelGGL(weight_average_kernel<true>, dim3(unsigned(chunks)), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(weight_average_kernel<false>, dim3(unsigned(chunks)), dim3(256), 0, s, p);
+    });
+}
+
+int lamp_weight_swap(const lamp_optim_entry* entries, int32_t n, lamp_stream_t stream) {
+    if (n < 0) return LAMP_E_DIMS;
+    if (n == 0) return LAMP_OK;
+    if (!entries) return LAMP_E_NULL;
+    bool skip = false;
+    if (int st = check_average_entries(entries, n, skip)) return st;
+    if (!average_chunks_served(entries, n)) return LAMP_E_UNSUPPORTED;
+    OptimParams p{};
+    const hipStream_t s = hipStream_t(stream);
+    return average_launches(entries, n, skip, p, [&](int64_t chunks) {
+        hipLaunchKernelGGL(weight_swap_kernel, dim3(unsigned(chunks)), dim3(256), 0, s, p);
+    });
 }

@@ -265,3 +265,175 @@ class SGD(_Base):
         else:
             self._launch(by_key)
         return loss
+
+
+def average_weight(kind, decay, warmup, n_averaged):
+    """The lerp weight of the update that follows `n_averaged` counted ones, a Python float (double), as torch takes it on the
+    host: 1 for the first (a copy); 'ema': 1 - d_t with d_t = decay, or min(decay, (1 + t) / (10 + t)) under warmup, t =
+    n_averaged; 'swa': 1 / (n_averaged + 1)."""
+    if n_averaged == 0:
+        return 1.0
+    if kind == 'swa':
+        return 1.0 / (n_averaged + 1)
+    d = float(decay)
+    if warmup:
+        d = min(d, (1.0 + n_averaged) / (10.0 + n_averaged))
+    return 1.0 - d
+
+
+class WeightAverage(object):
+    """An average of the weights kept beside them: kind 'ema' (a = a + (1 - decay)(p - a), optionally
+    with the warmup min(decay, (1 + t) / (10 + t))) or 'swa' (the running mean), torch.optim.swa_utils.AveragedModel's arithmetic
+    without its deep copy: one fp32 buffer per parameter, allocated here and never again, and ONE lamp_weight_average launch
+    per device and 72 parameters per update.
+
+        avg = WeightAverage(optimizer_params, kind='ema', decay=0.999)
+        loss.backward(); optimizer.step(); avg.update()
+        with avg.applied():            # the model holds the average: evaluate, save, ...
+            evaluate(model)            # (one lamp_weight_swap in, one out; the eval path's cached tables follow)
+
+    update() never looks at the optimizer: after a step that skip_nonfinite left out, the unchanged weights are averaged in, as
+    AveragedModel does.  `update_every=k` acts on every k-th call.  There are no running statistics in this model family, so an
+    average of the parameters is a complete model.  Not served: fp64 or bf16 averages, per-group decays, averaging of buffers,
+    nn.DataParallel replicas, a device-side count."""
+
+    def __init__(self, params, kind='ema', decay=0.999, warmup=False, update_every=1):
+        if kind not in ('ema', 'swa'):
+            raise ValueError("WeightAverage: kind %r is not 'ema' or 'swa'" % (kind,))
+        if not 0.0 <= float(decay) < 1.0:       # (false for NaN)
+            raise ValueError('WeightAverage: decay %r is not in [0, 1)' % (decay,))
+        if isinstance(update_every, bool) or int(update_every) != update_every or update_every < 1:
+            raise ValueError('WeightAverage: update_every %r: an integer >= 1' % (update_every,))
+        self.kind, self.decay, self.warmup, self.update_every = kind, float(decay), bool(warmup), int(update_every)
+        self.params, seen = [], set()
+        for p in params:
+            if id(p) in seen:
+                continue
+            seen.add(id(p))
+            if not (p.is_cuda and p.dtype == torch.float32):
+                raise RuntimeError('lamp_amd.optim updates fp32 parameters on a HIP device only; got %s %s. There is no CPU path.'
+                                   % (p.device, p.dtype))
+            if not p.is_contiguous():
+                raise RuntimeError('lamp_amd.optim expects contiguous parameters')
+            self.params.append(p)
+        self.buffers = [torch.zeros_like(p, memory_format=torch.contiguous_format, requires_grad=False) for p in self.params]
+        self.n_averaged = 0      # counted updates
+        self.n_calls = 0         # calls of update()
+        self.last_weight = None  # the weight of the last call of update(), None when update_every left it out
+        self._swapped = False
+        self._by_device = {}
+        for p, a in zip(self.params, self.buffers):
+            self._by_device.setdefault(p.device, []).append((p, a))
+        self._tables = {}        # device -> (the parameters' pointers, the ctypes table built from them)
+
+    def _launches(self):
+        """(device, entries, table) per device.  The buffers never move and the parameters rarely do (.to(), .data =): the
+        table is kept and rebuilt when a parameter's pointer is not the one it was built from."""
+        for dev, entries in self._by_device.items():
+            ptrs = [p.data_ptr() for p, _ in entries]
+            kept = self._tables.get(dev)
+            if kept is None or kept[0] != ptrs:
+                kept = self._tables[dev] = (ptrs, N.average_table('WeightAverage', entries))
+            yield dev, entries, kept[1]
+
+    def next_weight(self):
+        return average_weight(self.kind, self.decay, self.warmup, self.n_averaged)
+
+    def update(self):
+        """Fold the current weights into the average: host integers and one launch per device per 72 parameters."""
+        if self._swapped:
+            raise RuntimeError('WeightAverage.update() while the average is swapped in: the model holds the average and the '
+                               'buffers the trained weights')
+        self.n_calls += 1
+        if self.n_calls % self.update_every:
+            self.last_weight = None
+            return
+        w = self.last_weight = self.next_weight()
+        if self.buffers:
+            torch.autograd.graph.increment_version(self.buffers)
+        for dev, entries, table in self._launches():
+            with _on(dev):
+                N.weight_average(entries, w, table)
+        self.n_averaged += 1
+
+    def swap(self):
+        """Exchange the weights and their averages in place (one launch per device per 72 parameters).  The version counters
+        of both sides move, so the eval path's weights-only tables and a learnable label bias's folded buffer are rebuilt by the
+        next forward."""
+        if self.params:
+            torch.autograd.graph.increment_version(self.params + self.buffers)
+        for dev, entries, table in self._launches():
+            with _on(dev):
+                N.weight_swap(entries, table)
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def applied(self):
+        """The model holds the average inside the block and the trained weights after it, also after an exception."""
+        if self._swapped:
+            raise RuntimeError('WeightAverage.applied() does not nest: the average is already swapped in')
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    def _not_swapped(self, who):
+        if self._swapped:
+            raise RuntimeError('WeightAverage.%s while the average is swapped in: the buffers hold the trained weights' % who)
+
+    def copy_to(self, target):
+        """Load the average OUT OF PLACE, by torch copies: into the parameters this average was built over (`target` the
+        nn.Module that owns them: the model then holds the average for good, and the buffers keep it), or into an iterable
+        of as many parameters in this average's order.  Another module takes load_state_dict(averaged_state_dict(model))."""
+        self._not_swapped('copy_to()')
+        if isinstance(target, torch.nn.Module):
+            own = {id(p): a for p, a in zip(self.params, self.buffers)}
+            pairs = [(p, own[id(p)]) for p in target.parameters() if id(p) in own]
+            if len(pairs) != len(own):
+                raise ValueError('WeightAverage.copy_to: the module owns %d of the %d averaged parameters; load '
+                                 'averaged_state_dict(model) into another module' % (len(pairs), len(own)))
+        else:
+            ps = list(target)
+            if len(ps) != len(self.buffers) or any(p.shape != a.shape for p, a in zip(ps, self.buffers)):
+                raise ValueError('WeightAverage.copy_to: %d parameters do not match the %d averaged ones in count or shape'
+                                 % (len(ps), len(self.buffers)))
+            pairs = list(zip(ps, self.buffers))
+        with torch.no_grad():
+            for p, a in pairs:
+                p.copy_(a)
+
+    def averaged_state_dict(self, model):
+        """model.state_dict() with the averaged tensors in the places of the parameters this average covers (every name of a
+        tied weight).  Nothing is cloned and nothing is swapped: the values are the live tensors, as state_dict()'s are."""
+        self._not_swapped('averaged_state_dict()')
+        own = {id(p): a for p, a in zip(self.params, self.buffers)}
+        sd = model.state_dict()
+        for name, p in model.named_parameters(remove_duplicate=False):
+            if id(p) in own and name in sd:
+                sd[name] = own[id(p)]
+        return sd
+
+    def state_dict(self, buffers=True):
+        """kind, decay, warmup, update_every, n_averaged, n_calls and (unless buffers=False) the averages in parameter order."""
+        self._not_swapped('state_dict()')
+        sd = dict(kind=self.kind, decay=self.decay, warmup=self.warmup, update_every=self.update_every,
+                  n_averaged=self.n_averaged, n_calls=self.n_calls)
+        if buffers:
+            sd['buffers'] = list(self.buffers)
+        return sd
+
+    def load_state_dict(self, sd):
+        """The buffers are written in place (their pointers stay); a state without 'buffers' restores the schedule alone."""
+        self._not_swapped('load_state_dict()')
+        fresh = WeightAverage([], sd['kind'], sd['decay'], sd['warmup'], sd['update_every'])      # (validates)
+        bufs = sd.get('buffers')
+        if bufs is not None:
+            if len(bufs) != len(self.buffers) or any(b.shape != a.shape for b, a in zip(bufs, self.buffers)):
+                raise ValueError('WeightAverage.load_state_dict: %d buffers do not match the %d averaged parameters in count or '
+                                 'shape' % (len(bufs), len(self.buffers)))
+            with torch.no_grad():
+                for b, a in zip(bufs, self.buffers):
+                    a.copy_(b)
+        self.kind, self.decay, self.warmup, self.update_every = fresh.kind, fresh.decay, fresh.warmup, fresh.update_every
+        self.n_averaged, self.n_calls = int(sd['n_averaged']), int(sd['n_calls'])

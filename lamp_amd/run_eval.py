@@ -29,6 +29,9 @@ the five thresholded figures at the fitted thresholds join the JSON line as tune
 tuned_maF1, with tune_criterion, tune_split, n_labels_tuned, thresholds (a list; Infinity = the label is never predicted) and
 tune_seconds; the figures at -br_threshold stay.  -tune_thresholds checkpoint takes the thresholds run_train -tune_thresholds
 stored in the checkpoint.
+-weights auto|raw|avg picks between the trained weights ('model') and the EMA / SWA average ('model_avg') of a
+run_train -weight_avg checkpoint; auto, the default, takes the average when the checkpoint has one, and the JSON line then
+carries "weights": "avg".  A checkpoint without the key loads as it always has.
 """
 import argparse
 import json
@@ -109,6 +112,10 @@ def parse(argv=None):
     ap.add_argument('-tune_split', default='valid', choices=['train', 'valid', 'test'], help='the split the thresholds are fitted on')
     ap.add_argument('-tune_scope', default='label', choices=['label', 'global'],
                     help='label = one threshold per label; global = one threshold for all labels, fitted on the flattened matrix')
+    ap.add_argument('-weights', type=str, choices=['auto', 'raw', 'avg'], default='auto',
+                    help="which weights of a run_train -weight_avg checkpoint to evaluate: avg = 'model_avg' (the EMA / SWA "
+                         "average), raw = 'model' (as trained), auto = model_avg when the checkpoint has it, model otherwise -- "
+                         'every checkpoint without the key loads as it always has')
     ap.add_argument('-seed', type=int, default=0, help='weight init seed when no checkpoint is given')
     ap.add_argument('-gpus', type=int, default=1, help='processes (one per GPU) the batches are sharded over')
     opt = ap.parse_args(argv)
@@ -196,6 +203,22 @@ def checkpoint_settings(ckpt):
         return (ckpt['model'], bool(getattr(settings, 'enc_self_att', False)),
                 getattr(settings, 'attn_type', None) or 'softmax')
     return ckpt, False, 'softmax'
+
+
+def checkpoint_weights(ckpt, which='auto'):
+    """(state_dict, averaged) of a LOADED checkpoint under -weights: 'raw' = ckpt['model'] (or a bare state dict itself), 'avg'
+    = ckpt['model_avg'], the average run_train -weight_avg stored -- a ValueError naming the key where it is absent -- and
+    'auto' = the average when there is one."""
+    if which not in ('auto', 'raw', 'avg'):
+        raise ValueError("-weights %r: auto, raw or avg" % (which,))
+    wrapped = isinstance(ckpt, dict) and 'model' in ckpt
+    has_avg = wrapped and ckpt.get('model_avg') is not None
+    if which == 'avg' and not has_avg:
+        raise ValueError("-weights avg: the checkpoint holds no 'model_avg' (run_train -weight_avg ema|swa stores it once "
+                         "averaging has begun)")
+    if has_avg and which != 'raw':
+        return ckpt['model_avg'], True
+    return (ckpt['model'] if wrapped else ckpt), False
 
 
 def load_checkpoint_label_bias(ckpt):
@@ -287,6 +310,12 @@ def main(argv=None):
     torch.manual_seed(opt.seed)
     ckpt = load_checkpoint_object(opt.checkpoint) if opt.checkpoint else None
     state, live, attn_type = checkpoint_settings(ckpt) if ckpt is not None else (None, False, 'softmax')
+    averaged = False
+    if ckpt is not None or opt.weights == 'avg':
+        try:
+            state, averaged = checkpoint_weights(ckpt, opt.weights)
+        except ValueError as e:
+            raise SystemExit('%s: %s' % (opt.checkpoint or 'no -checkpoint was given', e))
     live = live or opt.enc_self_att
     if opt.attn_type != 'softmax':
         attn_type = opt.attn_type
@@ -354,6 +383,8 @@ def main(argv=None):
     out = {'split': opt.split, 'n_samples': batches.n_insts, 'n_labels': n_labels, 'n_batches': len(batches),
            'bce_total': bce_total, 'seconds': dt, 'samples_per_s': batches.n_insts / dt,
            'checkpoint': opt.checkpoint, 'onehot': opt.onehot, 'matmul_precision': model.matmul_precision, 'n_gpus': world, 'backend': plane.backend, 'backend_note': plane.note}
+    if averaged:
+        out['weights'] = 'avg'
     out.update(multilabel_metrics(preds, targets, opt.br_threshold))
     if opt.all_metrics and rank == 0:
         from .metrics import RANKING_KEYS, compute_metrics

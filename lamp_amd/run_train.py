@@ -49,8 +49,19 @@ the first four (torch: clip_grad_norm_ in front of every step, torch.optim.AdamW
 -skip_nonfinite exists with -optim_impl lamp only and adds steps_skipped to each epoch's record, read where the loop already
 synchronises.  Each adds .clip_<v> / .wd_<v> / .mom_<v> / .skipnf to the results name and its flag to the checkpoint's settings,
 and nothing when it is not given.
+
+-weight_avg ema|swa keeps an average of the weights (lamp_amd.optim.WeightAverage) beside the trained
+ones: one lamp_weight_average launch after every optimizer step (-avg_every k: after every k-th) from the first step of epoch
+-avg_start_epoch on; ema uses -ema_decay (with -ema_warmup: min(decay, (1 + t) / (10 + t))), swa the running mean.  Once
+averaging has begun each epoch's valid and test epochs run with the average swapped in -- thresholds, -at_k, -label_ranking and
+the valid loss -save_mode best compares are then the averaged model's, and the epoch's record says "weights": "avg" -- and the
+weights are swapped back before the next epoch trains.  The checkpoint keeps 'model' as trained (-load_pretrained resumes
+that; the average itself is not resumed and starts again), and gains 'weight_avg' (the average's state without buffers) and,
+once an average exists, 'model_avg' (run_eval -weights auto|raw|avg).  The flags add .wavg_<kind>_<decay or 'swa'>[_w][_e<k>]
+[_s<epoch>] to the results name and themselves to the checkpoint's settings, and nothing when -weight_avg is not given.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -159,6 +170,17 @@ def parse(argv=None):
     ap.add_argument('-skip_nonfinite', action='store_true',
                     help='-optim_impl lamp only: a batch whose gradient norm is inf or NaN changes no weight and no moment (the '
                          "decision is taken on the device); the epoch's log line reports steps_skipped")
+    ap.add_argument('-weight_avg', type=str, choices=['ema', 'swa'], default=None,
+                    help='keep an average of the weights beside them (lamp_amd.optim.WeightAverage, DESIGN.md section 8.14; one '
+                         'lamp_weight_average launch after every optimizer step, with either -optim_impl): ema = exponential '
+                         'moving average with -ema_decay, swa = the running mean.  Once averaging has begun the valid and test '
+                         "epochs run on the average, and the checkpoint holds it as 'model_avg' beside the trained 'model'")
+    ap.add_argument('-ema_decay', type=float, default=0.999, help='-weight_avg ema: the decay, in [0, 1)')
+    ap.add_argument('-ema_warmup', action='store_true',
+                    help='-weight_avg ema: the decay of update t is min(-ema_decay, (1 + t) / (10 + t))')
+    ap.add_argument('-avg_every', type=int, default=1, help='-weight_avg: average after every k-th optimizer step only')
+    ap.add_argument('-avg_start_epoch', type=int, default=1,
+                    help="-weight_avg: the 1-based epoch whose first step begins the average (SWA's usual last quarter of training)")
     ap.add_argument('-optim_impl', choices=['lamp', 'torch'], default=DEFAULT_OPTIM_IMPL,
                     help='lamp = lamp_amd.optim (one lamp_optim_step launch per step); torch = torch.optim (fused=True for adam)')
     ap.add_argument('-streams', type=int, default=4, choices=[1, 2, 3, 4], help='batches in flight in the valid / test epochs')
@@ -260,6 +282,48 @@ def optimizer_controls(opt):
     return name
 
 
+WEIGHT_AVG_FLAGS = ('weight_avg', 'ema_decay', 'ema_warmup', 'avg_every', 'avg_start_epoch')
+
+
+def weight_average_controls(opt):
+    """-weight_avg and its flags: normalised on `opt` (None = not given), what is not served refused, -> their part of the
+    results name ('' without -weight_avg): .wavg_<kind>_<decay or 'swa'>[_w][_e<k>][_s<epoch>]."""
+    opt.weight_avg = getattr(opt, 'weight_avg', None) or None
+    if opt.weight_avg is None:
+        return ''
+    if opt.weight_avg not in ('ema', 'swa'):
+        raise ValueError('-weight_avg %r: ema or swa' % (opt.weight_avg,))
+    opt.ema_decay = float(getattr(opt, 'ema_decay', 0.999))
+    opt.ema_warmup = bool(getattr(opt, 'ema_warmup', False))
+    opt.avg_every = int(getattr(opt, 'avg_every', 1))
+    opt.avg_start_epoch = int(getattr(opt, 'avg_start_epoch', 1))
+    if not 0.0 <= opt.ema_decay < 1.0:
+        raise ValueError('-ema_decay %r: a decay in [0, 1)' % (opt.ema_decay,))
+    if opt.avg_every < 1:
+        raise ValueError('-avg_every %r: an integer >= 1' % (opt.avg_every,))
+    if opt.avg_start_epoch < 1:
+        raise ValueError('-avg_start_epoch %r: epochs count from 1' % (opt.avg_start_epoch,))
+    ema = opt.weight_avg == 'ema'
+    name = '.wavg_%s_%s' % (opt.weight_avg, opt.ema_decay if ema else 'swa')
+    if ema and opt.ema_warmup:
+        name += '_w'
+    if opt.avg_every != 1:
+        name += '_e%d' % opt.avg_every
+    if opt.avg_start_epoch != 1:
+        name += '_s%d' % opt.avg_start_epoch
+    return name
+
+
+def build_weight_average(optimizer, opt):
+    """-> the optim.WeightAverage of -weight_avg over every parameter the optimizer holds, or None without the flag."""
+    if getattr(opt, 'weight_avg', None) is None:
+        return None
+    from . import optim
+    params = [p for g in optimizer.param_groups for p in g['params']]
+    return optim.WeightAverage(params, kind=opt.weight_avg, decay=opt.ema_decay if opt.weight_avg == 'ema' else 0.0,
+                               warmup=opt.ema_warmup and opt.weight_avg == 'ema', update_every=opt.avg_every)
+
+
 def derive(opt):
     """config_args.py:80-259 for the flags above."""
     if opt.gpus != 1:
@@ -348,6 +412,7 @@ def derive(opt):
             raise ValueError('-pos_weight_cap %r: a positive finite number' % (opt.pos_weight_cap,))
         name += '.posw_%s_%s' % (opt.pos_weight, opt.pos_weight_cap)
     name += optimizer_controls(opt)
+    name += weight_average_controls(opt)
     if opt.name:
         name += '.' + str(opt.name)
     opt.model_name = os.path.join(opt.results_dir, opt.dataset, name)
@@ -445,7 +510,9 @@ def checkpoint_settings(opt):
     """The Namespace that travels in the checkpoint: plain values only, so that it unpickles anywhere.  `learn_label_bias`
     and `tune_thresholds` travel only when they are set: without the flags the settings are what they were before they
     existed.  Likewise `loss_fn` with the flags of the chosen objective, and `pos_weight` with its cap."""
-    drop = {'loss_options', 'rank_loss'}      # (the run's own objects, None for plain BCE: never a setting)
+    drop = {'loss_options', 'rank_loss', 'weight_average'}      # (the run's own objects, None by default: never a setting)
+    if getattr(opt, 'weight_avg', None) is None:      # (-weight_avg's flags travel with it, never without)
+        drop.update(WEIGHT_AVG_FLAGS)
     drop.update(('label_ranking', 'at_k'))    # (reporting only: a checkpoint does not depend on what was printed beside it)
     loss_fn = getattr(opt, 'loss_fn', 'bce')
     if loss_fn == 'bce':
@@ -462,10 +529,16 @@ def checkpoint_settings(opt):
                                  and (k not in ('learn_label_bias', 'tune_thresholds') or v) and k not in drop})
 
 
-def save_model(opt, epoch_i, model, valid_loss, valid_losses, label_thresholds=None):
+def save_model(opt, epoch_i, model, valid_loss, valid_losses, label_thresholds=None, weight_average=None):
     """utils/utils.py:228-241, `>=` included (see the module docstring).  -> the path written, or None.  With
-    -tune_thresholds the epoch's fitted thresholds travel beside the weights."""
+    -tune_thresholds the epoch's fitted thresholds travel beside the weights.  With -weight_avg (`weight_average`, not
+    swapped in): 'weight_avg', the average's state without its buffers, and -- once it holds an average -- 'model_avg', the
+    state dict with the averaged weights; 'model' stays what was trained."""
     checkpoint = {'model': model.state_dict(), 'settings': checkpoint_settings(opt), 'epoch': epoch_i}
+    if weight_average is not None:
+        checkpoint['weight_avg'] = weight_average.state_dict(buffers=False)
+        if weight_average.n_averaged > 0:
+            checkpoint['model_avg'] = weight_average.averaged_state_dict(model)
     if label_thresholds is not None:
         checkpoint['label_thresholds'] = label_thresholds.detach().to('cpu', torch.float32).contiguous()
         checkpoint['tune_criterion'] = opt.tune_thresholds
@@ -504,6 +577,7 @@ def main(argv=None):
     optimizer = build_optimizer(model, opt)
     opt.loss_options = build_loss_options(opt, data, device)      # (None for plain BCE; never part of the checkpoint's settings)
     opt.rank_loss = build_rank_loss(opt)                          # (likewise; None unless -loss_fn is a ranking loss)
+    wavg = build_weight_average(optimizer, opt)                   # (None without -weight_avg: nothing below then differs)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=opt.lr_step_size, gamma=opt.lr_decay, last_epoch=-1)
@@ -532,6 +606,8 @@ def main(argv=None):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             on_dev = {}
+            if wavg is not None and epoch_i + 1 >= opt.avg_start_epoch:
+                opt.weight_average = wavg                         # (train_batch updates it after every optimizer.step())
             _, _, train_loss = train_epoch(model, train_data, optimizer, opt, device=device, prefetch=opt.prefetch,
                                            device_results=on_dev)
             torch.cuda.synchronize()
@@ -547,32 +623,38 @@ def main(argv=None):
                 out['steps_skipped'], skipped_before = total - skipped_before, total
             losses = {}
             label_thresholds = None
-            for split, batches in (('valid', valid_data), ('test', test_data)):
-                t0 = time.perf_counter()
-                on_dev = {}
-                _, _, loss = test_epoch(model, batches, n_labels, opt.test_batch_size, device, streams=opt.streams,
-                                        prefetch=opt.prefetch, int_preds=opt.int_preds, device_results=on_dev)
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t0
-                losses[split] = loss / batches.n_insts
-                metrics[split] = compute_metrics(on_dev['probs'], on_dev['targets'], losses[split], opt.br_threshold, dt / 60,
-                                                 **report)
-                if opt.tune_thresholds and split == 'valid':   # (valid comes first: the test epoch below uses them)
-                    fit = tune_thresholds(on_dev['probs'], on_dev['targets'], opt.tune_thresholds, opt.br_threshold)
-                    label_thresholds = fit['threshold']
-                    out['n_labels_tuned'] = int(fit['tuned'].sum())
-                    out['tune_criterion'] = opt.tune_thresholds
-                if label_thresholds is not None and split == 'test':
-                    tuned = compute_metrics(on_dev['probs'], on_dev['targets'], losses[split], opt.br_threshold, dt / 60,
-                                            all_metrics=False, thresholds=label_thresholds)
-                    metrics[split].update({'tuned_' + k: tuned[k] for k in ('ACC', 'HA', 'ebF1', 'miF1', 'maF1')})
-                out['%s_loss' % split] = losses[split]
-                out['%s_samples_per_s' % split] = batches.n_insts / dt
+            # once averaging has begun, valid and test (thresholds, -at_k and -label_ranking with them, and the loss -save_mode
+            # best compares) are the averaged model's: swapped in here, swapped back below, also on an exception
+            averaged = wavg is not None and wavg.n_averaged > 0
+            with (wavg.applied() if averaged else contextlib.nullcontext()):
+                for split, batches in (('valid', valid_data), ('test', test_data)):
+                    t0 = time.perf_counter()
+                    on_dev = {}
+                    _, _, loss = test_epoch(model, batches, n_labels, opt.test_batch_size, device, streams=opt.streams,
+                                            prefetch=opt.prefetch, int_preds=opt.int_preds, device_results=on_dev)
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    losses[split] = loss / batches.n_insts
+                    metrics[split] = compute_metrics(on_dev['probs'], on_dev['targets'], losses[split], opt.br_threshold, dt / 60,
+                                                     **report)
+                    if opt.tune_thresholds and split == 'valid':   # (valid comes first: the test epoch below uses them)
+                        fit = tune_thresholds(on_dev['probs'], on_dev['targets'], opt.tune_thresholds, opt.br_threshold)
+                        label_thresholds = fit['threshold']
+                        out['n_labels_tuned'] = int(fit['tuned'].sum())
+                        out['tune_criterion'] = opt.tune_thresholds
+                    if label_thresholds is not None and split == 'test':
+                        tuned = compute_metrics(on_dev['probs'], on_dev['targets'], losses[split], opt.br_threshold, dt / 60,
+                                                all_metrics=False, thresholds=label_thresholds)
+                        metrics[split].update({'tuned_' + k: tuned[k] for k in ('ACC', 'HA', 'ebF1', 'miF1', 'maF1')})
+                    out['%s_loss' % split] = losses[split]
+                    out['%s_samples_per_s' % split] = batches.n_insts / dt
             valid_losses.append(losses['valid'])
+            if wavg is not None:
+                out['weights'] = 'avg' if averaged else 'raw'
             out['metrics'] = {k: _json_metrics(v) for k, v in metrics.items()}
             out['checkpoint'] = None
             if 'test' not in opt.model_name:   # runner.py:85
-                out['checkpoint'] = save_model(opt, epoch_i, model, losses['valid'], valid_losses, label_thresholds)
+                out['checkpoint'] = save_model(opt, epoch_i, model, losses['valid'], valid_losses, label_thresholds, wavg)
             loss_file.write('%d,%s,%s,%s\n' % (epoch_i + 1, train_loss, losses['valid'], losses['test']))
             loss_file.flush()
             history.append(out)

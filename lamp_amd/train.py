@@ -137,7 +137,8 @@ def train_batch(model, optimizer, opt, src, adj, gold_d, probs_rows, loss_rows):
     this batch's rows of the epoch's prediction matrix and loss-sum matrix.  `opt.loss_options` (a LossOptions, or absent / None
     for the reference's BCE) picks the trained objective: the loss launch is then lamp_multilabel_loss_train and the row sums
     are that loss.  `opt.rank_loss` (a RankLossOptions) picks a ranking objective instead: lamp_rank_loss_train, whose row
-    numbers are R_r + bce_weight * bce_row_r / L; both options together are a ValueError.  Nothing here waits for the device."""
+    numbers are R_r + bce_weight * bce_row_r / L; both options together are a ValueError.  `opt.weight_average` (an
+    optim.WeightAverage, or absent / None) is updated after optimizer.step(): one more launch.  Nothing here waits for the device."""
     optimizer.zero_grad()
     pred, enc_output, *results = model(src, adj, None, gold_d, return_attns=opt.attns_loss, int_preds=opt.int_preds)
     mats = [pred]
@@ -170,6 +171,9 @@ def train_batch(model, optimizer, opt, src, adj, gold_d, probs_rows, loss_rows):
         grads += g
     torch.autograd.backward(mats, grads)
     optimizer.step()
+    wa = getattr(opt, 'weight_average', None)      # (an optim.WeightAverage, or absent / None: the loop as it has always been)
+    if wa is not None:
+        wa.update()
 
 
 def n_loss_matrices(model, opt):
